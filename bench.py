@@ -7,6 +7,13 @@ BASELINE.json metric "images/sec (whole node), MNIST CNN sync-SGD at 1/2/4/8 MI3
 batch gather, forward, fused softmax-CE, backward, RCCL all-reduce of the gradients, fused SGD update.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--model lenet5] [--batch-per-gpu B]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, settles the clocks, warms up, times the K steps and prints the result line.  ``--full``
+adds everything else the benchmark measures or checks: the gradient correctness guard (fused engine against
+the per-layer kernels, plus a CPU oracle for some models) and the async parameter-server comparison.
+``--dump-outputs DIR`` writes what the last timed step returned (``stats.npy``: [loss sum, correct]) and left
+behind (``weights.npy``: the flat fp32 master weights) as float32 ``.npy`` files; such a run takes a fixed
+number of settle steps, so two runs with the same arguments train on identical inputs.
 For N > 1 either launch with torch.distributed.run (one rank per GPU), or run it plainly: with
 WORLD_SIZE unset, ``--gpus N`` makes this process a launcher that starts N fresh rank processes
 (before anything touches the GPU) and exits with the first failing child's code.  Rank 0 prints
@@ -120,6 +127,29 @@ def correctness_guard(model: str, B: int, dev, data, labels) -> dict:
 
 _ORACLE_MODELS = {"resnet18_cifar": 64, "keras_cnn": 256}
 
+DUMP_MAX_BYTES = 64 << 20  # budget of one --dump-outputs directory
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write each array as ``<out_dir>/<name>.npy`` (float32), at most DUMP_MAX_BYTES in all.  The smallest
+    arrays are served first; one that is over an equal share of what is left is cut to a fixed, seeded, sorted
+    sample of its flattened elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    left = (DUMP_MAX_BYTES - 4096 * len(arrays)) // 4  # elements; 4 KB set aside per .npy header
+    rec = {}
+    for k, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].numel())):
+        a = t.detach().float().cpu().contiguous().numpy()
+        share = left // (len(arrays) - k)
+        if a.size > share:
+            pick = np.sort(np.random.RandomState(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[pick]
+        left -= a.size
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        rec[name] = list(a.shape)
+    return rec
+
 
 def _cpu_oracle(model, fast, x, y, Bo) -> dict:
     """``fast``: a freshly built GPU engine (its dropout counters at the start, like the CPU engine's: both draw
@@ -173,12 +203,20 @@ def main():
                          "(profiles/r6/lenet_clock_ramp_r6.txt), so without it a short timed run measures the ramp; "
                          "0 disables; reported as \"settle\" in the JSON")
     ap.add_argument("--async-steps", type=int, default=None,
-                    help="after the sync measurement, also time this many steps of the async parameter-server "
-                         "engine and report the async speedup (default: --steps; 0 disables)")
+                    help="with --full: after the sync measurement, also time this many steps of the async "
+                         "parameter-server engine and report the async speedup (default: --steps; 0 disables)")
     ap.add_argument("--json-extra", action="store_true", help="add diagnostic fields")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the correctness guard (see --no-check) "
+                         "and the async parameter-server comparison (see --async-steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (stats.npy: [loss sum, "
+                         "correct]; weights.npy: the flat fp32 master weights after its update) as float32 .npy "
+                         "files into DIR; the settle phase then takes a fixed number of steps (not a time), so the "
+                         "inputs of every step are the same from run to run")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the correctness guard (1-step gradient vs the per-layer kernels); the loss and "
-                         "finiteness checks of the timed run always run")
+                    help="with --full: skip the correctness guard (1-step gradient vs the per-layer kernels); the "
+                         "loss and finiteness checks of the timed run always run")
     ap.add_argument("--phases", type=int, default=0,
                     help="after timing, run this many EAGER steps with hipEvent phase timers and report the "
                          "data/compute/comm/update breakdown (diagnostic, not part of the timed number)")
@@ -245,7 +283,9 @@ def main():
         (``scripts/launch_overhead_probe.py --ramp``: LeNet-5 B = 4096 62.4 -> 57.1 us per step), so a
         short timed run would measure the power manager's ramp, not the step.  Every rank runs the same
         number of chunks (rank 0 decides after each one): the steps are complete training steps, with the
-        same collectives on every rank."""
+        same collectives on every rank.  With ``--dump-outputs`` the step count is fixed instead (all the
+        chunks that fit under SETTLE_MAX_STEPS), so the timed steps see the same weights and batches in
+        every run."""
         if args.settle_ms <= 0 or dev.type != "cuda":
             return
         u = getattr(tr, "_multi_u", 0) if multi else 0
@@ -261,7 +301,8 @@ def main():
             n += chunk
             chunks += 1
             sync()
-            go = (time.perf_counter() - t0) * 1e3 < args.settle_ms and n + chunk <= SETTLE_MAX_STEPS
+            go = ((args.dump_outputs is not None or (time.perf_counter() - t0) * 1e3 < args.settle_ms)
+                  and n + chunk <= SETTLE_MAX_STEPS)
             if world > 1:
                 f = torch.tensor([1 if go else 0], dtype=torch.int32, device=dev)
                 dist.broadcast(f, src=0)
@@ -318,16 +359,19 @@ def main():
     check = {"final_loss_finite": bool(torch.isfinite(torch.tensor(loss))), "weights_finite": w_finite}
     ms = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"stats": st, "weights": net.store.master})
     phases = None
     if args.phases > 0 and args.mode == "sync" and dev.type == "cuda":
         phases = {k: round(v, 4) for k, v in trainer.timed_eager_steps(args.phases).items()}
-    if not args.no_check and dev.type == "cuda":
+    if args.full and not args.no_check and dev.type == "cuda":
         check["gradient"] = correctness_guard(args.model, B, dev, data, labels)
     check["ok"] = (check["final_loss_finite"] and check["weights_finite"]
                    and check.get("gradient", {"ok": True})["ok"])
     async_rec = None
     async_steps = args.steps if args.async_steps is None else args.async_steps
-    if args.mode == "sync" and async_steps > 0 and dev.type == "cuda":
+    if args.full and args.mode == "sync" and async_steps > 0 and dev.type == "cuda":
         # BASELINE metric "...; async speedup": same model / batch / rank count through the async engine
         try:
             anet = build_model(args.model, device=dev, seed=0)
@@ -394,6 +438,8 @@ def main():
             out["async"] = async_rec
         if phases is not None:
             out["phases_ms_eager"] = phases
+        if dumped is not None:
+            out["dumped"] = dumped
         if diag_active():
             out["diagnostics"] = diag_active()  # a diagnostic run: never a production number
         if os.environ.get("DISTRIFLOW_DIAG", "").strip():

@@ -11,7 +11,8 @@ from distriflow_amd.checkpoint import (VersionedStore, load_flat, load_layers_mo
 from distriflow_amd.models.distri_model import CheckpointedServerModel, DynamicServerModel, fetch_model
 from distriflow_amd.models.zoo import build_model, keras_cnn_topology
 
-REF_MODEL_JSON = "/root/reference/experiment/mnist/model.json"
+# the reference experiment's model.json (topology + weights manifest, no weights), stored with the tests
+REF_MODEL_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "keras_cnn_model.json")
 
 
 def test_layers_model_round_trip(tmp_path):
@@ -31,8 +32,6 @@ def test_layers_model_round_trip(tmp_path):
 
 
 def test_manifest_matches_reference_model_json(tmp_path):
-    if not os.path.exists(REF_MODEL_JSON):
-        pytest.skip("reference not mounted")
     ref = json.load(open(REF_MODEL_JSON))
     ref_w = [(w["name"], w["shape"]) for g in ref["weightsManifest"] for w in g["weights"]]
     net = build_model("keras_cnn", "cpu")
@@ -51,8 +50,9 @@ def test_sharded_manifest_read(tmp_path):
 
 
 def test_fetch_model_from_reference_topology():
-    net = fetch_model(REF_MODEL_JSON if os.path.exists(REF_MODEL_JSON) else "keras_cnn", device="cpu")
+    net = fetch_model(REF_MODEL_JSON, device="cpu")
     assert net.num_params() == 600165
+    assert json.load(open(REF_MODEL_JSON))["modelTopology"] == keras_cnn_topology()  # the bundled copy is the same
 
 
 def test_flat_vars_round_trip(tmp_path):
