@@ -104,10 +104,12 @@ __global__ __launch_bounds__(kPSBlock) void ps_fetch_pull_kernel(PSArgs a) {
       }
     }
   }
-  if (b == 0) {
+  if (b == 0 && a.claim_given != 2) {  // (2: a checkpoint's drain -- no claim, the claimed id stays)
     // FCFS microbatch id (remote atomic on the server's cursor) + its example indices
     __shared__ long long s_bid;
-    if (a.done_epoch != nullptr) {
+    if (a.claim_given != 0) {  // resumed: the microbatch this rank had claimed when the checkpoint was taken
+      if (t == 0) s_bid = a.claim_bid;
+    } else if (a.done_epoch != nullptr) {
       claim_microbatch(a, t, &s_bid);
     } else if (t == 0) {
       s_bid = (long long)(__hip_atomic_fetch_add(a.batch_ctr, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) %
@@ -496,6 +498,9 @@ static bool ps_owner_ok(const PSArgs& a) {
 hipError_t ps_fetch_pull(const PSArgs& a, hipStream_t st) {
   if (a.n <= 0 || (a.n & 3) || !ps_shards_ok(a) || !ps_owner_ok(a) ||
       (a.perm != nullptr && (a.B <= 0 || (a.B & 1) || a.nbatches <= 0)))
+    return hipErrorInvalidValue;
+  // a given id indexes the perm table (ps_stage_indices): it must name one of its rows
+  if (a.claim_given == 1 && (a.perm == nullptr || a.claim_bid < 0 || (a.claim_bid & 0xffffffffLL) >= a.nbatches))
     return hipErrorInvalidValue;
   ps_fetch_pull_kernel<<<ps_excl_grid(a), kPSBlock, 0, st>>>(a);
   return hipGetLastError();

@@ -1937,8 +1937,16 @@ class PSComm {
       check_hip(hipMemcpy(v.data(), shared_ + 256, (size_t)nbatches_ * 4, hipMemcpyDeviceToHost), "ps done");
     return std::vector<int64_t>(v.begin(), v.end());
   }
-  void fetch_pull(torch::Tensor w, c10::optional<torch::Tensor> perm, c10::optional<torch::Tensor> idx) {
+  // bid: take this microbatch id (epoch << 32 | batch: a checkpoint's in-flight claim) instead of claiming
+  void fetch_pull(torch::Tensor w, c10::optional<torch::Tensor> perm, c10::optional<torch::Tensor> idx,
+                  c10::optional<int64_t> bid = c10::nullopt) {
     dfa::PSArgs a = args();
+    if (bid.has_value()) {
+      TORCH_CHECK(perm.has_value() && perm->defined(), "ps: a given microbatch id needs the perm table");
+      TORCH_CHECK(*bid >= 0 && (*bid & 0xffffffffLL) < perm->size(0), "ps: microbatch id out of range");
+      a.claim_given = 1;
+      a.claim_bid = *bid;
+    }
     need(w, at::kFloat, "ps local master");
     TORCH_CHECK(w.numel() == n_ && w.get_device() == dev_, "ps: local master mismatch");
     a.w = w.data_ptr<float>();
@@ -2163,7 +2171,25 @@ class PSComm {
   }
   // the owner's drain alone (a pull into `w` without a microbatch claim): adds every flagged slot of this
   // rank's inbox into its shard; after the last step of every rank, one drain per rank settles the master
-  void drain(torch::Tensor w) { fetch_pull(w, c10::nullopt, c10::nullopt); }
+  // quiesced (a checkpoint, nobody stepping): the drain claims no microbatch (the cursor, claimed_epoch and this
+  // rank's claimed id stay) and the refresh record kPSVMin is put back, so the next step decides as without it
+  void drain(torch::Tensor w, bool quiesced = false) {
+    if (!quiesced) {
+      fetch_pull(w, c10::nullopt, c10::nullopt, c10::nullopt);
+      return;
+    }
+    dfa::PSArgs a = args();
+    need(w, at::kFloat, "ps local master");
+    TORCH_CHECK(w.numel() == n_ && w.get_device() == dev_, "ps: local master mismatch");
+    a.w = w.data_ptr<float>();
+    a.claim_given = 2;
+    unsigned vmin = 0;
+    check_hip(hipStreamSynchronize(cur_stream()), "ps drain sync");
+    check_hip(hipMemcpy(&vmin, local_ + 1024 + 4 * dfa::kPSVMinWord, 4, hipMemcpyDeviceToHost), "ps vmin rd");
+    check_hip(dfa::ps_fetch_pull(a, cur_stream()), "ps_fetch_pull");
+    check_hip(hipStreamSynchronize(cur_stream()), "ps drain sync");
+    check_hip(hipMemcpy(local_ + 1024 + 4 * dfa::kPSVMinWord, &vmin, 4, hipMemcpyHostToDevice), "ps vmin wr");
+  }
   // [drained sequence count of every owner]
   std::vector<int64_t> owner_prefix() const {
     std::vector<unsigned> v(world_, 0);
@@ -2197,6 +2223,107 @@ class PSComm {
     check_hip(hipMemcpy(&ctr, shared_ + 16, 8, hipMemcpyDeviceToHost), "ps ctr");
     return {(int64_t)h[0], (int64_t)h[1], (int64_t)h[2], (int64_t)h[3], (int64_t)h[4], (int64_t)h[5],
             (int64_t)ver[0], (int64_t)ctr, (int64_t)h[6], (int64_t)ver[2]};
+  }
+  // ---- checkpoint / resume of the control state (the caller guarantees that nobody is stepping).  Offsets:
+  // the layout at the top of csrc/async_ps.hip, as args() uses them.
+  // this rank's claimed microbatch (epoch << 32 | batch; negative: the schedule is finished)
+  int64_t inflight_bid() const {
+    long long b = 0;
+    check_hip(hipDeviceSynchronize(), "ps inflight sync");
+    check_hip(hipMemcpy(&b, local_ + 8, 8, hipMemcpyDeviceToHost), "ps bid");
+    return (int64_t)b;
+  }
+  py::dict export_state() const {
+    TORCH_CHECK(shared_ != nullptr, "ps: open() the handles first");
+    TORCH_CHECK(nbatches_ > 0, "ps export_state: set_schedule first");
+    check_hip(hipDeviceSynchronize(), "ps export sync");
+    unsigned ver[3] = {0, 0, 0}, sch[2] = {0, 0};
+    unsigned long long cursor = 0, ctr[4] = {0, 0, 0, 0};
+    check_hip(hipMemcpy(ver, shared_, 12, hipMemcpyDeviceToHost), "ps export ver");
+    check_hip(hipMemcpy(&cursor, shared_ + 16, 8, hipMemcpyDeviceToHost), "ps export cursor");
+    check_hip(hipMemcpy(sch, shared_ + 32, 8, hipMemcpyDeviceToHost), "ps export sched");
+    check_hip(hipMemcpy(ctr, shared_ + 48, 32, hipMemcpyDeviceToHost), "ps export ctr");
+    std::vector<unsigned> done((size_t)nbatches_), claimed((size_t)nbatches_);
+    check_hip(hipMemcpy(done.data(), shared_ + 256, (size_t)nbatches_ * 4, hipMemcpyDeviceToHost), "ps export done");
+    check_hip(hipMemcpy(claimed.data(), shared_ + 256 + (size_t)dfa::kPSMaxBatches * 4, (size_t)nbatches_ * 4,
+                        hipMemcpyDeviceToHost),
+              "ps export claimed");
+    py::dict d;
+    std::vector<int64_t> pref;
+    int64_t applied = (int64_t)ver[2];
+    // owner-applies: the owners' drains publish (pref), the applied word is never written; "fully applied" is
+    // the minimum prefix.  (Inboxes that are mapped for the calibration only carry no prefixes.)
+    if (owner_on_) {
+      pref = owner_prefix();
+      applied = *std::min_element(pref.begin(), pref.end());
+    }
+    d["version"] = (int64_t)ver[0];
+    d["applied"] = applied;
+    d["cursor"] = (int64_t)cursor;
+    d["epoch"] = (int64_t)sch[0];
+    d["completed_in_epoch"] = (int64_t)sch[1];
+    d["sched_ctr"] = std::vector<int64_t>{(int64_t)ctr[0], (int64_t)ctr[1], (int64_t)ctr[2], (int64_t)ctr[3]};
+    d["done_epoch"] = std::vector<int64_t>(done.begin(), done.end());
+    d["claimed_epoch"] = std::vector<int64_t>(claimed.begin(), claimed.end());
+    d["owner_prefix"] = pref;
+    return d;
+  }
+  // server rank, after open() / init_master() and before the first step: write a quiesced job's words back
+  void import_state(py::dict st) {
+    TORCH_CHECK(rank_ == server_ && !joiner_, "ps import_state: the server rank writes the control buffer");
+    TORCH_CHECK(shared_ != nullptr && shard_[0] != nullptr, "ps: open() the handles first");
+    TORCH_CHECK(nbatches_ > 0, "ps import_state: set_schedule first");
+    const int64_t version = st["version"].cast<int64_t>(), applied = st["applied"].cast<int64_t>();
+    const int64_t cursor = st["cursor"].cast<int64_t>(), epoch = st["epoch"].cast<int64_t>();
+    const int64_t in_epoch = st["completed_in_epoch"].cast<int64_t>();
+    const auto ctr = st["sched_ctr"].cast<std::vector<int64_t>>();
+    const auto done = st["done_epoch"].cast<std::vector<int64_t>>();
+    const auto claimed = st["claimed_epoch"].cast<std::vector<int64_t>>();
+    std::vector<int64_t> pref;
+    if (st.contains("owner_prefix") && !st["owner_prefix"].is_none()) pref = st["owner_prefix"].cast<std::vector<int64_t>>();
+    TORCH_CHECK(version >= 0 && version <= 0xffffffffLL && cursor >= 0 && epoch >= 0 && epoch < 0xffffffffLL,
+                "ps import_state: word out of range");
+    TORCH_CHECK(version == applied, "ps import_state: version ", version, " != applied ", applied,
+                " (the job was not quiesced)");
+    for (int64_t p : pref)
+      TORCH_CHECK(p == version, "ps import_state: an owner prefix (", p, ") differs from the version ", version);
+    TORCH_CHECK((int64_t)done.size() == nbatches_ && (int64_t)claimed.size() == nbatches_,
+                "ps import_state: completion arrays of ", done.size(), " / ", claimed.size(), " entries, schedule has ",
+                nbatches_);
+    TORCH_CHECK(ctr.size() == 4, "ps import_state: four schedule counters");
+    int64_t cnt = 0;
+    for (int64_t v : done) {
+      TORCH_CHECK(v >= 0 && v <= 0xffffffffLL, "ps import_state: done_epoch out of range");
+      cnt += v == epoch + 1 ? 1 : 0;
+    }
+    TORCH_CHECK(cnt == in_epoch, "ps import_state: completed_in_epoch ", in_epoch, " but ", cnt,
+                " batches are done in epoch ", epoch);
+    for (int64_t v : claimed) TORCH_CHECK(v >= 0 && v <= 0xffffffffLL, "ps import_state: claimed_epoch out of range");
+    check_hip(hipDeviceSynchronize(), "ps import sync");
+    const unsigned ver[3] = {(unsigned)version, 0u, (unsigned)applied};
+    const unsigned long long cur = (unsigned long long)cursor;
+    const unsigned sch[2] = {(unsigned)epoch, (unsigned)in_epoch};
+    const unsigned long long c4[4] = {(unsigned long long)ctr[0], (unsigned long long)ctr[1], (unsigned long long)ctr[2],
+                                      (unsigned long long)ctr[3]};
+    std::vector<unsigned> d32(done.begin(), done.end()), c32(claimed.begin(), claimed.end());
+    check_hip(hipMemcpy(shared_, ver, 12, hipMemcpyHostToDevice), "ps import ver");
+    check_hip(hipMemcpy(shared_ + 16, &cur, 8, hipMemcpyHostToDevice), "ps import cursor");
+    check_hip(hipMemcpy(shared_ + 32, sch, 8, hipMemcpyHostToDevice), "ps import sched");
+    check_hip(hipMemcpy(shared_ + 48, c4, 32, hipMemcpyHostToDevice), "ps import ctr");
+    check_hip(hipMemcpy(shared_ + 256, d32.data(), d32.size() * 4, hipMemcpyHostToDevice), "ps import done");
+    check_hip(hipMemcpy(shared_ + 256 + (size_t)dfa::kPSMaxBatches * 4, c32.data(), c32.size() * 4, hipMemcpyHostToDevice),
+              "ps import claimed");
+    // (the FedSGD words, shared_ + 80..111, stay as they are)
+    if (inbox_[0] != nullptr) {
+      // Every owner's drained prefix = version.  Sequence numbers are the version word's values (ps_admit:
+      // kPSSeq = v), so the next admitted gradient has q = version; the drain loop of ps_fetch_pull_kernel
+      // starts at P = pref[k] and takes slot (P + n) % R only while its flag == P + n + 1 (>= 1).  A fresh
+      // server's ring flags are all zero, so nothing is drained until a sender has flagged q + 1 for
+      // q >= version: a resumed server with pref[k] = version is consistent with an empty ring.
+      std::vector<unsigned> p32((size_t)world_, (unsigned)version);
+      check_hip(hipMemcpy(shared_ + 192, p32.data(), p32.size() * 4, hipMemcpyHostToDevice), "ps import pref");
+    }
+    check_hip(hipDeviceSynchronize(), "ps import sync");
   }
   // the master, gathered from the shards (call while no worker is stepping)
   void copy_master(torch::Tensor dst) const {
@@ -2548,7 +2675,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("idx") = py::none())
       .def("excl_gate", &PSComm::excl_gate)
       .def("excl_mirror", &PSComm::excl_mirror)
-      .def("fetch_pull", &PSComm::fetch_pull, py::arg("w"), py::arg("perm") = py::none(), py::arg("idx") = py::none())
+      .def("fetch_pull", &PSComm::fetch_pull, py::arg("w"), py::arg("perm") = py::none(), py::arg("idx") = py::none(),
+           py::arg("bid") = py::none())
+      .def("export_state", &PSComm::export_state)
+      .def("import_state", &PSComm::import_state, py::arg("state"))
+      .def("inflight_bid", &PSComm::inflight_bid)
       .def("apply", &PSComm::apply, py::arg("g"), py::arg("lr"), py::arg("max_stale"))
       .def("stats", &PSComm::stats)
       .def("host_error", &PSComm::host_error)
@@ -2563,7 +2694,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("owner_enable", &PSComm::owner_enable, py::arg("on"))
       .def("owner_applies", &PSComm::owner_applies)
       .def("owner_ring", &PSComm::owner_ring)
-      .def("drain", &PSComm::drain)
+      .def("drain", &PSComm::drain, py::arg("w"), py::arg("quiesced") = false)
       .def("owner_prefix", &PSComm::owner_prefix)
       .def("calibrate", &PSComm::calibrate, py::arg("mode"), py::arg("reps") = 20)
       .def("fed_init", &PSComm::fed_init, py::arg("K"))

@@ -429,6 +429,12 @@ struct PSArgs {
   unsigned* pref;               // shared [nshards] drained-sequence counts
   unsigned* dlock;              // shared [nshards] drain locks (0 free, rank + 1 held): any pulling rank drains
   int owner_ring, rank;
+  // resume (ps_fetch_pull only): claim_given != 0 makes the pull take `claim_bid` (epoch << 32 | batch, the id a
+  // checkpoint recorded as claimed but not yet trained) instead of claiming: no cursor add, no claimed_epoch
+  // exchange.  A flag, since a zero-initialised id is the valid (epoch 0, batch 0).  claim_given == 2: no claim
+  // at all and bid_out / idx stay as they are (the drain of a checkpoint's quiesce).
+  int claim_given;
+  long long claim_bid;
 };
 constexpr int kPSMaxGrid = 64;
 

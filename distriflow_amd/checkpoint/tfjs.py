@@ -70,16 +70,24 @@ def _bn_stat(layer: BatchNorm, which: str, device) -> torch.Tensor:
     return layer.run_mean if which == "moving_mean" else layer.run_var
 
 
-def save_layers_model(net, directory: str, topology: Optional[dict] = None, shard_bytes: int = 0) -> str:
-    """Write ``directory/model.json`` + weight shard(s).  Returns the model.json path."""
+def save_layers_model(net, directory: str, topology: Optional[dict] = None, shard_bytes: int = 0,
+                      master: Optional[torch.Tensor] = None) -> str:
+    """Write ``directory/model.json`` + weight shard(s).  Returns the model.json path.  ``master``: a flat fp32
+    buffer laid out like ``net.store.master`` to take the weights from (default: the store's own), so a
+    snapshot can be written without touching the live weights."""
     os.makedirs(directory, exist_ok=True)
+    st = net.store
+    if master is not None and (master.dim() != 1 or master.numel() != st.total):
+        raise ValueError(f"save_layers_model: master has {master.numel()} elements, the store {st.total}")
     entries = []
     blobs = []
     for name, layer in _weight_layers(net):
         if name.endswith("/moving_mean") or name.endswith("/moving_variance"):
             arr = _bn_stat(layer, name.rsplit("/", 1)[1], net.device).float().cpu().numpy()
         else:
-            arr = _engine_to_keras(name, net.store[name], layer)
+            src = st[name] if master is None else \
+                master[st.offsets[name]: st.offsets[name] + st.spec(name).numel].view(st.spec(name).shape)
+            arr = _engine_to_keras(name, src, layer)
         arr = np.ascontiguousarray(arr, dtype="<f4")
         entries.append({"name": name, "shape": list(arr.shape), "dtype": "float32"})
         blobs.append(arr.tobytes())

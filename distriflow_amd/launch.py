@@ -5,16 +5,19 @@ The reference has no CLI — its experiments are two hand-written TypeScript mai
 for ``python -m distriflow.launch``).  One process per GPU, torchrun-compatible environment
 (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR / MASTER_PORT); with ``--nproc N`` this module is its
 own launcher (children are spawned before anything touches the GPU) and, with ``--max-restarts``,
-restarts a failed job from its last checkpoint (``--resume``), which is the all-reduce mode's
-answer to a lost rank.
+restarts a failed job from its last checkpoint (``--resume``; ``sync`` always, ``async`` / ``fedavg``
+when they have a ``--save-dir``), which is the answer to a lost rank.
 
 Modes
   sync    synchronous data parallelism: RCCL all-reduce SGD (DataParallelTrainer), tf.js
           checkpoints + resume record per epoch (``--save-dir``)
   async   asynchronous parameter server (rank 0) with bounded staleness; workers hold the dataset
-          in HBM and receive batch ids (``--ship-data`` sends tensors instead, as the reference)
+          in HBM and receive batch ids (``--ship-data`` sends tensors instead, as the reference);
+          device engine: ``--save-dir`` checkpoints the parameter server every ``--save-every``
+          steps and at the end, ``--resume`` continues from it (also at another rank count)
   fedsgd  the reference's FederatedServer / FederatedClient (count barrier + version gating)
-  fedavg  federated averaging over non-IID label shards
+  fedavg  federated averaging over non-IID label shards; device engine: ``--save-dir`` /
+          ``--resume`` per round
 
 With WORLD_SIZE == 1 the parameter-server modes run in one process: server + ``--workers``
 worker threads over the in-process transport (same GPU).
@@ -86,6 +89,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="device = GPU-resident parameter server (parallel/async_ps.py, every rank a worker); "
                         "roles = message-level AsynchronousSGDServer/Client (reference protocol); "
                         "auto = device on GPUs, roles on CPU")
+    p.add_argument("--save-dir", default=None,
+                   help="device engine: checkpoint directory (tf.js model + resume record of the parameter server)")
+    p.add_argument("--resume", action="store_true", help="continue from the checkpoint in --save-dir")
+    p.add_argument("--save-every", type=int, default=1024,
+                   help="checkpoint every this many steps per rank, rounded up to whole chunks (0 = only at the end)")
+    p.add_argument("--steps", type=int, default=0,
+                   help="stop cleanly after this many steps per rank and write a final checkpoint (0 = all epochs)")
 
     p = sub.add_parser("join", help="a late-joining async worker: attach to a running device parameter server "
                                     "(started with async --store-port) and train until its schedule finishes")
@@ -108,7 +118,31 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--engine", default="auto", choices=["auto", "device", "roles"],
                    help="device = every rank a client, graph-captured local steps, collective weight average "
                         "(parallel/fedavg.py); roles = FedAvgServer/FedAvgClient messages; auto = device on GPUs")
+    p.add_argument("--save-dir", default=None, help="device engine: checkpoint directory (averaged model + round)")
+    p.add_argument("--resume", action="store_true", help="continue from the checkpoint in --save-dir")
+    p.add_argument("--save-every", type=int, default=1, help="checkpoint every this many rounds")
     return ap
+
+
+def check_args(ap: argparse.ArgumentParser, args):
+    """Combinations argparse cannot express (usage errors)."""
+    if args.mode == "async":
+        if args.save_dir and args.store_port:
+            ap.error("async: --save-dir cannot be combined with --store-port (joiners are outside the process "
+                     "group and cannot be quiesced for a checkpoint)")
+        if args.resume and not args.save_dir:
+            ap.error("async: --resume needs --save-dir")
+        if args.engine == "roles" and (args.save_dir or args.resume or args.steps):
+            ap.error("async: --save-dir / --resume / --steps belong to the device engine (--engine device)")
+        if args.save_every < 0 or args.steps < 0:
+            ap.error("async: --save-every and --steps must be >= 0")
+    if args.mode == "fedavg":
+        if args.resume and not args.save_dir:
+            ap.error("fedavg: --resume needs --save-dir")
+        if args.engine == "roles" and (args.save_dir or args.resume):
+            ap.error("fedavg: --save-dir / --resume belong to the device engine (--engine device)")
+        if args.save_every < 1:
+            ap.error("fedavg: --save-every must be >= 1")
 
 
 # ------------------------------------------------------------------------------------------ spawner
@@ -159,10 +193,20 @@ def _spawn(argv: list, nproc: int, max_restarts: int, port: int) -> int:
         if attempt >= max_restarts:
             return failed[1] or 1
         attempt += 1
-        # a restarted job resumes from its checkpoint and runs without the injected fault
-        child_argv = [a for a in child_argv if a != "--resume"]
-        child_argv = _strip_opt(child_argv, "--fault-kill-rank") + ["--resume"] if "sync" in child_argv else child_argv
-        child_argv = _strip_opt(child_argv, "--fault-kill-step")
+        child_argv = restart_argv(child_argv)
+
+
+def restart_argv(argv: list) -> list:
+    """The argv of a restarted job: it runs without the injected kill (every mode) and resumes from its
+    checkpoint -- ``sync`` always (without --save-dir the flag is inert), ``async`` and ``fedavg`` when they
+    were given a --save-dir."""
+    out = [a for a in argv if a != "--resume"]
+    out = _strip_opt(_strip_opt(out, "--fault-kill-rank"), "--fault-kill-step")
+    mode = next((a for a in out if a in ("sync", "async", "join", "fedsgd", "fedavg")), None)
+    saves = any(a == "--save-dir" or a.startswith("--save-dir=") for a in out)
+    if mode == "sync" or (mode in ("async", "fedavg") and saves):
+        out.append("--resume")
+    return out
 
 
 def _strip_opt(argv: list, name: str) -> list:
@@ -372,6 +416,18 @@ def run_async_device(args) -> dict:
     tr.bind_dataset(x, y, B, scale=1.0 / 255.0 if x.dtype == torch.uint8 else 1.0)
     # one table row per microbatch id of an epoch; at-least-once dispatch per epoch on the device
     tr.bind_schedule(epoch_permutations(n, B, nb, dev, seed=args.seed), epochs=args.epochs)
+    # checkpoint / resume (AsyncPSTrainer.save_checkpoint / load_checkpoint): the schedule is always built from
+    # the original seed; the record says which of its batches are complete
+    ckpt, resumed, ck_ms = None, None, []
+    save_dir = getattr(args, "save_dir", None)
+    limit = int(getattr(args, "steps", 0) or 0)
+    if save_dir:
+        from .checkpoint.ps_state import open_store
+
+        ckpt = open_store(save_dir)
+        if getattr(args, "resume", False) and ckpt.read_resume() is not None:
+            resumed = int(tr.load_checkpoint(ckpt)["version"])
+            log.log(f"resumed from version {resumed}")
     # per-replay JSONL through the trainer callbacks (device counters, read back asynchronously)
     tr.on_upload(lambda st: log.metric(event="upload", **st))
     faults = Faults(args, rank)
@@ -383,19 +439,45 @@ def run_async_device(args) -> dict:
     chunk = 32 if chunked else 8
     if chunked:
         tr.prepare_run(chunk)
+    save_every = -(-int(getattr(args, "save_every", 0) or 0) // chunk) * chunk  # whole chunks
+
+    def checkpoint():
+        t_c = time.perf_counter()
+        tr.save_checkpoint(ckpt)
+        ck_ms.append((time.perf_counter() - t_c) * 1e3)
+
     t0 = time.perf_counter()
-    steps = 0
+    steps, since = 0, 0
     while True:
+        todo = min(chunk, limit - steps) if limit else chunk
         if chunked:
-            st = tr.run(chunk)
-            steps += chunk
+            st = tr.run(todo)
+            steps += todo
         else:
-            for _ in range(chunk):
+            for _ in range(todo):
                 faults.step(steps)
                 st = tr.step()
                 steps += 1
-        if tr.finished():
-            break
+        since += todo
+        stop = bool(limit) and steps >= limit
+        if ckpt is None:
+            if tr.finished() or stop:
+                break
+        else:
+            # the ranks agree on whether EVERYONE is finished, then all break or all save: a rank whose
+            # finished() turned true one chunk early must not leave the others alone in the save's barriers
+            # (its further steps are device no-ops)
+            fin = tr.finished()
+            if world > 1:
+                from .parallel.p2p import _agree
+
+                fin = _agree(fin, None, dev)
+            if fin or stop:
+                checkpoint()  # the final checkpoint
+                break
+            if save_every and since >= save_every:
+                checkpoint()
+                since = 0
         if steps >= cap:
             raise RuntimeError(f"async PS did not finish {args.epochs} epochs in {steps} steps: {tr.ps_stats()}")
     torch.cuda.synchronize(dev)
@@ -416,6 +498,8 @@ def run_async_device(args) -> dict:
                    capture_warmup=tr.capture_warmup if tr.graph_mode == "full" else 0, step=tr.step_launches,
                    graph=tr.graph_mode, capture_error=getattr(tr, "capture_error", None),
                    **tr.ps_stats())
+        out.update(checkpoints=len(ck_ms), checkpoint_ms_mean=sum(ck_ms) / len(ck_ms) if ck_ms else None,
+                   checkpoint_ms_max=max(ck_ms) if ck_ms else None, resumed_from_version=resumed)
         log.metric(event="async_done", **out)
         print(json.dumps(out), flush=True)
     shutdown()
@@ -466,6 +550,8 @@ def run_async(args) -> dict:
         engine = "device" if _device(args) == "cuda" else "roles"
     if engine == "device":
         return run_async_device(args)
+    if getattr(args, "save_dir", None) or getattr(args, "resume", False) or getattr(args, "steps", 0):
+        raise SystemExit("async: --save-dir / --resume / --steps belong to the device engine (needs a GPU)")
 
     from .data.dataset import DistriDataset
     from .models.distri_model import ClientModel, InMemoryServerModel
@@ -647,12 +733,42 @@ def run_fedavg_device(args) -> dict:
     tr = FedAvgTrainer(net, lr=args.lr, local_steps=args.local_steps,
                        graph="full" if dev.type == "cuda" else "none")
     tr.bind_dataset(x, y, B, scale=scale)
-    tr.bind_index_stream(stream)
-    if dev.type == "cuda":
+    # checkpoint / resume: rank 0 saves the averaged model (identical on every rank after a round) and the
+    # round; the stream is always built from the original seed and a resumed job skips the rounds already run
+    ckpt, start = None, 0
+    if getattr(args, "save_dir", None):
+        from .checkpoint.ps_state import open_store
+        from .checkpoint.tfjs import load_layers_model_weights, save_layers_model
+
+        ckpt = open_store(args.save_dir)
+        rec = ckpt.read_resume() if args.resume else None
+        if rec is not None:
+            if rec.get("engine") != "fedavg_device" or int(rec.get("local_steps", -1)) != args.local_steps:
+                raise ValueError(f"fedavg: {args.save_dir} holds no checkpoint of this job (engine / local steps)")
+            # the version the record names: a newer directory is a torn save
+            load_layers_model_weights(net, os.path.join(ckpt.path(str(rec["store_version"])), "model.json"))
+            net.step_dev.fill_(int(rec.get("engine_step", 0)))
+            start = min(int(rec["round"]), args.rounds)
+            tr.rounds = start
+    if start < args.rounds:
+        tr.bind_index_stream(stream[start * args.local_steps:])
+    if dev.type == "cuda" and start < args.rounds:
         tr.prepare_run(args.local_steps)  # the local steps' multi-step graph, captured before the clock starts
     t0 = time.perf_counter()
-    for _ in range(args.rounds):
+    for r in range(start, args.rounds):
         tr.run_round()
+        if ckpt is not None and ((r + 1) % args.save_every == 0 or r + 1 == args.rounds):
+            if rank == 0:
+                v = ckpt.new_version()
+                save_layers_model(net, ckpt.path(v))
+                ckpt.write_resume({"engine": "fedavg_device", "round": r + 1, "local_steps": args.local_steps,
+                                   "engine_step": int(net.step_dev.item()), "store_version": v})
+                ckpt.mark_current(v)
+                ckpt.prune()
+            if world > 1:
+                import torch.distributed as dist
+
+                dist.barrier()
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     el = time.perf_counter() - t0
@@ -752,7 +868,9 @@ MODES = {"sync": run_sync, "async": run_async, "join": run_join, "fedsgd": run_f
 
 def main(argv: Optional[list] = None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    check_args(ap, args)
     if args.nproc > 1 and "WORLD_SIZE" not in os.environ:
         child = _strip_opt(_strip_opt(_strip_opt(argv, "--nproc"), "--max-restarts"), "--master-port")
         return _spawn(child, args.nproc, args.max_restarts, args.master_port)

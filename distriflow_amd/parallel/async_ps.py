@@ -174,6 +174,8 @@ class AsyncPSTrainer(DataParallelTrainer):
                            and net.store.compute_bf16 and net.store.lenet_frag is None and diag_on("ps_excl_fused")
                            and h[1] == 0.0 and h[2] == 0.0 and h[3] == 1.0)
         self._primed = False
+        self._resume_bid = None           # load_checkpoint: the id this rank had claimed but not trained
+        self.resumed_from_version = None  # load_checkpoint: the version the job was resumed from
         self._ps_stats_dev = self.ps.stats_tensor()  # device view of this rank's PS counters (callbacks)
         from .watchdog import register_owner_probe
 
@@ -292,7 +294,13 @@ class AsyncPSTrainer(DataParallelTrainer):
         into the local weights and compute copies; every later step's reduce launch (or, one rank: its
         admission workgroup and gated optimizer launch) does both itself."""
         if (self.fused_ps or self.excl_fused) and not self._primed:
-            self.ps.fetch_pull(self.net.store.master, self._perm, self.idx)
+            # a resumed rank's prologue takes the microbatch it had claimed when the checkpoint was written
+            # instead of claiming (exactly once; the prologue is eager, never part of a captured graph)
+            bid, self._resume_bid = self._resume_bid, None
+            if bid is None:
+                self.ps.fetch_pull(self.net.store.master, self._perm, self.idx)
+            else:
+                self.ps.fetch_pull(self.net.store.master, self._perm, self.idx, bid=int(bid))
             self.net.store.refresh_compute()
             self._primed = True
 
@@ -400,7 +408,7 @@ class AsyncPSTrainer(DataParallelTrainer):
                 "apply_calibration": self.apply_calib,
                 "cursor": cursor, "noop_steps": noops, "epoch": epoch, "completed_in_epoch": in_epoch,
                 "completed": completed, "redispatched": redisp, "skipped": skipped, "duplicates": dups,
-                "finished": bool(fin)}
+                "finished": bool(fin), "resumed_from_version": self.resumed_from_version}
 
     def finished(self) -> bool:
         """Every batch of every configured epoch has an admitted gradient (host read; syncs)."""
@@ -432,3 +440,131 @@ class AsyncPSTrainer(DataParallelTrainer):
             return self.net.store.master
         self.ps.copy_master(dst)
         return dst
+
+    # ------------------------------------------------------------------ checkpoint / resume
+    # The state that says where an async job is lives in HBM (the control words, the sharded master, every
+    # rank's claimed microbatch).  A checkpoint is taken at a QUIESCE point, collectively and off the hot path:
+    #   1. every rank synchronises its stream; the ranks agree that no device error bit is set (a barrier);
+    #   2. owner-applies: every rank drains its inbox (claiming nothing), synchronises; a barrier -- the sharded
+    #      master now holds every admitted gradient, every owner prefix equals the version;
+    #   3. the ranks all-gather their in-flight ids.  On the fused paths (LeNet-5 reduce, exclusive writer) a
+    #      step ends by claiming the NEXT microbatch, so between steps each rank holds one claimed, untrained
+    #      id; on the generic path claim, compute and apply are one step and nothing is in flight;
+    #   4. the server rank gathers the master into a scratch buffer, exports the control words, writes the record;
+    #   5. a barrier, and the ranks go on.
+    # Saving touches neither the local weights, the compute copies, the refresh record nor the staged indices.
+    # Joinable trainers and joiners cannot checkpoint: a joiner is outside the process group and cannot be
+    # quiesced.
+    def _ckpt_guard(self, what: str):
+        if self.joinable or self.joiner:
+            raise RuntimeError(f"{what}: not supported with joinable trainers / joiners (workers outside the "
+                               "process group cannot be quiesced)")
+        if self._perm is None or getattr(self, "idx", None) is None:
+            raise RuntimeError(f"{what}: bind_dataset() and bind_schedule() first")
+
+    def _ckpt_agree(self, err, what: str):
+        """Collective: every rank learns whether every rank managed ``what`` (doubles as the barrier)."""
+        ok = err is None
+        if self.world > 1:
+            from .p2p import _agree
+
+            ok = _agree(ok, self.group, self.net.device)
+        if err is not None:
+            raise err
+        if not ok:
+            raise RuntimeError(f"async PS checkpoint: {what} failed on another rank")
+
+    def _schedule_hash(self) -> str:
+        from ..checkpoint.ps_state import schedule_sha256
+
+        return schedule_sha256(self._perm.cpu().numpy().tobytes())
+
+    def save_checkpoint(self, store) -> Optional[str]:
+        """Collective over the members' group: write a resumable checkpoint into ``store`` (a
+        :class:`VersionedStore`; construct it with ``keep_last``).  Returns the store version on the server rank."""
+        from ..checkpoint import ps_state
+        from ..checkpoint.tfjs import save_layers_model
+
+        self._ckpt_guard("save_checkpoint")
+        dev = self.net.device
+        torch.cuda.synchronize(dev)
+        err = None
+        bits = self.ps.stats()[5]
+        if bits:  # a trainer with device error bits set writes no checkpoint
+            err = RuntimeError(f"async PS: device wait timed out (error bits {bits:#x}); no checkpoint written")
+        self._ckpt_agree(err, "the device error check")
+        if self.owner_apply:
+            try:
+                if not hasattr(self, "_drain_buf"):
+                    self._drain_buf = torch.empty_like(self.net.store.master)
+                self.ps.drain(self._drain_buf, quiesced=True)
+                torch.cuda.synchronize(dev)
+            except Exception as e:
+                err = e
+            self._ckpt_agree(err, "the inbox drain")
+        bid = None
+        if (self.fused_ps or self.excl_fused) and self._primed:
+            b = int(self.ps.inflight_bid())
+            bid = b if b >= 0 else None
+        elif self._resume_bid is not None:  # resumed and saved again before the first step
+            bid = int(self._resume_bid)
+        bids = [bid] * self.world
+        if self.world > 1:
+            dist.all_gather_object(bids, bid, group=self.group)
+        v = None
+        if self.rank == self.server_rank:
+            try:
+                if not hasattr(self, "_ckpt_master"):
+                    self._ckpt_master = torch.empty_like(self.net.store.master)
+                self.ps.copy_master(self._ckpt_master)
+                torch.cuda.synchronize(dev)
+                rec = ps_state.make_record(
+                    dict(self.ps.export_state()), bids, world=self.world, n_params=self.net.store.total,
+                    nbatches=int(self._perm.shape[0]), batch=self.B, epochs=self.epochs,
+                    schedule_hash=self._schedule_hash(), engine_step=int(self.net.step_dev.item()), lr=float(self.lr),
+                    max_staleness=self.max_staleness)
+                v = ps_state.write_checkpoint(
+                    store, lambda d: save_layers_model(self.net, d, master=self._ckpt_master), rec)
+            except Exception as e:
+                err = e
+        self._ckpt_agree(err, "the checkpoint write")
+        return v
+
+    def load_checkpoint(self, store) -> dict:
+        """Collective: resume from the checkpoint in ``store``.  Call after :meth:`bind_dataset` and
+        :meth:`bind_schedule` and before the first step.  Every rank loads the weights and seeds its own shard
+        (so the job may resume at another rank count: the gathered master reshards for free), the server rank
+        writes the control words back.  Rank r's first pull takes ``inflight[r]`` instead of claiming; the ids of
+        ranks that no longer exist are still incomplete in ``done_epoch`` and come round again on the cursor's
+        next lap.  Returns the record."""
+        from ..checkpoint import ps_state
+        from ..checkpoint.tfjs import load_layers_model_weights
+
+        self._ckpt_guard("load_checkpoint")
+        if self.steps > 0 or self._primed or self._graph is not None:
+            raise RuntimeError("load_checkpoint: call it before the first step (and before prepare_run)")
+        err, rec = None, None
+        try:
+            rec = ps_state.read_checkpoint(store, n_params=self.net.store.total, nbatches=int(self._perm.shape[0]),
+                                           batch=self.B, schedule_hash=self._schedule_hash())
+            if rec is None:
+                raise FileNotFoundError(f"no async PS checkpoint in {store.save_dir}")
+            load_layers_model_weights(self.net, rec["model_json"])
+            self.net.step_dev.fill_(int(rec["engine_step"]))
+            torch.cuda.synchronize(self.net.device)
+            self.ps.init_master(self.net.store.master)
+        except Exception as e:
+            err = e
+        self._ckpt_agree(err, "reading the checkpoint")
+        if self.rank == self.server_rank:
+            try:
+                self.ps.import_state(rec["ps"])
+            except Exception as e:
+                err = e
+        self._ckpt_agree(err, "the control-state import")
+        infl = rec["inflight"]
+        # (the generic path's claim is part of its captured step: an id recorded by a fused-path job is left
+        # incomplete there and comes round again like a vanished rank's)
+        self._resume_bid = infl[self.rank] if self.rank < len(infl) and (self.fused_ps or self.excl_fused) else None
+        self.resumed_from_version = int(rec["version"])
+        return rec
