@@ -508,6 +508,37 @@ void gap_bwd_py(torch::Tensor dy, torch::Tensor dx, int64_t B, int64_t HW, int64
             "gap_bwd");
 }
 
+// the optimizer launch's extra workgroup (csrc/optim_device.h index_stream_body): next-batch index staging
+// and / or the device run statistics
+static void fill_index_stream(dfa::IndexStream& is, const c10::optional<torch::Tensor>& idx_stream,
+                              const c10::optional<torch::Tensor>& idx_cursor,
+                              const c10::optional<torch::Tensor>& idx_dst,
+                              const c10::optional<torch::Tensor>& step_stats,
+                              const c10::optional<torch::Tensor>& run_stats) {
+  if (idx_stream.has_value() && idx_stream->defined()) {
+    TORCH_CHECK(idx_cursor.has_value() && idx_dst.has_value(), "index stream needs cursor and dst");
+    need(*idx_stream, at::kLong, "idx_stream");
+    need(*idx_cursor, at::kLong, "idx_cursor");
+    need(*idx_dst, at::kLong, "idx_dst");
+    TORCH_CHECK(idx_stream->dim() == 2 && idx_stream->size(1) == idx_dst->numel() && idx_cursor->numel() >= 1,
+                "idx_stream must be [nsteps][B] with B = idx_dst.numel()");
+    is.src = reinterpret_cast<const long long*>(idx_stream->data_ptr());
+    is.cursor = reinterpret_cast<long long*>(idx_cursor->data_ptr());
+    is.dst = reinterpret_cast<long long*>(idx_dst->data_ptr());
+    is.B = (int)idx_dst->numel();
+    is.nsteps = (int)idx_stream->size(0);
+  }
+  // device run statistics, with or without an index stream (the same extra workgroup accumulates them)
+  if (run_stats.has_value() && run_stats->defined()) {
+    TORCH_CHECK(step_stats.has_value() && step_stats->defined(), "run_stats needs step_stats");
+    need(*run_stats, at::kFloat, "run_stats");
+    need(*step_stats, at::kFloat, "step_stats");
+    TORCH_CHECK(run_stats->numel() >= 3 && step_stats->numel() >= 2, "run_stats [3] / step_stats [2]");
+    is.run_stats = run_stats->data_ptr<float>();
+    is.step_stats = step_stats->data_ptr<float>();
+  }
+}
+
 // descs: int64 GPU tensor [ndesc][6] laid out as ParamDesc (see optim.hip)
 void sgd_multi_py(torch::Tensor descs, int64_t ndesc, int64_t total_blocks, torch::Tensor master, torch::Tensor grad,
                   c10::optional<torch::Tensor> mom, torch::Tensor wbf, torch::Tensor hyper, bool apply_update,
@@ -539,28 +570,7 @@ void sgd_multi_py(torch::Tensor descs, int64_t ndesc, int64_t total_blocks, torc
     mp = mom->data_ptr<float>();
   }
   dfa::IndexStream is{};
-  if (idx_stream.has_value() && idx_stream->defined()) {
-    TORCH_CHECK(idx_cursor.has_value() && idx_dst.has_value(), "index stream needs cursor and dst");
-    need(*idx_stream, at::kLong, "idx_stream");
-    need(*idx_cursor, at::kLong, "idx_cursor");
-    need(*idx_dst, at::kLong, "idx_dst");
-    TORCH_CHECK(idx_stream->dim() == 2 && idx_stream->size(1) == idx_dst->numel() && idx_cursor->numel() >= 1,
-                "idx_stream must be [nsteps][B] with B = idx_dst.numel()");
-    is.src = reinterpret_cast<const long long*>(idx_stream->data_ptr());
-    is.cursor = reinterpret_cast<long long*>(idx_cursor->data_ptr());
-    is.dst = reinterpret_cast<long long*>(idx_dst->data_ptr());
-    is.B = (int)idx_dst->numel();
-    is.nsteps = (int)idx_stream->size(0);
-  }
-  // device run statistics, with or without an index stream (the same extra workgroup accumulates them)
-  if (run_stats.has_value() && run_stats->defined()) {
-    TORCH_CHECK(step_stats.has_value() && step_stats->defined(), "run_stats needs step_stats");
-    need(*run_stats, at::kFloat, "run_stats");
-    need(*step_stats, at::kFloat, "step_stats");
-    TORCH_CHECK(run_stats->numel() >= 3 && step_stats->numel() >= 2, "run_stats [3] / step_stats [2]");
-    is.run_stats = run_stats->data_ptr<float>();
-    is.step_stats = step_stats->data_ptr<float>();
-  }
+  fill_index_stream(is, idx_stream, idx_cursor, idx_dst, step_stats, run_stats);
   if (lenet_frag.has_value() && lenet_frag->defined()) {
     TORCH_CHECK(lenet_frag->is_cuda() && lenet_frag->is_contiguous() &&
                     (size_t)lenet_frag->nbytes() >= dfa::lenet_frag_bytes(),
@@ -589,6 +599,52 @@ void sgd_multi_py(torch::Tensor descs, int64_t ndesc, int64_t total_blocks, torc
                            master.data_ptr<float>(), grad.data_ptr<float>(), mp, (dfa::bf16*)wbf.data_ptr(),
                            hyper.data_ptr<float>(), apply_update ? 1 : 0, cur_stream(), any ? &is : nullptr, hd),
             "sgd_multi");
+}
+
+// Adam / AdamW twin of sgd_multi (csrc/adam.hip).  The LeNet-5 fragment rebuild is SGD-only (no argument
+// for it here) and so are the async parameter server's gate / mirror, which are rejected.
+void adam_multi_py(torch::Tensor descs, int64_t ndesc, int64_t total_blocks, torch::Tensor master, torch::Tensor grad,
+                   torch::Tensor m, torch::Tensor v, torch::Tensor wbf, torch::Tensor hyper, torch::Tensor state,
+                   torch::Tensor tickets, c10::optional<torch::Tensor> idx_stream, c10::optional<torch::Tensor> idx_cursor,
+                   c10::optional<torch::Tensor> idx_dst, c10::optional<torch::Tensor> descs_host,
+                   c10::optional<torch::Tensor> step_stats, c10::optional<torch::Tensor> run_stats,
+                   uintptr_t gate, uintptr_t mirror) {
+  TORCH_CHECK(gate == 0 && mirror == 0,
+              "adam_multi: the async parameter server's exclusive-writer gate / mirror take SGD only");
+  TORCH_CHECK(descs.is_cuda() && descs.scalar_type() == at::kLong && descs.is_contiguous(), "descs must be int64 GPU");
+  const dfa::ParamDesc* hd = nullptr;
+  if (descs_host.has_value() && descs_host->defined()) {
+    TORCH_CHECK(!descs_host->is_cuda() && descs_host->scalar_type() == at::kLong && descs_host->is_contiguous() &&
+                    descs_host->numel() == descs.numel(),
+                "descs_host must be the int64 CPU copy of descs");
+    hd = reinterpret_cast<const dfa::ParamDesc*>(descs_host->data_ptr());
+  }
+  TORCH_CHECK(ndesc > 0 && total_blocks > 0, "adam_multi: nothing to update");
+  TORCH_CHECK(descs.numel() * 8 >= ndesc * (int64_t)sizeof(dfa::ParamDesc), "descs too small");
+  need(master, at::kFloat, "master");
+  need(grad, at::kFloat, "grad");
+  need(m, at::kFloat, "m");
+  need(v, at::kFloat, "v");
+  need(wbf, at::kBFloat16, "wbf");
+  need(hyper, at::kFloat, "hyper");
+  need(state, at::kLong, "state");
+  TORCH_CHECK(hyper.numel() >= dfa::kAdamHyper,
+              "hyper needs [lr, beta1, beta2, eps, wd, grad_scale, decoupled, 1-beta1, 1-beta2]");
+  TORCH_CHECK(state.numel() >= dfa::kAdamState, "state needs [c1, c2, t, ticket]");
+  need(tickets, at::kLong, "tickets");
+  TORCH_CHECK(tickets.numel() >= dfa::kAdamTicketGroups * dfa::kAdamTicketStride, "ticket buffer too small");
+  TORCH_CHECK(grad.numel() >= master.numel() && m.numel() >= master.numel() && v.numel() >= master.numel(),
+              "grad / m / v smaller than master");
+  dfa::IndexStream is{};
+  fill_index_stream(is, idx_stream, idx_cursor, idx_dst, step_stats, run_stats);
+  const bool any = is.src || is.run_stats;
+  check_hip(dfa::adam_multi(reinterpret_cast<const dfa::ParamDesc*>(descs.data_ptr()), (int)ndesc, (int)total_blocks,
+                            master.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(),
+                            v.data_ptr<float>(), (dfa::bf16*)wbf.data_ptr(), hyper.data_ptr<float>(),
+                            reinterpret_cast<unsigned long long*>(state.data_ptr()),
+                            reinterpret_cast<unsigned long long*>(tickets.data_ptr()), cur_stream(),
+                            any ? &is : nullptr, hd),
+            "adam_multi");
 }
 
 void sum_buffers_py(torch::Tensor ptrs, int64_t nin, torch::Tensor out, double scale) {
@@ -2542,6 +2598,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("descs_host") = py::none(), py::arg("lenet_frag") = py::none(), py::arg("frag_w1") = 0,
         py::arg("frag_w2") = 0, py::arg("lenet_snap") = py::none(), py::arg("step_stats") = py::none(),
         py::arg("run_stats") = py::none(), py::arg("gate") = 0, py::arg("mirror") = 0);
+  m.def("adam_multi", &adam_multi_py, py::arg("descs"), py::arg("ndesc"), py::arg("total_blocks"), py::arg("master"),
+        py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("wbf"), py::arg("hyper"), py::arg("state"),
+        py::arg("tickets"), py::arg("idx_stream") = py::none(), py::arg("idx_cursor") = py::none(), py::arg("idx_dst") = py::none(),
+        py::arg("descs_host") = py::none(), py::arg("step_stats") = py::none(), py::arg("run_stats") = py::none(),
+        py::arg("gate") = 0, py::arg("mirror") = 0,
+        "Fused multi-tensor Adam / AdamW: master, m, v, bf16 compute copies and the step state in one launch");
+  m.attr("ADAM_TICKET_WORDS") = dfa::kAdamTicketGroups * dfa::kAdamTicketStride;
   m.def("sum_buffers", &sum_buffers_py);
   m.def("graph_upload", [](uintptr_t exec) {
     // stage an instantiated graph's kernel arguments / launch packets on the device now, outside any

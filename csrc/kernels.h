@@ -212,6 +212,15 @@ struct IndexStream {  // next-batch staging folded into the optimizer launch (cs
 hipError_t sgd_multi(const ParamDesc* descs, int ndesc, int total_blocks, float* master, const float* grad,
                      float* mom_buf, bf16* wbf, const float* hyper, int apply_update, hipStream_t st,
                      const IndexStream* is = nullptr, const ParamDesc* host_descs = nullptr);
+// Fused multi-tensor Adam / AdamW (csrc/adam.hip): sgd_multi's descriptors, grid and bf16 copies.
+// hyper = [lr, beta1, beta2, eps, wd, grad_scale, decoupled, 1-beta1, 1-beta2]; state = [c1, c2 (double bias
+// corrections 1 - beta^t), t, ticket], advanced by the launch itself; tickets = kAdamTicketGroups first-level
+// ticket words kAdamTicketStride apart, zero between launches.  ``is``: index stream / run statistics only
+// (frag, gate and mirror are rejected).
+constexpr int kAdamHyper = 9, kAdamState = 4, kAdamTicketGroups = 64, kAdamTicketStride = 64;
+hipError_t adam_multi(const ParamDesc* descs, int ndesc, int total_blocks, float* master, const float* grad,
+                      float* m_buf, float* v_buf, bf16* wbf, const float* hyper, unsigned long long* state,
+                      unsigned long long* tickets, hipStream_t st, const IndexStream* is = nullptr, const ParamDesc* host_descs = nullptr);
 hipError_t sum_buffers(const float* const* ins, int nin, float* out, long long n, float scale, hipStream_t st);
 hipError_t axpby(float* out, const float* a, const float* b, float alpha, float beta, long long n, hipStream_t st);
 // ---- BatchNorm (csrc/bn.hip)

@@ -73,4 +73,118 @@ __device__ __forceinline__ float sgd_apply_one(const ParamDesc& d, int i, float 
   return w;
 }
 
+// ---- the grid and the copy layouts shared by every multi-tensor optimizer (csrc/optim.hip, csrc/adam.hip)
+constexpr int SGD_ELEMS_PER_BLOCK = 1024;
+
+template <typename DT>
+__device__ __forceinline__ int find_desc(const DT& d, int n, int bid) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (d[mid].block_start <= bid) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Workgroup ``bid`` of a multi-tensor optimizer launch, d = descs[find_desc(descs, ndesc, bid)] its
+// tensor: calls update(i) -> the (new) fp32 value of element i for every element the workgroup owns and
+// writes that value's bf16 compute copies.
+// The optimizers differ in ``update`` only; which workgroup owns which element and where the copies go
+// is decided here, once.
+template <typename U>
+__device__ __forceinline__ void multi_tensor_body(const ParamDesc& d, bf16* __restrict__ wbf, int bid, const U& update) {
+  const int base = (bid - d.block_start) * SGD_ELEMS_PER_BLOCK;
+  const int K = d.T * d.Ci;
+  // d.pad_ bit 28: tile mode for a plain [N][K] matrix with a plain dgrad copy [Ci][T*N]: the workgroup
+  // owns a 32 (n) x 32 (k) tile; the update and the primary copy run along k (coalesced), and the
+  // dgrad copy is written through an LDS transpose as 64-byte runs along n (instead of 2-byte
+  // scatters one KpadT row apart)
+  if ((d.pad_ >> 28) & 1) {
+    __shared__ bf16 tt[32][34];
+    const int ntk = cdiv(K, 32);
+    const int tl = bid - d.block_start;
+    const int n0 = (tl / ntk) * 32, k0 = (tl % ntk) * 32;
+    const int Kp = round_up(K, 32);
+    const int KpT = round_up(d.T * d.N, 32);
+    const int cc = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int n = n0 + r0 + 8 * rr, k = k0 + cc;
+      if (n < d.N && k < K) {
+        const bf16 wb = f2bf(update(n * K + k));
+        wbf[d.bf_off + (long long)n * Kp + k] = wb;
+        tt[cc][r0 + 8 * rr] = wb;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int k = k0 + r0 + 8 * rr, n = n0 + cc;
+      if (n < d.N && k < K) {
+        const int t = k / d.Ci, ci = k - t * d.Ci;
+        wbf[d.bft_off + (long long)ci * KpT + t * d.N + n] = tt[r0 + 8 * rr][cc];
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int r = 0; r < SGD_ELEMS_PER_BLOCK / 256; ++r) {
+    const int i = base + r * 256 + threadIdx.x;
+    if (i >= d.numel) break;
+    emit_copies(d, i, update(i), wbf);
+  }
+}
+
+// Device-resident index stream: the optimizer is the last kernel of a training step, so one extra
+// workgroup of the same launch stages the NEXT step's batch indices (src[(cursor+1) % nsteps]) into
+// the static index buffer the step's first kernels read, then advances the cursor.  A replayed step
+// graph then needs no host-side copy (and no extra launch) to move to the next batch.
+__device__ __forceinline__ void index_stream_body(const IndexStream& is) {
+  if (is.src == nullptr) {  // run statistics only (no index stream bound)
+    if (threadIdx.x == 0 && is.run_stats != nullptr) {
+      is.run_stats[0] += is.step_stats[0];
+      is.run_stats[1] += is.step_stats[1];
+      is.run_stats[2] += 1.f;
+    }
+    return;
+  }
+  __shared__ long long next;
+  // thread 0 loads the cursor and, with it, the running / step statistics it updates at the end: one round
+  // trip for all of them (the statistics used to be read after the index copy, a third round trip on the
+  // launch's critical path)
+  float rs[3] = {0.f, 0.f, 0.f}, ss[2] = {0.f, 0.f};
+  if (threadIdx.x == 0) {
+    const long long c = *is.cursor;
+    if (is.run_stats != nullptr) {
+      rs[0] = is.run_stats[0], rs[1] = is.run_stats[1], rs[2] = is.run_stats[2];
+      ss[0] = is.step_stats[0], ss[1] = is.step_stats[1];
+    }
+    next = (c + 1) % is.nsteps;
+  }
+  __syncthreads();
+  const long long* src = is.src + next * is.B;
+  // all loads of a thread are issued before its stores (one memory round trip for B <= 8192)
+  constexpr int R = 16;
+  long long v[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = threadIdx.x + 256 * r;
+    v[r] = src[min(i, is.B - 1)];
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = threadIdx.x + 256 * r;
+    if (i < is.B) is.dst[i] = v[r];
+  }
+  for (int i = threadIdx.x + 256 * R; i < is.B; i += 256) is.dst[i] = src[i];
+  if (threadIdx.x == 0) {
+    *is.cursor = next;
+    if (is.run_stats != nullptr) {  // this step's stats are final: every step kernel precedes this launch
+      is.run_stats[0] = rs[0] + ss[0];
+      is.run_stats[1] = rs[1] + ss[1];
+      is.run_stats[2] = rs[2] + 1.f;
+    }
+  }
+}
+
 }  // namespace dfa

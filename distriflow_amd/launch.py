@@ -67,8 +67,15 @@ def build_parser() -> argparse.ArgumentParser:
     p = sub.add_parser("sync", help="synchronous all-reduce data parallelism")
     common(p)
     p.add_argument("--momentum", type=float, default=0.0)
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adamw", "model"],
+                   help="model = what the loaded model.json's training_config says (its lr, betas, epsilon and "
+                        "momentum replace --lr / --beta1 / --beta2 / --eps / --momentum)")
+    p.add_argument("--beta1", type=float, default=0.9)
+    p.add_argument("--beta2", type=float, default=0.999)
+    p.add_argument("--eps", type=float, default=1e-7)
+    p.add_argument("--weight-decay", type=float, default=0.0, help="L2 for sgd / adam, decoupled for adamw")
     p.add_argument("--graph", default=None, choices=["full", "split", "none"])
-    p.add_argument("--save-dir", default=None)
+    p.add_argument("--save-dir", default=None, help="checkpoint directory: weights and optimizer state per version")
     p.add_argument("--resume", action="store_true")
     p.add_argument("--steps", type=int, default=0, help="stop after this many steps (0 = full epochs)")
     p.add_argument("--min-updates", type=int, default=0,
@@ -270,12 +277,76 @@ def _logger(args, role):
 
 
 # ------------------------------------------------------------------------------------------ sync
+def sync_optimizer(args, net) -> dict:
+    """DataParallelTrainer's optimizer keywords from the ``sync`` arguments; ``--optimizer model`` reads
+    the model's Keras ``training_config`` (models/keras.py optimizer_from_keras)."""
+    kw = {"optimizer": args.optimizer, "lr": args.lr, "momentum": args.momentum,
+          "betas": (args.beta1, args.beta2), "eps": args.eps, "weight_decay": args.weight_decay}
+    if args.optimizer == "model":
+        from .models.keras import optimizer_from_keras
+        from .models.zoo import keras_cnn_topology
+
+        topo = getattr(net, "topology", None) or (keras_cnn_topology() if net.name == "keras_cnn" else None)
+        oc = optimizer_from_keras(topo) if topo else None
+        if oc is None:
+            raise SystemExit(f"--optimizer model: model {net.name!r} carries no Keras training_config")
+        kw.update(optimizer=oc["name"], lr=oc["lr"], momentum=oc["momentum"])
+        if oc["name"] == "adam":
+            kw.update(betas=oc["betas"], eps=oc["eps"])
+    if kw["optimizer"] != "sgd":
+        if kw["momentum"]:
+            raise SystemExit(f"--momentum belongs to sgd; {kw['optimizer']} takes --beta1 / --beta2")
+        kw["momentum"] = 0.0
+    return kw
+
+
+def save_sync_checkpoint(store, net, epoch: int, step: int) -> str:
+    """One checkpoint version of a ``sync`` job: the weights (tf.js LayersModel), the optimizer state beside
+    them (checkpoint/optim_state.py) and the resume record naming the optimizer and its hyper-parameters."""
+    from .checkpoint.optim_state import save_optimizer_state
+    from .checkpoint.tfjs import save_layers_model
+
+    v = store.new_version()
+    save_layers_model(net, store.path(v))
+    cfg = save_optimizer_state(net.store, store.path(v))
+    store.mark_current(v)
+    store.write_resume({"epoch": epoch, "step": step, "version": v, "optimizer": cfg})
+    return v
+
+
+def resume_sync_checkpoint(store, net, log=None) -> int:
+    """Load the last version of ``store`` into ``net`` (whose optimizer is already chosen): weights and
+    optimizer state.  Returns the step to continue from (0 without a checkpoint).  A checkpoint saved under
+    another optimizer is refused; one without optimizer state loads with zero state and a warning."""
+    from .checkpoint.optim_state import load_optimizer_state
+    from .checkpoint.tfjs import load_layers_model_weights
+
+    if store.last() is None:
+        return 0
+    rec = store.read_resume() or {}
+    saved = (rec.get("optimizer") or {}).get("name")
+    if saved is not None and saved != net.store.optimizer:
+        raise SystemExit(f"--resume: the checkpoint in {store.save_dir} was saved with optimizer {saved!r}; refusing "
+                         f"to resume under {net.store.optimizer!r}")
+    d = store.path(store.last())
+    load_layers_model_weights(net, os.path.join(d, "model.json"))
+    try:
+        have = load_optimizer_state(net.store, d)
+    except ValueError as e:
+        raise SystemExit(f"--resume: {e}") from e
+    if not have:
+        net.store.reset_optimizer_state()
+        if log is not None and (net.store.optimizer != "sgd" or net.store.momentum is not None):
+            log.log(f"warning: checkpoint {store.last()} holds no optimizer state; {net.store.optimizer} "
+                    "restarts from zero state")
+    return int(rec.get("step", 0))
+
+
 def run_sync(args) -> dict:
     import torch
     import torch.distributed as dist
 
     from .checkpoint.store import VersionedStore
-    from .checkpoint.tfjs import load_layers_model_weights, save_layers_model
     from .models.zoo import build_model
     from .parallel.comm import init_distributed, shutdown
     from .data.dataset import DistriDataset
@@ -291,16 +362,18 @@ def run_sync(args) -> dict:
     B = args.batch
     start_step = 0
     store = VersionedStore(args.save_dir) if args.save_dir else None
+    graph = args.graph or "full"
+    opt = sync_optimizer(args, net)
+    tr = DataParallelTrainer(net, graph=graph if dev.type == "cuda" else "none",
+                             min_updates_per_version=args.min_updates or None, **opt)
+    if opt["optimizer"] != "sgd":
+        log.log(f"optimizer {opt['optimizer']}: lr {opt['lr']:g}, betas {opt['betas']}, eps {opt['eps']:g}")
     if store is not None:
         store.setup()
         if args.resume and store.last() is not None:
-            load_layers_model_weights(net, os.path.join(store.path(store.last()), "model.json"))
+            start_step = resume_sync_checkpoint(store, net, log)
             rec = store.read_resume() or {}
-            start_step = int(rec.get("step", 0))
             log.log(f"resumed from version {store.last()} at step {start_step} (after epoch {rec.get('epoch')})")
-    graph = args.graph or "full"
-    tr = DataParallelTrainer(net, lr=args.lr, momentum=args.momentum, graph=graph if dev.type == "cuda" else "none",
-                             min_updates_per_version=args.min_updates or None)
     scale = 1.0 / 255.0 if x.dtype == torch.uint8 else 1.0
     # the DistriDataset's dispenser (epochs, per-epoch shuffle, FCFS order, completion) becomes the device
     # index stream: batch k of the schedule goes to rank k % world, and every step's update launch stages
@@ -354,10 +427,7 @@ def run_sync(args) -> dict:
         log.metric(event="epoch", epoch=epoch, step=step, loss=last_loss, images_per_s=seen / el)
         log.log(f"epoch {epoch}: loss {last_loss:.4f}, {seen / el:.0f} images/s")
         if epoch_end and store is not None and rank == 0:
-            v = store.new_version()
-            save_layers_model(net, store.path(v))
-            store.mark_current(v)
-            store.write_resume({"epoch": epoch, "step": step, "version": v})
+            save_sync_checkpoint(store, net, epoch, step)
         if world > 1:
             dist.barrier()
     if dev.type == "cuda":

@@ -35,6 +35,7 @@ from ..checkpoint import VersionedStore, load_flat, load_layers_model_weights, s
 from ..config import compile_args
 from ..losses import accuracy, get_loss
 from .net import Net
+from .params import OPTIMIZERS
 
 
 class DistriModel(ABC):
@@ -211,7 +212,9 @@ class EngineModel(DistriModel):
     """The MI355X engine behind the DistriModel contract (reference DistributedTfModel)."""
 
     def __init__(self, model: ModelSource, compile_config: Optional[dict] = None, device=None,
-                 strict_loss: bool = False):
+                 strict_loss: bool = False, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-7):
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         self._src = model
         self._device = device
         self.compile = compile_args(compile_config)
@@ -220,6 +223,10 @@ class EngineModel(DistriModel):
         self.net: Optional[Net] = model if isinstance(model, Net) else None
         self.momentum = 0.0
         self.weight_decay = 0.0
+        # "sgd" | "adam" | "adamw" (ParamStore.set_optimizer); betas / eps are Adam's
+        self.optimizer = optimizer
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = float(eps)
         self._strict_loss = strict_loss
         # checked now when the output is known (or cannot matter); a sigmoidCrossEntropy compile loss on a
         # not-yet-fetched model is checked once fetch_initial() knows whether the model ends in sigmoid
@@ -260,6 +267,9 @@ class EngineModel(DistriModel):
         return self.net
 
     def _sync_hyper(self, grad_scale: float = 1.0):
+        st = self.net.store
+        if st.optimizer != self.optimizer or (self.optimizer != "sgd" and st._adam_cfg != (*self.betas, self.eps)):
+            st.set_optimizer(self.optimizer, self.betas[0], self.betas[1], self.eps)
         self.net.store.set_hyper(self.learning_rate, self.momentum, self.weight_decay, grad_scale)
 
     @property
@@ -293,19 +303,19 @@ class EngineModel(DistriModel):
         return [st.gradient(s.name).clone() for s in st.specs]
 
     def update_flat(self, flat_grad: torch.Tensor, scale: float = 1.0) -> None:
-        """w -= lr * scale * g — ONE fused launch over every parameter."""
+        """w -= lr * scale * g (or the Adam / AdamW update) — ONE fused launch over every parameter."""
         st = self._need().store
         if flat_grad.data_ptr() != st.grad.data_ptr():
             st.grad[: flat_grad.numel()].copy_(flat_grad.reshape(-1))
         self._sync_hyper(scale)
-        st.sgd_step()
+        st.step()
 
     def update(self, grads: Sequence[torch.Tensor]) -> None:
         st = self._need().store
         for s, g in zip(st.specs, grads):
             st.gradient(s.name).copy_(torch.as_tensor(g).reshape(s.shape))
         self._sync_hyper(1.0)
-        st.sgd_step()
+        st.step()
 
     def predict(self, x) -> torch.Tensor:
         net = self._need()

@@ -195,6 +195,37 @@ def layers_from_keras(model_config: dict) -> tuple[list[Layer], tuple]:
     return layers, input_shape
 
 
+def optimizer_from_keras(topology: dict) -> dict | None:
+    """The optimizer a Keras / tf.js ``modelTopology`` was compiled with, from
+    ``training_config.optimizer_config``: ``{"name": "adam" | "sgd", "lr", "betas", "eps", "momentum"}``
+    (betas / eps None for SGD, momentum 0.0 for Adam), or None when the topology names no optimizer.
+    Both the ``lr`` and the ``learning_rate`` spelling are read.  AMSGrad, a learning-rate ``decay`` and
+    other optimizer classes are not implemented and raise instead of training something else."""
+    tc = (topology or {}).get("training_config") or {}
+    oc = tc.get("optimizer_config")
+    if not oc:
+        return None
+    cls = oc.get("class_name")
+    cfg = oc.get("config") or {}
+    if cls not in ("Adam", "SGD"):
+        raise NotImplementedError(f"Keras optimizer {cls!r} (supported: Adam, SGD)")
+    if cfg.get("amsgrad"):
+        raise NotImplementedError("Adam with amsgrad=true")
+    if float(cfg.get("decay") or 0.0) != 0.0:
+        raise NotImplementedError(f"optimizer learning-rate decay {cfg['decay']!r}")
+    lr = cfg.get("learning_rate", cfg.get("lr"))
+    if lr is None:
+        lr = 0.001 if cls == "Adam" else 0.01  # the Keras defaults
+    if isinstance(lr, dict):
+        raise NotImplementedError("a learning-rate schedule object")
+    if cls == "Adam":
+        return {"name": "adam", "lr": float(lr), "betas": (float(cfg.get("beta_1", 0.9)), float(cfg.get("beta_2", 0.999))),
+                "eps": float(cfg.get("epsilon") or 1e-7), "momentum": 0.0}
+    if cfg.get("nesterov"):
+        raise NotImplementedError("Keras SGD with nesterov=true from a model.json")
+    return {"name": "sgd", "lr": float(lr), "betas": None, "eps": None, "momentum": float(cfg.get("momentum", 0.0))}
+
+
 def keras_config_from_layers(layers: list[Layer], input_shape: tuple, name: str = "sequential") -> dict:
     """Inverse of :func:`layers_from_keras` (Keras 2.x Sequential JSON, as tf.js writes it)."""
     out = []

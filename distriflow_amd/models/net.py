@@ -699,8 +699,7 @@ class Net:
         """Every tensor a training step mutates besides gradients/activations: master weights,
         optimizer state, BN running statistics, the dropout step counter."""
         out = [self.store.master, self.step_dev]
-        if self.store.momentum is not None:
-            out.append(self.store.momentum)
+        out += list(self.store.optimizer_state().values())  # SGD momentum / Adam m, v and step state
         for l in self._all_leaf_layers():
             if isinstance(l, BatchNorm) and hasattr(l, "run_mean"):
                 out += [l.run_mean, l.run_var]

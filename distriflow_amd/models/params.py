@@ -7,9 +7,9 @@ LayersModel's ``trainableWeights`` / ``weightsManifest`` (SURVEY §2.9 quirk 3: 
 
   * the gradient all-reduce is a single RCCL call on one buffer (or a few contiguous buckets,
     since backward produces gradients in reverse layer order = a growing suffix of the buffer);
-  * the SGD update is one fused multi-tensor launch (``sgd_multi``) that also re-emits the bf16
-    compute copies of every weight matrix in the two MFMA layouts ([N][K] and the dgrad layout),
-    zero padded to 16 x 32 tiles;
+  * the optimizer update is one fused multi-tensor launch (``sgd_multi``, or ``adam_multi`` for
+    Adam / AdamW) that also re-emits the bf16 compute copies of every weight matrix in the two MFMA
+    layouts ([N][K] and the dgrad layout), zero padded to 16 x 32 tiles;
   * serialisation (protocol / checkpoints) is a view of one buffer.
 
 Matrix parameters use the layout [N][T*Ci] (dense: [out][in]; conv: OHWI = [Cout][KH*KW*Cin]).
@@ -26,6 +26,7 @@ import torch
 from .. import native
 
 SGD_ELEMS_PER_BLOCK = 1024
+OPTIMIZERS = ("sgd", "adam", "adamw")
 
 
 def _r(a, b):
@@ -95,6 +96,15 @@ class ParamStore:
         self._spec = {s.name: s for s in self.specs}
         self.hyper = torch.zeros(5, dtype=torch.float32, device=self.device)
         self._hyper_host = None
+        # Adam / AdamW (set_optimizer): first and second moments, the device hyper-parameters and the step
+        # state [c1, c2 (float64 bits: the bias corrections 1 - beta^t), t, ticket] (csrc/adam.hip)
+        self.optimizer = "sgd"
+        self.adam_m: Optional[torch.Tensor] = None
+        self.adam_v: Optional[torch.Tensor] = None
+        self.adam_state: Optional[torch.Tensor] = None
+        self.adam_hyper: Optional[torch.Tensor] = None
+        self._adam_cfg = (0.9, 0.999, 1e-7)
+        self._adam_hyper_host = None
         self._init_values(seed)
         if self.compute_bf16:
             self._build_compute_copies()
@@ -262,6 +272,79 @@ class ParamStore:
             self._hyper_host = h
         if momentum != 0.0 and self.momentum is None:
             self.momentum = torch.zeros_like(self.master)
+        self._push_adam_hyper()
+
+    def set_optimizer(self, name: str, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-7):
+        """Choose the update :meth:`step` applies: ``"sgd"`` (momentum / weight decay from
+        :meth:`set_hyper`), ``"adam"`` (weight decay as L2, added to the gradient) or ``"adamw"`` (decoupled
+        weight decay).  The learning rate, weight decay and gradient scale stay :meth:`set_hyper`'s.  The
+        moment buffers and the step state are allocated on first use and kept (zeroed by
+        :meth:`reset_optimizer_state`)."""
+        if name not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {name!r}")
+        if name != "sgd":
+            if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0 and eps > 0.0):
+                raise ValueError(f"Adam needs 0 <= beta < 1 and eps > 0, got {beta1}, {beta2}, {eps}")
+            self._adam_cfg = (float(beta1), float(beta2), float(eps))
+            if self.adam_m is None:
+                self.adam_m = torch.zeros_like(self.master)
+                self.adam_v = torch.zeros_like(self.master)
+                self.adam_state = torch.zeros(4, dtype=torch.int64, device=self.device)
+                self.adam_hyper = torch.zeros(12, dtype=torch.float32, device=self.device)
+                if self.compute_bf16:  # the launch's first-level ticket words (zero between launches)
+                    self._adam_tickets = torch.zeros(native.require().ADAM_TICKET_WORDS, dtype=torch.int64,
+                                                     device=self.device)
+        self.optimizer = name
+        self._push_adam_hyper()
+
+    def _push_adam_hyper(self):
+        """adam_hyper = [lr, beta1, beta2, eps, wd, grad_scale, decoupled, 1-beta1, 1-beta2] (fp32, device).
+        1 - beta is rounded from the double: 1.f - 0.999f would be 1.3e-5 off 0.001."""
+        if self.optimizer == "sgd" or self._hyper_host is None:
+            return
+        lr, _, wd, gs, _ = self._hyper_host
+        b1, b2, eps = self._adam_cfg
+        h = (lr, b1, b2, eps, wd, gs, 1.0 if self.optimizer == "adamw" else 0.0, 1.0 - b1, 1.0 - b2)
+        if h != self._adam_hyper_host:
+            self.adam_hyper[:9].copy_(torch.tensor(h, dtype=torch.float32), non_blocking=False)
+            self._adam_hyper_host = h
+
+    @property
+    def adam_t(self) -> int:
+        """Adam updates applied so far (read from the device)."""
+        return 0 if self.adam_state is None else int(self.adam_state[2])
+
+    def reset_optimizer_state(self):
+        for t in (self.momentum, self.adam_m, self.adam_v, self.adam_state):
+            if t is not None:
+                t.zero_()
+
+    def optimizer_config(self) -> dict:
+        lr, mom, wd, _, nest = self._hyper_host or (0.0, 0.0, 0.0, 1.0, 0.0)
+        cfg = {"name": self.optimizer, "lr": lr, "weight_decay": wd}
+        if self.optimizer == "sgd":
+            cfg.update(momentum=mom, nesterov=bool(nest))
+        else:
+            cfg.update(beta1=self._adam_cfg[0], beta2=self._adam_cfg[1], eps=self._adam_cfg[2])
+        return cfg
+
+    def optimizer_state(self) -> dict:
+        """The optimizer's own tensors by name (checkpoints; ``Net.state_tensors``): SGD's momentum buffer
+        when it has one, Adam's m, v and step state."""
+        if self.optimizer == "sgd":
+            return {} if self.momentum is None else {"momentum": self.momentum}
+        return {"m": self.adam_m, "v": self.adam_v, "state": self.adam_state}
+
+    def load_optimizer_state(self, tensors: dict):
+        mine = self.optimizer_state()
+        if set(tensors) != set(mine):
+            raise ValueError(f"optimizer state {sorted(tensors)} does not fit optimizer {self.optimizer!r} "
+                             f"(expects {sorted(mine)})")
+        for k, t in mine.items():
+            v = tensors[k]
+            if v.numel() != t.numel() or v.dtype != t.dtype:
+                raise ValueError(f"optimizer state {k!r}: {tuple(v.shape)} {v.dtype}, expected {tuple(t.shape)} {t.dtype}")
+            t.copy_(v.reshape(t.shape))
 
     def sgd_step(self, index_stream=None, run_stats=None, ps_gate: int = 0, ps_mirror: int = 0):
         """w -= lr * (grad_scale * g [+ wd w]) (momentum optional); uses the device-side hyper tensor.
@@ -272,6 +355,8 @@ class ParamStore:
         ``ps_gate`` / ``ps_mirror`` (device addresses, async PS with one rank: PSComm.excl_gate / excl_mirror):
         the update runs only if the admission word says accepted, and the new weights are also written to
         the parameter server's shard."""
+        if self.optimizer != "sgd":
+            return self._adam_step(index_stream, run_stats, ps_gate, ps_mirror)
         if self.compute_bf16:
             src, cur, dst = index_stream if index_stream is not None else (None, None, None)
             kw = self._frag_kw(True)
@@ -283,6 +368,18 @@ class ParamStore:
                                        self.momentum, self.wbf, self.hyper, True, src, cur, dst,
                                        self._descs_host, **kw)
             return
+        self._cpu_stream_and_stats(index_stream, run_stats)
+        lr, mom, wd, gs, nest = self._hyper_host
+        g = self._cpu_scaled_grad(gs)
+        if wd:
+            g = g + wd * self.master
+        if mom:
+            self.momentum.mul_(mom).add_(g)
+            g = g + mom * self.momentum if nest else self.momentum
+        self.master.sub_(lr * g)
+
+    def _cpu_stream_and_stats(self, index_stream, run_stats):
+        """CPU engine: what the optimizer launch's extra workgroup does on the GPU."""
         if index_stream is not None:
             src, cur, dst = index_stream
             nxt = (int(cur[0]) + 1) % src.shape[0]
@@ -291,18 +388,57 @@ class ParamStore:
         if run_stats is not None:
             run_stats[1][:2] += run_stats[0][:2]
             run_stats[1][2] += 1.0
-        lr, mom, wd, gs, nest = self._hyper_host
+
+    def _cpu_scaled_grad(self, gs) -> torch.Tensor:
+        """grad_scale * grad with the alignment padding of the flat buffer forced to 0."""
         if not hasattr(self, "_valid"):
             self._valid = torch.zeros(self.total, dtype=torch.bool, device=self.device)
             for s in self.specs:
                 self._valid[self.offsets[s.name]: self.offsets[s.name] + s.numel] = True
-        g = torch.where(self._valid, self.grad * gs, torch.zeros((), device=self.device))
-        if wd:
-            g = g + wd * self.master
-        if mom:
-            self.momentum.mul_(mom).add_(g)
-            g = g + mom * self.momentum if nest else self.momentum
-        self.master.sub_(lr * g)
+        return torch.where(self._valid, self.grad * gs, torch.zeros((), device=self.device))
+
+    def step(self, index_stream=None, run_stats=None, ps_gate: int = 0, ps_mirror: int = 0):
+        """Apply the chosen optimizer (:meth:`set_optimizer`) to the gradient buffer: one fused launch on the
+        GPU whatever the optimizer.  Arguments as :meth:`sgd_step`."""
+        return self.sgd_step(index_stream, run_stats, ps_gate, ps_mirror)
+
+    def _adam_step(self, index_stream, run_stats, ps_gate, ps_mirror):
+        """Adam / AdamW (csrc/adam.hip; the CPU branch is the same arithmetic in fp32 torch ops)."""
+        if ps_gate or ps_mirror:
+            raise ValueError("the async parameter server's exclusive-writer update takes SGD only")
+        if self.compute_bf16:
+            src, cur, dst = index_stream if index_stream is not None else (None, None, None)
+            kw = {}
+            if run_stats is not None:
+                kw.update(step_stats=run_stats[0], run_stats=run_stats[1])
+            native.require().adam_multi(self._descs, self._ndesc, self._sgd_blocks, self.master, self.grad,
+                                        self.adam_m, self.adam_v, self.wbf, self.adam_hyper, self.adam_state,
+                                        self._adam_tickets, src, cur, dst, self._descs_host, **kw)
+            if self.lenet_frag is not None:
+                # the LeNet-5 fragment rebuild recomputes the SGD update: under Adam the fragments are
+                # stale after every update and the next fused train step launches its prep kernel
+                self.lenet_state = "stale"
+            return
+        self._cpu_stream_and_stats(index_stream, run_stats)
+        h = self.adam_hyper  # 0-dim fp32 operands: every product below is rounded to fp32 like the kernel's
+        lr, b1, b2, eps, wd, gs, omb1, omb2 = h[0], h[1], h[2], h[3], h[4], h[5], h[7], h[8]
+        g = self._cpu_scaled_grad(gs)
+        # bias corrections c = 1 - beta^t as the double recurrence c' = (1 - beta) + beta * c from c = 0
+        corr = self.adam_state[:2].view(torch.float64)
+        c1 = float(omb1) + float(b1) * float(corr[0])
+        c2 = float(omb2) + float(b2) * float(corr[1])
+        w = self.master
+        if float(wd) != 0.0:
+            if self.optimizer == "adamw":
+                w.mul_(1.0 - lr * wd)
+            else:
+                g = g + wd * w
+        self.adam_m.mul_(b1).add_(omb1 * g)
+        self.adam_v.mul_(b2).add_((omb2 * g) * g)
+        c1f, c2f = torch.tensor(c1, dtype=torch.float32), torch.tensor(c2, dtype=torch.float32)
+        w.sub_((lr * (self.adam_m / c1f)) / (torch.sqrt(self.adam_v / c2f) + eps))
+        corr[0], corr[1] = c1, c2
+        self.adam_state[2] += 1
 
     def apply_delta(self, delta: torch.Tensor, lr: float):
         """master -= lr * delta  (server-side update with an already-aggregated gradient)."""

@@ -46,7 +46,7 @@ import torch.distributed as dist
 
 from .. import native
 from ..diagnostics import diag, on as diag_on
-from .data_parallel import DataParallelTrainer, shared_gpu_exch_blocks
+from .data_parallel import DataParallelTrainer, require_sgd, shared_gpu_exch_blocks
 
 
 class AsyncPSTrainer(DataParallelTrainer):
@@ -57,10 +57,11 @@ class AsyncPSTrainer(DataParallelTrainer):
 
     def __init__(self, net, lr: float = 0.001, max_staleness: int = 4, group=None, server_rank: int = 0,
                  graph: str = "full", timeout_s: float = 30.0, owner_apply: Optional[bool] = None,
-                 joinable: bool = False):
+                 joinable: bool = False, optimizer: str = "sgd"):
         """``joinable``: workers outside this process group may attach later (:meth:`publish` /
         :meth:`attach`, parallel/elastic.py): uncached buffers and no exclusive-writer shortcuts even at one
         rank."""
+        require_sgd(optimizer, type(self).__name__, "the master is updated by the parameter-server kernels")
         if not net.is_gpu:
             raise RuntimeError("AsyncPSTrainer is the GPU path; use AsynchronousSGDServer/Client on CPU")
         super().__init__(net, lr=lr, group=group, overlap=False, graph="full" if graph == "split" else graph,

@@ -28,13 +28,29 @@ import torch.distributed as dist
 
 from .. import native, ops
 from ..diagnostics import on as _diag_on
+from ..models.params import OPTIMIZERS
+
+
+def require_sgd(optimizer: str, who: str, why: str):
+    """The engines whose update is not the store's optimizer launch take SGD only, and say so."""
+    if optimizer != "sgd":
+        raise ValueError(f"{who} supports optimizer='sgd' only ({why}); got {optimizer!r}")
 
 
 class DataParallelTrainer:
     def __init__(self, net, lr: float = 0.001, momentum: float = 0.0, weight_decay: float = 0.0,
                  group=None, bucket_mb: Optional[float] = None, overlap: bool = True, graph: str = "full",
                  broadcast_init: bool = True, allreduce: str = "auto", p2p_max_mb: float = 4.0,
-                 min_updates_per_version: Optional[int] = None):
+                 min_updates_per_version: Optional[int] = None, optimizer: str = "sgd", betas=(0.9, 0.999),
+                 eps: float = 1e-7):
+        """``optimizer``: "sgd" (``momentum``), "adam" (``weight_decay`` as L2) or "adamw" (decoupled
+        ``weight_decay``), with Adam's ``betas`` / ``eps``; at every world size (the gradient exchange is the
+        same, and every rank applies the same update to the same summed gradient)."""
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+        if optimizer != "sgd" and momentum:
+            raise ValueError(f"momentum belongs to SGD; {optimizer} takes betas")
+        self.optimizer, self.betas, self.eps = optimizer, (float(betas[0]), float(betas[1])), float(eps)
         self.net = net
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -95,6 +111,7 @@ class DataParallelTrainer:
         if broadcast_init and self.world > 1:
             dist.broadcast(net.store.master, src=0, group=group)
             net.store.refresh_compute()
+        net.store.set_optimizer(optimizer, self.betas[0], self.betas[1], self.eps)
         net.store.set_hyper(lr, momentum, weight_decay, grad_scale=self._grad_scale())
 
     def _grad_scale(self) -> float:
@@ -236,7 +253,7 @@ class DataParallelTrainer:
         if pt is not None:
             pt.stop("comm")
             pt.start("update")
-        self.net.store.sgd_step(self._index_stream, run_stats=(stats, self.run_stats))
+        self.net.store.step(self._index_stream, run_stats=(stats, self.run_stats))
         if pt is not None:
             pt.stop("update")
         return stats
@@ -244,7 +261,11 @@ class DataParallelTrainer:
     def _fused_step_ok(self) -> bool:
         """The fused LeNet-5 step (train + reduce/exchange/update: two launches) is usable: single rank,
         or every rank on the one-shot p2p path (its communicator carries the LL exchange slots) and the
-        exchange passed its real-kernel self-test (:meth:`_verify_fused_exchange`)."""
+        exchange passed its real-kernel self-test (:meth:`_verify_fused_exchange`).  SGD only: the reduce
+        kernel applies the SGD update itself, so any other optimizer takes compute_gradients, the
+        all-reduce and the optimizer launch."""
+        if self.optimizer != "sgd":
+            return False
         if not (self.fused_update and getattr(self.net, "lenet_fused", False)
                 and self.net.store.lenet_frag is not None):
             return False
@@ -267,7 +288,7 @@ class DataParallelTrainer:
         Reference semantics held here: the synchronous server's mean of the K uploaded gradients
         (/root/reference/src/server/federated_server.ts:92-117)."""
         if (self.fused_selftest or self.world == 1 or not self._step_all_reduces or not _diag_on("fused_selftest")
-                or getattr(self, "data", None) is None):
+                or getattr(self, "data", None) is None or self.optimizer != "sgd"):
             return
         if not (self.fused_update and getattr(self.net, "lenet_fused", False) and self.net.store.lenet_frag is not None
                 and self.p2p is not None and getattr(self.p2p.comm, "ll_slots", 0) >= 256
@@ -358,7 +379,8 @@ class DataParallelTrainer:
         if self._fused_step_ok():
             return ("train+reduce/exchange/update" if self.world > 1 and self._step_all_reduces
                     else "train+reduce/update")
-        return "compute+allreduce+sgd" if self.world > 1 else "compute+sgd"
+        opt = "sgd" if self.optimizer == "sgd" else "adam"
+        return f"compute+allreduce+{opt}" if self.world > 1 else f"compute+{opt}"
 
     def timed_eager_steps(self, n: int) -> dict:
         """Per-phase GPU milliseconds per step over ``n`` eager (uncaptured) steps on the bound index
@@ -499,7 +521,7 @@ class DataParallelTrainer:
                     self._gather()
                     self.stats = self.net.compute_gradients(self.xb, self.yb)
                 with torch.cuda.graph(g2, stream=cs):
-                    self.net.store.sgd_step(self._index_stream, run_stats=(self.stats, self.run_stats))
+                    self.net.store.step(self._index_stream, run_stats=(self.stats, self.run_stats))
                 self._graph = (g, g2)
         except Exception:
             # a collective that cannot be captured (e.g. gloo on device tensors) leaves the capture open

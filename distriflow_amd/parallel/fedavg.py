@@ -20,14 +20,15 @@ from __future__ import annotations
 
 import torch
 
-from .data_parallel import DataParallelTrainer
+from .data_parallel import DataParallelTrainer, require_sgd
 
 
 class FedAvgTrainer(DataParallelTrainer):
     _step_all_reduces = False  # local steps exchange nothing (the fused LeNet-5 step stays local)
 
     def __init__(self, net, lr: float = 0.05, local_steps: int = 20, group=None, graph: str = "full",
-                 allreduce: str = "auto"):
+                 allreduce: str = "auto", optimizer: str = "sgd"):
+        require_sgd(optimizer, "FedAvgTrainer", "whether optimizer state survives the weight averaging is undecided")
         super().__init__(net, lr=lr, group=group, overlap=False, graph=graph, allreduce=allreduce)
         self.local_steps = int(local_steps)
         self.rounds = 0
