@@ -25,9 +25,7 @@
 // Microbatch dispatch is at-least-once and epoch scoped (claim_microbatch / complete_microbatch):
 // a batch is complete only once a gradient for it is admitted; rejected ones are dispatched again.
 //
-// Control buffer layout (server rank): [0] u32 version, [8] u32 fully applied, [16] u64 batch cursor, [32] u32 dataset epoch,
-// [36] u32 batches completed in it, [48] u64 completed / redispatched / skipped / duplicate counters,
-// [256] u32 done_epoch[kPSMaxBatches], then u32 claimed_epoch[kPSMaxBatches].
+// Layout of the server rank's control buffer and of every rank's local words: csrc/ps_layout.h.
 #include "common.h"
 #include "kernels.h"
 #include "ps_device.h"

@@ -1,0 +1,1013 @@
+// Single-kernel launches: implicit GEMM, pooling, losses, dropout, gather, merge, activations, GAP, metrics;
+// BatchNorm (csrc/bn.hip); the optimizers (csrc/optim.hip, csrc/adam.hip) and the fp32 buffer arithmetic.
+#include "bindings_util.h"
+
+namespace dfa_py {
+namespace {
+
+void igemm_fwd_py(torch::Tensor src, torch::Tensor w, c10::optional<torch::Tensor> bias,
+                  c10::optional<torch::Tensor> mask, torch::Tensor out, int64_t M, int64_t N, int64_t K, int64_t Kpad,
+                  int64_t lda, int64_t ldc, std::vector<int64_t> geom, int64_t mode, bool relu, double alpha,
+                  c10::optional<torch::Tensor> res, c10::optional<torch::Tensor> resmask, double drop_p,
+                  int64_t drop_seed, c10::optional<torch::Tensor> drop_step, c10::optional<torch::Tensor> pool_code,
+                  int64_t drop_step_add, c10::optional<torch::Tensor> bn_ws, c10::optional<torch::Tensor> bn_ticket,
+                  int64_t bn_mode, std::vector<torch::Tensor> bn_vecs, c10::optional<torch::Tensor> bn_x,
+                  double bn_momentum, double bn_eps, double bn_gscale, c10::optional<torch::Tensor> bacc,
+                  int64_t bacc_mode, std::vector<torch::Tensor> bacc_in, c10::optional<torch::Tensor> bacc2,
+                  std::vector<torch::Tensor> bacc2_in) {
+  need(src, at::kBFloat16, "src");
+  need(w, at::kBFloat16, "w");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous(), "out must be a contiguous GPU tensor");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat, "out must be bf16 or fp32");
+  TORCH_CHECK(Kpad % 32 == 0 && Kpad >= K, "Kpad must be a multiple of 32 and >= K");
+  TORCH_CHECK(w.numel() >= ((N + 15) / 16 * 16) * Kpad, "weight buffer smaller than [Npad16][Kpad]");
+  const bool pooled = has(pool_code);
+  if (pooled) {
+    TORCH_CHECK(mode == 1 && M % 4 == 0 && ldc == N, "pooled conv: forward conv, M % 4 == 0, ldc == N");
+    TORCH_CHECK(pool_code->is_cuda() && pool_code->is_contiguous() && pool_code->scalar_type() == at::kByte &&
+                    pool_code->numel() >= M / 4 * N,
+                "pool_code must be a uint8 GPU tensor of [M/4][N]");
+    TORCH_CHECK(out.numel() >= M / 4 * N, "pooled out too small for [M/4][N]");
+  } else {
+    TORCH_CHECK(out.numel() >= (M - 1) * ldc + N, "out too small for [M][ldc]");
+  }
+  TORCH_CHECK(ldc >= N, "ldc < N");
+  dfa::IGemmArgs a{};
+  set_conv_geom(a, geom, (int)mode);
+  if (mode == 0) {
+    TORCH_CHECK(src.numel() >= (M - 1) * lda + K, "src too small for [M][lda]");
+  } else {
+    TORCH_CHECK(a.OH > 0 && a.OW > 0 && M % (a.OH * a.OW) == 0, "M must be B*OH*OW");
+    const int64_t Bn = M / (a.OH * a.OW);
+    TORCH_CHECK(src.numel() >= Bn * a.SH * a.SW * a.SC, "src too small for the conv geometry");
+    TORCH_CHECK(K == (int64_t)a.KH * a.KW * a.SC, "K must be KH*KW*C");
+    TORCH_CHECK(a.KH < 128 && a.KW < 128 && a.SC < 65536, "conv geometry out of range");
+  }
+  a.bias = opt_ptr<const float>(bias, at::kFloat, "bias", N, "bias too small");
+  a.mask = opt_ptr<const dfa::bf16>(mask, at::kBFloat16, "mask", (M - 1) * ldc + N, "mask too small");
+  a.res = opt_ptr<const dfa::bf16>(res, at::kBFloat16, "residual", (M - 1) * ldc + N, "residual too small");
+  a.resmask = opt_ptr<const dfa::bf16>(resmask, at::kBFloat16, "residual", (M - 1) * ldc + N, "residual too small");
+  TORCH_CHECK(!has(resmask) || has(res), "resmask without res");
+  a.src = reinterpret_cast<const dfa::bf16*>(src.data_ptr());
+  a.w = reinterpret_cast<const dfa::bf16*>(w.data_ptr());
+  a.out = out.data_ptr();
+  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.Kpad = (int)Kpad; a.lda = (int)lda; a.ldc = (int)ldc;
+  a.relu = relu ? 1 : 0;
+  a.out_f32 = out.scalar_type() == at::kFloat ? 1 : 0;
+  a.alpha = (float)alpha;
+  a.drop = drop_from(drop_p, drop_seed, drop_step, drop_step_add);
+  if (pooled) {
+    a.pool_code = pool_code->data_ptr<uint8_t>();
+    TORCH_CHECK(dfa::igemm64_pool_supported(a), "pooled conv: unsupported geometry / alignment");
+  }
+  if (has(bn_ws)) {
+    // BatchNorm statistics finalised inside this launch (kernels.h BnEpi)
+    need(*bn_ws, at::kFloat, "bn_ws");
+    TORCH_CHECK(has(bn_ticket), "bn_ws needs bn_ticket");
+    need(*bn_ticket, at::kInt, "bn_ticket");
+    int ntn = 0;
+    const int ntm = dfa::igemm64_bn_layout(a, (int)mode, &ntn);
+    TORCH_CHECK(ntm > 0, "bn: this conv launch cannot finalise BatchNorm statistics");
+    const int ngrp = (ntm + 15) / 16;
+    TORCH_CHECK(bn_ws->numel() >= (int64_t)(ntm + ngrp) * 2 * N, "bn_ws too small");
+    TORCH_CHECK(bn_ticket->numel() >= (int64_t)ntn * (1 + ngrp), "bn_ticket too small");
+    TORCH_CHECK(out.scalar_type() == at::kBFloat16, "bn: bf16 output");
+    dfa::BnEpi& e = a.bn;
+    e.part = bn_ws->data_ptr<float>();
+    e.ticket = reinterpret_cast<unsigned*>(bn_ticket->data_ptr<int>());
+    e.ntm = ntm;
+    e.ngrp = ngrp;
+    e.mode = (int)bn_mode;
+    e.momentum = (float)bn_momentum;
+    e.eps = (float)bn_eps;
+    e.gscale = (float)bn_gscale;
+    for (auto& v : bn_vecs) {
+      need(v, at::kFloat, "bn vector");
+      TORCH_CHECK(v.numel() >= N, "bn vector smaller than N");
+    }
+    if (bn_mode == 0) {
+      TORCH_CHECK(bn_vecs.size() == 4, "bn mode 0: [mean, invstd, run_mean, run_var]");
+      e.mean_out = bn_vecs[0].data_ptr<float>();
+      e.invstd_out = bn_vecs[1].data_ptr<float>();
+      e.run_mean = bn_vecs[2].data_ptr<float>();
+      e.run_var = bn_vecs[3].data_ptr<float>();
+    } else {
+      TORCH_CHECK(bn_mode == 1 && bn_vecs.size() == 6, "bn mode 1: [mean, invstd, gamma, dgamma, dbeta, coef]");
+      TORCH_CHECK(has(bn_x), "bn mode 1 needs the BN input");
+      need(*bn_x, at::kBFloat16, "bn_x");
+      TORCH_CHECK(bn_x->numel() >= (M - 1) * ldc + N, "bn_x too small");
+      TORCH_CHECK(bn_vecs[5].numel() >= 3 * N, "bn coef must hold [3][N]");
+      e.x = reinterpret_cast<const dfa::bf16*>(bn_x->data_ptr());
+      e.mean = bn_vecs[0].data_ptr<float>();
+      e.invstd = bn_vecs[1].data_ptr<float>();
+      e.gamma = bn_vecs[2].data_ptr<float>();
+      e.dgamma = bn_vecs[3].data_ptr<float>();
+      e.dbeta = bn_vecs[4].data_ptr<float>();
+      e.coef = bn_vecs[5].data_ptr<float>();
+    }
+  }
+  if (has(bacc)) {
+    // BatchNorm sums accumulated by the epilogue (kernels.h BnAcc): acc [nrep][2][N] fp64; mode 1 inputs
+    // [x, mean, invstd] of the BatchNorm (and of a second one sharing the gradient)
+    need(*bacc, at::kDouble, "bacc");
+    TORCH_CHECK(bacc->numel() % (2 * N) == 0, "bacc must be [nrep][2][N]");
+    dfa::BnAcc& e = a.bacc;
+    e.acc = bacc->data_ptr<double>();
+    e.nrep = (int)(bacc->numel() / (2 * N));
+    e.mode = (int)bacc_mode;
+    TORCH_CHECK(bacc_mode == 0 || bacc_mode == 1, "bacc_mode 0 (forward) or 1 (backward)");
+    auto inputs = [&](const std::vector<torch::Tensor>& v, const dfa::bf16** x, const float** mu, const float** is) {
+      TORCH_CHECK(v.size() == 3, "bacc mode 1 inputs: [x, mean, invstd]");
+      need(v[0], at::kBFloat16, "bacc x");
+      TORCH_CHECK(v[0].numel() >= (M - 1) * ldc + N, "bacc x too small");
+      need(v[1], at::kFloat, "bacc mean");
+      need(v[2], at::kFloat, "bacc invstd");
+      TORCH_CHECK(v[1].numel() >= N && v[2].numel() >= N, "bacc mean / invstd smaller than N");
+      *x = reinterpret_cast<const dfa::bf16*>(v[0].data_ptr());
+      *mu = v[1].data_ptr<float>();
+      *is = v[2].data_ptr<float>();
+    };
+    if (bacc_mode == 1) inputs(bacc_in, &e.x, &e.mean, &e.invstd);
+    if (has(bacc2)) {
+      TORCH_CHECK(bacc_mode == 1, "a second BatchNorm's sums: backward only");
+      need(*bacc2, at::kDouble, "bacc2");
+      TORCH_CHECK(bacc2->numel() == bacc->numel(), "bacc2 must match bacc");
+      e.acc2 = bacc2->data_ptr<double>();
+      inputs(bacc2_in, &e.x2, &e.mean2, &e.invstd2);
+    }
+    TORCH_CHECK(dfa::igemm_bacc_ok(a, (int)mode), "bacc: this launch cannot accumulate BatchNorm sums");
+  }
+  TORCH_CHECK(!a.drop.on || (ldc == N && !a.out_f32), "folded dropout needs a dense bf16 output (ldc == N)");
+  // split-K partials for the under-filled (small-M, long-K) shapes: PyTorch's caching allocator is
+  // stream ordered and graph-capture aware, so the scratch is safe to drop right after the launch
+  torch::Tensor splitk;
+  const long long skf = dfa::igemm64_splitk_floats(a, (int)mode);
+  if (skf > 0) {
+    splitk = torch::empty({skf}, out.options().dtype(at::kFloat));
+    a.splitk_ws = splitk.data_ptr<float>();
+  }
+  check_hip(dfa::igemm_fwd(a, (int)mode, cur_stream()), "igemm_fwd");
+}
+
+void igemm_wgrad_py(torch::Tensor dy, torch::Tensor src, torch::Tensor gw, c10::optional<torch::Tensor> gb,
+                    torch::Tensor workspace, int64_t M, int64_t N, int64_t K, int64_t ldd, int64_t lda,
+                    std::vector<int64_t> geom, int64_t mode, double scale) {
+  need(dy, at::kBFloat16, "dy");
+  need(src, at::kBFloat16, "src");
+  need(gw, at::kFloat, "gw");
+  need(workspace, at::kFloat, "workspace");
+  TORCH_CHECK(gw.numel() >= N * K, "gw too small");
+  TORCH_CHECK(dy.numel() >= (M - 1) * ldd + N, "dy too small");
+  dfa::WgradArgs a{};
+  set_conv_geom(a, geom, (int)mode);
+  if (mode == 0) {
+    TORCH_CHECK(src.numel() >= (M - 1) * lda + K, "src too small");
+  } else {
+    TORCH_CHECK(M % (a.OH * a.OW) == 0, "M must be B*OH*OW");
+    TORCH_CHECK(src.numel() >= (M / (a.OH * a.OW)) * a.SH * a.SW * a.SC, "src too small");
+    TORCH_CHECK(K == (int64_t)a.KH * a.KW * a.SC, "K must be KH*KW*C");
+  }
+  a.gb = opt_ptr<float>(gb, at::kFloat, "gb", N, "gb too small");
+  a.dy = reinterpret_cast<const dfa::bf16*>(dy.data_ptr());
+  a.src = reinterpret_cast<const dfa::bf16*>(src.data_ptr());
+  a.gw = gw.data_ptr<float>();
+  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.ldd = (int)ldd; a.lda = (int)lda;
+  a.with_bias = a.gb ? 1 : 0;
+  a.scale = (float)scale;
+  check_hip(dfa::igemm_wgrad(a, (int)mode, workspace.data_ptr<float>(), (size_t)workspace.numel(), cur_stream()),
+            "igemm_wgrad");
+}
+
+void maxpool_fwd_py(torch::Tensor x, torch::Tensor y, int64_t B, int64_t H, int64_t W, int64_t C, int64_t P,
+                    double drop_p, int64_t drop_seed, c10::optional<torch::Tensor> drop_step, int64_t drop_step_add) {
+  need(x, at::kBFloat16, "x");
+  need(y, at::kBFloat16, "y");
+  TORCH_CHECK(P > 0 && H >= P && W >= P, "bad pool geometry");
+  TORCH_CHECK(x.numel() >= B * H * W * C && y.numel() >= B * (H / P) * (W / P) * C, "pool buffers too small");
+  check_hip(dfa::maxpool_fwd((const dfa::bf16*)x.data_ptr(), (dfa::bf16*)y.data_ptr(), B, H, W, C, P, cur_stream(),
+                             drop_from(drop_p, drop_seed, drop_step, drop_step_add)),
+            "maxpool_fwd");
+}
+
+void maxpool_bwd_py(torch::Tensor x, torch::Tensor dy, torch::Tensor dx, int64_t B, int64_t H, int64_t W, int64_t C,
+                    int64_t P, bool relu_fused) {
+  need(x, at::kBFloat16, "x");
+  need(dy, at::kBFloat16, "dy");
+  need(dx, at::kBFloat16, "dx");
+  TORCH_CHECK(P > 0 && H >= P && W >= P, "bad pool geometry");
+  TORCH_CHECK(x.numel() >= B * H * W * C && dx.numel() >= B * H * W * C &&
+                  dy.numel() >= B * (H / P) * (W / P) * C,
+              "pool buffers too small");
+  check_hip(dfa::maxpool_bwd((const dfa::bf16*)x.data_ptr(), (const dfa::bf16*)dy.data_ptr(),
+                             (dfa::bf16*)dx.data_ptr(), B, H, W, C, P, relu_fused ? 1 : 0, cur_stream()),
+            "maxpool_bwd");
+}
+
+void softmax_ce_py(torch::Tensor logits, torch::Tensor labels, c10::optional<torch::Tensor> dlogits,
+                   c10::optional<torch::Tensor> stats, int64_t B, int64_t C, int64_t ldl, int64_t ldg,
+                   double grad_scale) {
+  need(logits, at::kFloat, "logits");
+  need(labels, at::kInt, "labels");
+  TORCH_CHECK(logits.numel() >= (B - 1) * ldl + C && labels.numel() >= B, "softmax_ce inputs too small");
+  dfa::bf16* dl = opt_ptr<dfa::bf16>(dlogits, at::kBFloat16, "dlogits", (B - 1) * ldg + C, "dlogits too small");
+  float* sp = opt_ptr<float>(stats, at::kFloat, "stats", 2, "stats needs 2 floats");
+  check_hip(dfa::softmax_ce(logits.data_ptr<float>(), labels.data_ptr<int>(), dl, sp, B, C, ldl, ldg,
+                            (float)grad_scale, cur_stream()),
+            "softmax_ce");
+}
+
+void dropout_py(torch::Tensor x, torch::Tensor y, double p, int64_t seed, c10::optional<torch::Tensor> mask,
+                c10::optional<torch::Tensor> step) {
+  const long long* sp = opt_ptr<const long long>(step, at::kLong, "step");
+  need(x, at::kBFloat16, "x");
+  need(y, at::kBFloat16, "y");
+  TORCH_CHECK(y.numel() >= x.numel(), "dropout out too small");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0,1)");
+  const auto* mp = opt_ptr<const dfa::bf16>(mask, at::kBFloat16, "mask", x.numel(), "dropout mask too small");
+  check_hip(dfa::dropout((const dfa::bf16*)x.data_ptr(), (dfa::bf16*)y.data_ptr(), mp, x.numel(),
+                         (float)p, (unsigned long long)seed, sp, cur_stream()),
+            "dropout");
+}
+
+void gather_batch_py(torch::Tensor data, c10::optional<torch::Tensor> labels, torch::Tensor idx, torch::Tensor out,
+                     c10::optional<torch::Tensor> out_labels, int64_t B, int64_t row, double scale,
+                     c10::optional<torch::Tensor> step_inc) {
+  TORCH_CHECK(data.is_cuda() && data.is_contiguous(), "data must be a contiguous GPU tensor");
+  const bool u8 = data.scalar_type() == at::kByte;
+  TORCH_CHECK(u8 || data.scalar_type() == at::kBFloat16, "data must be uint8 or bf16");
+  need(idx, at::kLong, "idx");
+  need(out, at::kBFloat16, "out");
+  TORCH_CHECK(idx.numel() >= B && out.numel() >= B * row, "gather buffers too small");
+  TORCH_CHECK(data.dim() >= 1 && data.size(0) > 0 && data.numel() / data.size(0) == row, "data row size mismatch");
+  const int* lp = nullptr;
+  int* olp = nullptr;
+  if (has(labels)) {
+    need(*labels, at::kInt, "labels");
+    TORCH_CHECK(has(out_labels), "out_labels required with labels");
+    need(*out_labels, at::kInt, "out_labels");
+    lp = labels->data_ptr<int>();
+    olp = out_labels->data_ptr<int>();
+  }
+  check_hip(dfa::gather_batch(data.data_ptr(), u8 ? 1 : 0, lp, reinterpret_cast<const long long*>(idx.data_ptr<int64_t>()), (dfa::bf16*)out.data_ptr(),
+                              olp, B, row, (float)scale, (long long)data.size(0), cur_stream(),
+                              has(step_inc)
+                                  ? reinterpret_cast<long long*>(step_inc->data_ptr<int64_t>())
+                                  : nullptr),
+            "gather_batch");
+}
+
+// Keras merge layer (csrc/merge.hip): inputs [rows][w_i] bf16; fwd writes out, bwd writes grads[i]
+static dfa::MergeArgs merge_args(std::vector<torch::Tensor> ins, int64_t kind, int64_t cout) {
+  TORCH_CHECK(ins.size() >= 1 && ins.size() <= (size_t)dfa::kMergeMaxIn, "merge: 1..8 inputs");
+  dfa::MergeArgs a{};
+  a.n = (int)ins.size();
+  a.kind = (int)kind;
+  a.cout = (int)cout;
+  for (int i = 0; i < a.n; ++i) {
+    need(ins[i], at::kBFloat16, "merge input");
+    const int64_t w = ins[i].size(-1);
+    TORCH_CHECK(ins[i].numel() % w == 0, "merge: bad input");
+    if (i == 0) a.rows = ins[i].numel() / w;
+    TORCH_CHECK(ins[i].numel() / w == a.rows, "merge: inputs differ in rows");
+    a.w[i] = (int)w;
+    a.in[i] = (const dfa::bf16*)ins[i].data_ptr();
+  }
+  return a;
+}
+void merge_fwd_py(std::vector<torch::Tensor> ins, torch::Tensor out, int64_t kind) {
+  need(out, at::kBFloat16, "merge out");
+  dfa::MergeArgs a = merge_args(ins, kind, out.size(-1));
+  TORCH_CHECK(out.numel() == a.rows * (int64_t)a.cout, "merge: out size");
+  a.out = (dfa::bf16*)out.data_ptr();
+  check_hip(dfa::merge_fwd(a, cur_stream()), "merge_fwd");
+}
+void merge_bwd_py(std::vector<torch::Tensor> ins, torch::Tensor dy, std::vector<torch::Tensor> grads, int64_t kind) {
+  need(dy, at::kBFloat16, "merge dy");
+  dfa::MergeArgs a = merge_args(ins, kind, dy.size(-1));
+  TORCH_CHECK(grads.size() == ins.size() && dy.numel() == a.rows * (int64_t)a.cout, "merge: grads / dy size");
+  a.dy = (const dfa::bf16*)dy.data_ptr();
+  for (int i = 0; i < a.n; ++i) {
+    need(grads[i], at::kBFloat16, "merge grad");
+    TORCH_CHECK(grads[i].numel() == ins[i].numel(), "merge: grad size");
+    a.grad[i] = (dfa::bf16*)grads[i].data_ptr();
+  }
+  check_hip(dfa::merge_bwd(a, cur_stream()), "merge_bwd");
+}
+
+void add_act_py(torch::Tensor a, torch::Tensor b, torch::Tensor out, bool relu) {
+  need(a, at::kBFloat16, "a");
+  need(b, at::kBFloat16, "b");
+  need(out, at::kBFloat16, "out");
+  TORCH_CHECK(a.numel() == b.numel() && out.numel() >= a.numel(), "add_act size mismatch");
+  check_hip(dfa::add_act((const dfa::bf16*)a.data_ptr(), (const dfa::bf16*)b.data_ptr(), (dfa::bf16*)out.data_ptr(),
+                         a.numel(), relu ? 1 : 0, cur_stream()),
+            "add_act");
+}
+
+void relu_bwd_py(torch::Tensor y, torch::Tensor dy, torch::Tensor dx) {
+  need(y, at::kBFloat16, "y");
+  need(dy, at::kBFloat16, "dy");
+  need(dx, at::kBFloat16, "dx");
+  TORCH_CHECK(y.numel() == dy.numel() && dx.numel() >= y.numel(), "relu_bwd size mismatch");
+  check_hip(dfa::relu_bwd((const dfa::bf16*)y.data_ptr(), (const dfa::bf16*)dy.data_ptr(), (dfa::bf16*)dx.data_ptr(),
+                          y.numel(), cur_stream()),
+            "relu_bwd");
+}
+
+// ---- generic Keras layers (csrc/act.hip)
+void act_fwd_py(torch::Tensor x, torch::Tensor y, int64_t kind) {
+  need(x, at::kBFloat16, "act x");
+  need(y, at::kBFloat16, "act y");
+  TORCH_CHECK(y.numel() >= x.numel(), "act: output too small");
+  TORCH_CHECK(kind >= dfa::kActLinear && kind <= dfa::kActExp, "act: unknown kind");
+  check_hip(dfa::act_fwd((const dfa::bf16*)x.data_ptr(), (dfa::bf16*)y.data_ptr(), x.numel(), (int)kind,
+                         cur_stream()),
+            "act_fwd");
+}
+
+void act_bwd_py(torch::Tensor x, torch::Tensor dy, torch::Tensor dx, int64_t kind, bool in_relu) {
+  need(x, at::kBFloat16, "act x");
+  need(dy, at::kBFloat16, "act dy");
+  need(dx, at::kBFloat16, "act dx");
+  TORCH_CHECK(dy.numel() == x.numel() && dx.numel() >= x.numel(), "act_bwd: size mismatch");
+  TORCH_CHECK(kind >= dfa::kActLinear && kind <= dfa::kActExp, "act: unknown kind");
+  check_hip(dfa::act_bwd((const dfa::bf16*)x.data_ptr(), (const dfa::bf16*)dy.data_ptr(), (dfa::bf16*)dx.data_ptr(),
+                         x.numel(), (int)kind, in_relu ? 1 : 0, cur_stream()),
+            "act_bwd");
+}
+
+void sigmoid_ce_py(torch::Tensor logits, torch::Tensor labels, c10::optional<torch::Tensor> dlogits,
+                   c10::optional<torch::Tensor> stats, int64_t B, int64_t C, int64_t ldl, int64_t ldg,
+                   double grad_scale) {
+  need(logits, at::kFloat, "logits");
+  need(labels, at::kInt, "labels");
+  TORCH_CHECK(B > 0 && C > 0 && ldl >= C && ldg >= C, "sigmoid_ce: bad shape");
+  TORCH_CHECK(logits.numel() >= (B - 1) * ldl + C && labels.numel() >= B, "sigmoid_ce inputs too small");
+  dfa::bf16* dl = opt_ptr<dfa::bf16>(dlogits, at::kBFloat16, "dlogits", (B - 1) * ldg + C, "dlogits too small");
+  float* sp = opt_ptr<float>(stats, at::kFloat, "stats", 2, "stats needs 2 floats");
+  check_hip(dfa::sigmoid_ce(logits.data_ptr<float>(), labels.data_ptr<int>(), dl, sp, B, C, ldl, ldg,
+                            (float)grad_scale, cur_stream()),
+            "sigmoid_ce");
+}
+
+static dfa::Pool2DGeom pool_geom(const std::vector<int64_t>& g) {
+  TORCH_CHECK(g.size() == 12, "pool2d: geom = [B, H, W, C, OH, OW, ph, pw, sh, sw, pt, pl]");
+  dfa::Pool2DGeom p{};
+  p.B = (int)g[0]; p.H = (int)g[1]; p.W = (int)g[2]; p.C = (int)g[3]; p.OH = (int)g[4]; p.OW = (int)g[5];
+  p.ph = (int)g[6]; p.pw = (int)g[7]; p.sh = (int)g[8]; p.sw = (int)g[9]; p.pt = (int)g[10]; p.pl = (int)g[11];
+  TORCH_CHECK(p.B > 0 && p.H > 0 && p.W > 0 && p.C > 0 && p.OH > 0 && p.OW > 0 && p.ph > 0 && p.pw > 0 && p.sh > 0 &&
+                  p.sw > 0 && p.pt >= 0 && p.pl >= 0 && p.pt < p.ph && p.pl < p.pw,
+              "pool2d: bad geometry");
+  // every window starts inside the padded image
+  TORCH_CHECK((p.OH - 1) * p.sh - p.pt < p.H && (p.OW - 1) * p.sw - p.pl < p.W, "pool2d: output too large");
+  return p;
+}
+
+void pool2d_fwd_py(torch::Tensor x, torch::Tensor y, std::vector<int64_t> geom, bool avg) {
+  const dfa::Pool2DGeom g = pool_geom(geom);
+  need(x, at::kBFloat16, "pool x");
+  need(y, at::kBFloat16, "pool y");
+  TORCH_CHECK(x.numel() == (int64_t)g.B * g.H * g.W * g.C && y.numel() == (int64_t)g.B * g.OH * g.OW * g.C,
+              "pool2d: tensor sizes do not match the geometry");
+  check_hip(dfa::pool2d_fwd((const dfa::bf16*)x.data_ptr(), (dfa::bf16*)y.data_ptr(), g, avg ? 1 : 0, cur_stream()),
+            "pool2d_fwd");
+}
+
+void pool2d_bwd_py(torch::Tensor x, torch::Tensor dy, torch::Tensor dx, std::vector<int64_t> geom, bool avg,
+                   bool in_relu) {
+  const dfa::Pool2DGeom g = pool_geom(geom);
+  need(x, at::kBFloat16, "pool x");
+  need(dy, at::kBFloat16, "pool dy");
+  need(dx, at::kBFloat16, "pool dx");
+  TORCH_CHECK(x.numel() == (int64_t)g.B * g.H * g.W * g.C && dx.numel() == x.numel() &&
+                  dy.numel() == (int64_t)g.B * g.OH * g.OW * g.C,
+              "pool2d: tensor sizes do not match the geometry");
+  check_hip(dfa::pool2d_bwd((const dfa::bf16*)x.data_ptr(), (const dfa::bf16*)dy.data_ptr(), (dfa::bf16*)dx.data_ptr(),
+                            g, avg ? 1 : 0, in_relu ? 1 : 0, cur_stream()),
+            "pool2d_bwd");
+}
+
+void gap_fwd_py(torch::Tensor x, torch::Tensor y, int64_t B, int64_t HW, int64_t C) {
+  need(x, at::kBFloat16, "x");
+  need(y, at::kBFloat16, "y");
+  TORCH_CHECK(x.numel() >= B * HW * C && y.numel() >= B * C, "gap buffers too small");
+  check_hip(dfa::gap_fwd((const dfa::bf16*)x.data_ptr(), (dfa::bf16*)y.data_ptr(), B, HW, C, cur_stream()), "gap_fwd");
+}
+
+void gap_bwd_py(torch::Tensor dy, torch::Tensor dx, int64_t B, int64_t HW, int64_t C) {
+  need(dy, at::kBFloat16, "dy");
+  need(dx, at::kBFloat16, "dx");
+  TORCH_CHECK(dx.numel() >= B * HW * C && dy.numel() >= B * C, "gap buffers too small");
+  check_hip(dfa::gap_bwd((const dfa::bf16*)dy.data_ptr(), (dfa::bf16*)dx.data_ptr(), B, HW, C, cur_stream()),
+            "gap_bwd");
+}
+
+void gather_labels_py(torch::Tensor labels, torch::Tensor idx, torch::Tensor out) {
+  need(labels, at::kInt, "labels");
+  need(idx, at::kLong, "idx");
+  need(out, at::kInt, "out");
+  TORCH_CHECK(out.numel() >= idx.numel() && labels.numel() > 0, "gather_labels sizes");
+  check_hip(dfa::gather_labels(labels.data_ptr<int>(), reinterpret_cast<const long long*>(idx.data_ptr<int64_t>()),
+                               out.data_ptr<int>(), (int)idx.numel(), labels.numel(), cur_stream()),
+            "gather_labels");
+}
+
+void classifier_metrics_py(torch::Tensor z, torch::Tensor labels, int64_t kind, int64_t out_act, torch::Tensor out) {
+  need(z, at::kFloat, "metrics logits");
+  need(labels, at::kInt, "metrics labels");
+  need(out, at::kFloat, "metrics out");
+  TORCH_CHECK(z.dim() == 2 && labels.numel() == z.size(0) && out.numel() >= 2, "metrics: z [B][C], labels [B]");
+  check_hip(dfa::classifier_metrics(z.data_ptr<float>(), labels.data_ptr<int>(), (int)z.size(0), (int)z.size(1),
+                                    (int)kind, (int)out_act, out.data_ptr<float>(), cur_stream()),
+            "classifier_metrics");
+}
+
+// ---- BatchNorm (csrc/bn.hip)
+void bn_check_vec(const torch::Tensor& t, int64_t n, const char* name) {
+  need(t, at::kFloat, name);
+  TORCH_CHECK(t.numel() >= n, name, " too small");
+}
+
+void bn_check_act(const torch::Tensor& t, int64_t n, const char* name) {
+  need(t, at::kBFloat16, name);
+  TORCH_CHECK(t.numel() >= n, name, " too small");
+}
+
+void bn_check_stats_ws(const torch::Tensor& ws, const torch::Tensor& counter, int64_t M, int64_t C) {
+  TORCH_CHECK(C > 0 && C <= 1024 && M > 0, "bn: need 0 < C <= 1024 and M > 0");
+  TORCH_CHECK(C % 8 == 0 || C <= 256, "bn: C must be a multiple of 8 or <= 256");
+  bn_check_vec(ws, dfa::bn_stats_ws_floats((int)M, (int)C), "bn workspace");
+  need(counter, at::kInt, "bn counter");
+  TORCH_CHECK(counter.numel() >= dfa::bn_stats_counters((int)M, (int)C), "bn counter: need ",
+              dfa::bn_stats_counters((int)M, (int)C), " int32 tickets");
+}
+
+// the running statistics go together; returns whether they are given
+bool bn_check_run(const c10::optional<torch::Tensor>& run_mean, const c10::optional<torch::Tensor>& run_var, int64_t C,
+                  const char* alone = "run_var required with run_mean") {
+  if (!has(run_mean)) return false;
+  bn_check_vec(*run_mean, C, "run_mean");
+  TORCH_CHECK(has(run_var), alone);
+  bn_check_vec(*run_var, C, "run_var");
+  return true;
+}
+
+// launch arguments of the forward statistics (tensors already checked)
+dfa::BnStatsArgs bn_fwd_args(torch::Tensor& x, torch::Tensor& mean, torch::Tensor& invstd,
+                             c10::optional<torch::Tensor>& run_mean, c10::optional<torch::Tensor>& run_var, bool run,
+                             torch::Tensor& ws, torch::Tensor& counter, int64_t M, int64_t C, double momentum,
+                             double eps) {
+  dfa::BnStatsArgs a{};
+  a.x = (const dfa::bf16*)x.data_ptr();
+  a.mean_out = mean.data_ptr<float>();
+  a.invstd_out = invstd.data_ptr<float>();
+  a.run_mean = run ? run_mean->data_ptr<float>() : nullptr;
+  a.run_var = run ? run_var->data_ptr<float>() : nullptr;
+  a.ws = ws.data_ptr<float>();
+  a.counter = reinterpret_cast<unsigned*>(counter.data_ptr<int>());
+  a.M = (int)M; a.C = (int)C; a.momentum = (float)momentum; a.eps = (float)eps;
+  return a;
+}
+
+// checks and launch arguments of the backward statistics; dx: the fused launch's output (checked in its place)
+dfa::BnStatsArgs bn_bwd_args(torch::Tensor& x, c10::optional<torch::Tensor>& mask, torch::Tensor& dy,
+                             const torch::Tensor* dx, torch::Tensor& gamma, torch::Tensor& mean, torch::Tensor& invstd,
+                             torch::Tensor& dgamma, torch::Tensor& dbeta, torch::Tensor& coef, torch::Tensor& ws,
+                             torch::Tensor& counter, int64_t M, int64_t C, double gscale) {
+  bn_check_act(x, M * C, "x");
+  bn_check_act(dy, M * C, "dy");
+  if (dx) bn_check_act(*dx, M * C, "dx");
+  if (has(mask)) bn_check_act(*mask, M * C, "mask");
+  bn_check_vec(gamma, C, "gamma");
+  bn_check_vec(mean, C, "mean");
+  bn_check_vec(invstd, C, "invstd");
+  bn_check_vec(dgamma, C, "dgamma");
+  bn_check_vec(dbeta, C, "dbeta");
+  bn_check_vec(coef, 3 * C, "coef");
+  bn_check_stats_ws(ws, counter, M, C);
+  dfa::BnStatsArgs a{};
+  a.x = (const dfa::bf16*)x.data_ptr();
+  a.mask = cptr<dfa::bf16>(mask);
+  a.dy = (const dfa::bf16*)dy.data_ptr();
+  a.gamma = gamma.data_ptr<float>();
+  a.mean = mean.data_ptr<float>();
+  a.invstd = invstd.data_ptr<float>();
+  a.dgamma = dgamma.data_ptr<float>();
+  a.dbeta = dbeta.data_ptr<float>();
+  a.coef = coef.data_ptr<float>();
+  a.ws = ws.data_ptr<float>();
+  a.counter = reinterpret_cast<unsigned*>(counter.data_ptr<int>());
+  a.M = (int)M; a.C = (int)C; a.gscale = (float)gscale;
+  return a;
+}
+
+// the residual join of an apply: r, or bn_r(r) when the residual BatchNorm's vectors are given
+void bn_set_residual(dfa::BnApplyArgs& a, c10::optional<torch::Tensor>& r, c10::optional<torch::Tensor>& rgamma,
+                     c10::optional<torch::Tensor>& rbeta, c10::optional<torch::Tensor>& rmean,
+                     c10::optional<torch::Tensor>& rinvstd, int64_t M, int64_t C) {
+  if (!has(r)) return;
+  bn_check_act(*r, M * C, "residual");
+  a.r = (const dfa::bf16*)r->data_ptr();
+  if (!has(rgamma)) return;
+  for (auto* t : {&rgamma, &rbeta, &rmean, &rinvstd}) {
+    TORCH_CHECK(has(*t), "residual BN needs gamma, beta, mean, invstd");
+    bn_check_vec(**t, C, "residual bn vector");
+  }
+  a.rgamma = rgamma->data_ptr<float>();
+  a.rbeta = rbeta->data_ptr<float>();
+  a.rmean = rmean->data_ptr<float>();
+  a.rinvstd = rinvstd->data_ptr<float>();
+}
+
+// forward statistics: batch mean / invstd (+ running statistics) in one launch
+void bn_stats_fwd_py(torch::Tensor x, torch::Tensor mean, torch::Tensor invstd, c10::optional<torch::Tensor> run_mean,
+                     c10::optional<torch::Tensor> run_var, torch::Tensor ws, torch::Tensor counter, int64_t M,
+                     int64_t C, double momentum, double eps) {
+  bn_check_act(x, M * C, "x");
+  bn_check_vec(mean, C, "mean");
+  bn_check_vec(invstd, C, "invstd");
+  const bool run = bn_check_run(run_mean, run_var, C);
+  bn_check_stats_ws(ws, counter, M, C);
+  dfa::BnStatsArgs a = bn_fwd_args(x, mean, invstd, run_mean, run_var, run, ws, counter, M, C, momentum, eps);
+  check_hip(dfa::bn_stats(a, 0, cur_stream()), "bn_stats_fwd");
+}
+
+// backward statistics: dgamma/dbeta + dx coefficients coef[3][C]; g = dy * (mask > 0) when mask is given
+void bn_stats_bwd_py(torch::Tensor x, c10::optional<torch::Tensor> mask, torch::Tensor dy, torch::Tensor gamma,
+                     torch::Tensor mean, torch::Tensor invstd, torch::Tensor dgamma, torch::Tensor dbeta,
+                     torch::Tensor coef, torch::Tensor ws, torch::Tensor counter, int64_t M, int64_t C, double gscale) {
+  dfa::BnStatsArgs a =
+      bn_bwd_args(x, mask, dy, nullptr, gamma, mean, invstd, dgamma, dbeta, coef, ws, counter, M, C, gscale);
+  check_hip(dfa::bn_stats(a, 1, cur_stream()), "bn_stats_bwd");
+}
+
+// y = act(bn(x) [+ r | + bn_r(r)]); eval: mean/invstd are the running mean / variance
+void bn_apply_py(torch::Tensor x, torch::Tensor y, torch::Tensor gamma, torch::Tensor beta, torch::Tensor mean,
+                 torch::Tensor invstd, c10::optional<torch::Tensor> r, c10::optional<torch::Tensor> rgamma,
+                 c10::optional<torch::Tensor> rbeta, c10::optional<torch::Tensor> rmean,
+                 c10::optional<torch::Tensor> rinvstd, int64_t M, int64_t C, bool relu, bool eval, double eps) {
+  bn_check_act(x, M * C, "x");
+  bn_check_act(y, M * C, "y");
+  for (auto* t : {&gamma, &beta, &mean, &invstd}) bn_check_vec(*t, C, "bn vector");
+  dfa::BnApplyArgs a{};
+  a.x = (const dfa::bf16*)x.data_ptr();
+  a.y = (dfa::bf16*)y.data_ptr();
+  a.gamma = gamma.data_ptr<float>();
+  a.beta = beta.data_ptr<float>();
+  a.mean = mean.data_ptr<float>();
+  a.invstd = invstd.data_ptr<float>();
+  bn_set_residual(a, r, rgamma, rbeta, rmean, rinvstd, M, C);
+  a.M = (int)M; a.C = (int)C; a.relu = relu ? 1 : 0; a.eval = eval ? 1 : 0; a.eps = (float)eps;
+  check_hip(dfa::bn_apply(a, cur_stream()), "bn_apply");
+}
+
+// statistics + apply in one launch (training forward): y = act(bn(x) [+ r | + bn_r(r)]); the generation
+// word of the in-launch hand-off is counter[64]
+void bn_fwd_fused_py(torch::Tensor x, torch::Tensor y, torch::Tensor gamma, torch::Tensor beta, torch::Tensor mean,
+                     torch::Tensor invstd, c10::optional<torch::Tensor> run_mean, c10::optional<torch::Tensor> run_var,
+                     c10::optional<torch::Tensor> r, c10::optional<torch::Tensor> rgamma,
+                     c10::optional<torch::Tensor> rbeta, c10::optional<torch::Tensor> rmean,
+                     c10::optional<torch::Tensor> rinvstd, torch::Tensor ws, torch::Tensor counter, int64_t M,
+                     int64_t C, bool relu, double momentum, double eps) {
+  TORCH_CHECK(dfa::bn_fused_ok((int)C), "bn_fwd_fused: C must be a multiple of 8 (<= 1024)");
+  bn_check_act(x, M * C, "x");
+  bn_check_act(y, M * C, "y");
+  for (auto* t : {&gamma, &beta, &mean, &invstd}) bn_check_vec(*t, C, "bn vector");
+  const bool run = bn_check_run(run_mean, run_var, C);
+  bn_check_stats_ws(ws, counter, M, C);
+  TORCH_CHECK(counter.numel() >= 65, "bn_fwd_fused: counter needs 65 words (generation at 64)");
+  TORCH_CHECK(ws.numel() >= (1008 + 63) * 2 * C, "bn_fwd_fused: workspace needs (1008 + 63) x 2C floats");
+  dfa::BnStatsArgs a = bn_fwd_args(x, mean, invstd, run_mean, run_var, run, ws, counter, M, C, momentum, eps);
+  dfa::BnApplyArgs p{};
+  p.x = a.x;
+  p.y = (dfa::bf16*)y.data_ptr();
+  p.gamma = gamma.data_ptr<float>();
+  p.beta = beta.data_ptr<float>();
+  p.mean = a.mean_out;
+  p.invstd = a.invstd_out;
+  bn_set_residual(p, r, rgamma, rbeta, rmean, rinvstd, M, C);
+  p.M = (int)M; p.C = (int)C; p.relu = relu ? 1 : 0; p.eval = 0; p.eps = (float)eps;
+  check_hip(dfa::bn_fwd_fused(a, p, a.counter + 64, cur_stream()), "bn_fwd_fused");
+}
+
+// backward statistics + dx in one launch; generation word counter[64]
+void bn_bwd_fused_py(torch::Tensor x, c10::optional<torch::Tensor> mask, torch::Tensor dy, torch::Tensor dx,
+                     torch::Tensor gamma, torch::Tensor mean, torch::Tensor invstd, torch::Tensor dgamma,
+                     torch::Tensor dbeta, torch::Tensor coef, torch::Tensor ws, torch::Tensor counter, int64_t M,
+                     int64_t C, double gscale) {
+  TORCH_CHECK(dfa::bn_fused_ok((int)C), "bn_bwd_fused: C must be a multiple of 8 (<= 1024)");
+  dfa::BnStatsArgs a = bn_bwd_args(x, mask, dy, &dx, gamma, mean, invstd, dgamma, dbeta, coef, ws, counter, M, C, gscale);
+  TORCH_CHECK(counter.numel() >= 65, "bn_bwd_fused: counter needs 65 words (generation at 64)");
+  TORCH_CHECK(ws.numel() >= (1008 + 63) * 2 * C, "bn_bwd_fused: workspace needs (1008 + 63) x 2C floats");
+  check_hip(dfa::bn_bwd_fused(a, (dfa::bf16*)dx.data_ptr(), a.counter + 64, cur_stream()), "bn_bwd_fused");
+}
+
+void bn_dx_py(torch::Tensor x, c10::optional<torch::Tensor> mask, torch::Tensor dy, torch::Tensor dx,
+              torch::Tensor coef, int64_t M, int64_t C) {
+  bn_check_act(x, M * C, "x");
+  bn_check_act(dy, M * C, "dy");
+  bn_check_act(dx, M * C, "dx");
+  if (has(mask)) bn_check_act(*mask, M * C, "mask");
+  bn_check_vec(coef, 3 * C, "coef");
+  check_hip(dfa::bn_dx((const dfa::bf16*)x.data_ptr(), cptr<dfa::bf16>(mask), (const dfa::bf16*)dy.data_ptr(),
+                       (dfa::bf16*)dx.data_ptr(), coef.data_ptr<float>(), (int)M, (int)C, cur_stream()),
+            "bn_dx");
+}
+
+// BatchNorm consumers that finalise epilogue-accumulated sums (csrc/bn.hip, kernels.h BnAccFin)
+static dfa::BnAccFin bn_fin(const torch::Tensor& acc, const c10::optional<torch::Tensor>& zero, int64_t C) {
+  need(acc, at::kDouble, "bn acc");
+  TORCH_CHECK(acc.numel() % (2 * C) == 0 && acc.numel() / (2 * C) <= dfa::kBnAccMaxRep, "bn acc must be [nrep][2][C]");
+  dfa::BnAccFin f{};
+  f.acc = acc.data_ptr<double>();
+  f.nrep = (int)(acc.numel() / (2 * C));
+  if (has(zero)) {
+    need(*zero, at::kDouble, "bn acc zero");
+    TORCH_CHECK(zero->numel() == acc.numel(), "bn acc zero must match acc");
+    f.zero = zero->data_ptr<double>();
+  }
+  return f;
+}
+
+// y = act(bn(x) [+ r | + bn_r(r)]) in training mode, statistics from the producer's sums; workgroup 0
+// writes mean / invstd / running statistics (of the residual BN too) and clears `zero` / `rzero`
+void bn_apply_acc_py(torch::Tensor x, torch::Tensor y, torch::Tensor gamma, torch::Tensor beta, torch::Tensor acc,
+                     c10::optional<torch::Tensor> zero, torch::Tensor mean, torch::Tensor invstd,
+                     c10::optional<torch::Tensor> run_mean, c10::optional<torch::Tensor> run_var,
+                     c10::optional<torch::Tensor> r, std::vector<torch::Tensor> rbn, int64_t M, int64_t C, bool relu,
+                     double momentum, double eps) {
+  TORCH_CHECK(C % 8 == 0 && C <= 1024, "bn_apply_acc: C % 8 == 0, C <= 1024");
+  bn_check_act(x, M * C, "x");
+  bn_check_act(y, M * C, "y");
+  for (auto* t : {&gamma, &beta, &mean, &invstd}) bn_check_vec(*t, C, "bn vector");
+  dfa::BnApplyArgs a{};
+  a.x = (const dfa::bf16*)x.data_ptr();
+  a.y = (dfa::bf16*)y.data_ptr();
+  a.gamma = gamma.data_ptr<float>();
+  a.beta = beta.data_ptr<float>();
+  a.M = (int)M; a.C = (int)C; a.relu = relu ? 1 : 0; a.eval = 0; a.eps = (float)eps;
+  dfa::BnAccFin f = bn_fin(acc, zero, C);
+  f.mean = mean.data_ptr<float>();
+  f.invstd = invstd.data_ptr<float>();
+  if (bn_check_run(run_mean, run_var, C, "run_var with run_mean")) {
+    f.run_mean = run_mean->data_ptr<float>();
+    f.run_var = run_var->data_ptr<float>();
+  }
+  f.momentum = (float)momentum;
+  f.eps = (float)eps;
+  dfa::BnAccFin fr{};
+  const bool has_rbn = !rbn.empty();
+  if (has(r)) {
+    bn_check_act(*r, M * C, "residual");
+    a.r = (const dfa::bf16*)r->data_ptr();
+    if (has_rbn) {
+      // [gamma, beta, acc, zero (or empty), mean, invstd, run_mean, run_var]
+      TORCH_CHECK(rbn.size() == 8, "residual BN: [gamma, beta, acc, zero, mean, invstd, run_mean, run_var]");
+      for (int i : {0, 1, 4, 5, 6, 7}) bn_check_vec(rbn[i], C, "residual bn vector");
+      a.rgamma = rbn[0].data_ptr<float>();
+      a.rbeta = rbn[1].data_ptr<float>();
+      fr = bn_fin(rbn[2], rbn[3].numel() ? c10::optional<torch::Tensor>(rbn[3]) : c10::nullopt, C);
+      fr.mean = rbn[4].data_ptr<float>();
+      fr.invstd = rbn[5].data_ptr<float>();
+      fr.run_mean = rbn[6].data_ptr<float>();
+      fr.run_var = rbn[7].data_ptr<float>();
+      fr.momentum = (float)momentum;
+      fr.eps = (float)eps;
+      a.rmean = fr.mean;  // non-null marks RES 2
+      a.rinvstd = fr.invstd;
+    }
+  } else {
+    TORCH_CHECK(!has_rbn, "residual BN without a residual");
+  }
+  check_hip(dfa::bn_apply_acc(a, f, has_rbn ? &fr : nullptr, cur_stream()), "bn_apply_acc");
+}
+
+// dx = k1 g + k2 x + k3 from the producer's backward sums; workgroup 0 writes dgamma / dbeta (x gscale) and
+// coef, and clears `zero`
+void bn_dx_acc_py(torch::Tensor x, torch::Tensor g, torch::Tensor dx, torch::Tensor acc,
+                  c10::optional<torch::Tensor> zero, torch::Tensor gamma, torch::Tensor mean, torch::Tensor invstd,
+                  torch::Tensor dgamma, torch::Tensor dbeta, torch::Tensor coef, int64_t M, int64_t C, double gscale) {
+  TORCH_CHECK(C % 8 == 0 && C <= 1024, "bn_dx_acc: C % 8 == 0, C <= 1024");
+  bn_check_act(x, M * C, "x");
+  bn_check_act(g, M * C, "g");
+  bn_check_act(dx, M * C, "dx");
+  for (auto* t : {&gamma, &mean, &invstd, &dgamma, &dbeta}) bn_check_vec(*t, C, "bn vector");
+  bn_check_vec(coef, 3 * C, "coef");
+  dfa::BnAccFin f = bn_fin(acc, zero, C);
+  f.mean = mean.data_ptr<float>();
+  f.invstd = invstd.data_ptr<float>();
+  f.gamma = gamma.data_ptr<float>();
+  f.dgamma = dgamma.data_ptr<float>();
+  f.dbeta = dbeta.data_ptr<float>();
+  f.coef = coef.data_ptr<float>();
+  f.gscale = (float)gscale;
+  check_hip(dfa::bn_dx_acc((const dfa::bf16*)x.data_ptr(), (const dfa::bf16*)g.data_ptr(), (dfa::bf16*)dx.data_ptr(),
+                           f, (int)M, (int)C, cur_stream()),
+            "bn_dx_acc");
+}
+
+// GAP backward with relu' (mask) and the BatchNorm backward sums of the result (ResNet's last block)
+void gap_bwd_bn_py(torch::Tensor dy, torch::Tensor mask, torch::Tensor dx, int64_t B, int64_t HW, int64_t C,
+                   torch::Tensor acc, std::vector<torch::Tensor> bn_in) {
+  need(dy, at::kBFloat16, "dy");
+  need(mask, at::kBFloat16, "mask");
+  need(dx, at::kBFloat16, "dx");
+  TORCH_CHECK(dy.numel() >= B * C && mask.numel() >= B * HW * C && dx.numel() >= B * HW * C, "gap_bwd_bn sizes");
+  TORCH_CHECK(C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0, "gap_bwd_bn: C / 4 must divide 256");
+  need(acc, at::kDouble, "bn acc");
+  TORCH_CHECK(acc.numel() % (2 * C) == 0, "bn acc must be [nrep][2][C]");
+  TORCH_CHECK(bn_in.size() == 3, "gap_bwd_bn: [x, mean, invstd]");
+  need(bn_in[0], at::kBFloat16, "bn x");
+  TORCH_CHECK(bn_in[0].numel() >= B * HW * C, "bn x too small");
+  bn_check_vec(bn_in[1], C, "bn mean");
+  bn_check_vec(bn_in[2], C, "bn invstd");
+  dfa::BnAcc e{};
+  e.acc = acc.data_ptr<double>();
+  e.nrep = (int)(acc.numel() / (2 * C));
+  e.mode = 1;
+  e.x = (const dfa::bf16*)bn_in[0].data_ptr();
+  e.mean = bn_in[1].data_ptr<float>();
+  e.invstd = bn_in[2].data_ptr<float>();
+  check_hip(dfa::gap_bwd_bn((const dfa::bf16*)dy.data_ptr(), (const dfa::bf16*)mask.data_ptr(),
+                            (dfa::bf16*)dx.data_ptr(), (int)B, (int)HW, (int)C, e, cur_stream()),
+            "gap_bwd_bn");
+}
+
+// ---- optimizers
+// the optimizer launch's extra workgroup (csrc/optim_device.h index_stream_body): next-batch index staging
+// and / or the device run statistics
+static void fill_index_stream(dfa::IndexStream& is, const c10::optional<torch::Tensor>& idx_stream,
+                              const c10::optional<torch::Tensor>& idx_cursor,
+                              const c10::optional<torch::Tensor>& idx_dst,
+                              const c10::optional<torch::Tensor>& step_stats,
+                              const c10::optional<torch::Tensor>& run_stats) {
+  if (has(idx_stream)) {
+    TORCH_CHECK(idx_cursor.has_value() && idx_dst.has_value(), "index stream needs cursor and dst");
+    need(*idx_stream, at::kLong, "idx_stream");
+    need(*idx_cursor, at::kLong, "idx_cursor");
+    need(*idx_dst, at::kLong, "idx_dst");
+    TORCH_CHECK(idx_stream->dim() == 2 && idx_stream->size(1) == idx_dst->numel() && idx_cursor->numel() >= 1,
+                "idx_stream must be [nsteps][B] with B = idx_dst.numel()");
+    is.src = reinterpret_cast<const long long*>(idx_stream->data_ptr());
+    is.cursor = reinterpret_cast<long long*>(idx_cursor->data_ptr());
+    is.dst = reinterpret_cast<long long*>(idx_dst->data_ptr());
+    is.B = (int)idx_dst->numel();
+    is.nsteps = (int)idx_stream->size(0);
+  }
+  // device run statistics, with or without an index stream (the same extra workgroup accumulates them)
+  if (has(run_stats)) {
+    TORCH_CHECK(has(step_stats), "run_stats needs step_stats");
+    need(*run_stats, at::kFloat, "run_stats");
+    need(*step_stats, at::kFloat, "step_stats");
+    TORCH_CHECK(run_stats->numel() >= 3 && step_stats->numel() >= 2, "run_stats [3] / step_stats [2]");
+    is.run_stats = run_stats->data_ptr<float>();
+    is.step_stats = step_stats->data_ptr<float>();
+  }
+}
+
+// the descriptor table's host copy (or null), passed in the kernel arguments
+const dfa::ParamDesc* host_descs(const c10::optional<torch::Tensor>& descs_host, const torch::Tensor& descs) {
+  if (!has(descs_host)) return nullptr;
+  TORCH_CHECK(!descs_host->is_cuda() && descs_host->scalar_type() == at::kLong && descs_host->is_contiguous() &&
+                  descs_host->numel() == descs.numel(),
+              "descs_host must be the int64 CPU copy of descs");
+  return reinterpret_cast<const dfa::ParamDesc*>(descs_host->data_ptr());
+}
+
+// descs: int64 GPU tensor [ndesc][6] laid out as ParamDesc (see optim.hip)
+void sgd_multi_py(torch::Tensor descs, int64_t ndesc, int64_t total_blocks, torch::Tensor master, torch::Tensor grad,
+                  c10::optional<torch::Tensor> mom, torch::Tensor wbf, torch::Tensor hyper, bool apply_update,
+                  c10::optional<torch::Tensor> idx_stream, c10::optional<torch::Tensor> idx_cursor,
+                  c10::optional<torch::Tensor> idx_dst, c10::optional<torch::Tensor> descs_host,
+                  c10::optional<torch::Tensor> lenet_frag, int64_t frag_w1, int64_t frag_w2,
+                  c10::optional<torch::Tensor> lenet_snap, c10::optional<torch::Tensor> step_stats,
+                  c10::optional<torch::Tensor> run_stats, uintptr_t gate, uintptr_t mirror) {
+  TORCH_CHECK(descs.is_cuda() && descs.scalar_type() == at::kLong && descs.is_contiguous(), "descs must be int64 GPU");
+  const dfa::ParamDesc* hd = host_descs(descs_host, descs);
+  static_assert(sizeof(dfa::ParamDesc) == 48, "ParamDesc layout");
+  TORCH_CHECK(descs.numel() * 8 >= ndesc * (int64_t)sizeof(dfa::ParamDesc), "descs too small");
+  need(master, at::kFloat, "master");
+  need(grad, at::kFloat, "grad");
+  need(wbf, at::kBFloat16, "wbf");
+  need(hyper, at::kFloat, "hyper");
+  TORCH_CHECK(hyper.numel() >= 5, "hyper needs [lr, momentum, wd, grad_scale, nesterov]");
+  TORCH_CHECK(grad.numel() >= master.numel(), "grad smaller than master");
+  float* mp = opt_ptr<float>(mom, at::kFloat, "mom", master.numel(), "momentum buffer too small");
+  dfa::IndexStream is{};
+  fill_index_stream(is, idx_stream, idx_cursor, idx_dst, step_stats, run_stats);
+  if (has(lenet_frag)) {
+    TORCH_CHECK(lenet_frag->is_cuda() && lenet_frag->is_contiguous() &&
+                    (size_t)lenet_frag->nbytes() >= dfa::lenet_frag_bytes(),
+                "lenet_frag: fragment buffer too small");
+    TORCH_CHECK(frag_w1 >= 0 && frag_w1 + 150 <= master.numel() && frag_w2 >= 0 && frag_w2 + 2400 <= master.numel(),
+                "lenet_frag: conv kernel offsets out of range");
+    TORCH_CHECK(!apply_update || has(lenet_snap), "lenet_frag: an update needs the pre-update snapshot (lenet_snap)");
+    is.snap = opt_ptr<float>(lenet_snap, at::kFloat, "lenet_snap", 2 * 2550, "lenet_snap must hold 2 x 2550 floats");
+    is.frag = lenet_frag->data_ptr();
+    is.frag_w1 = frag_w1;
+    is.frag_w2 = frag_w2;
+  }
+  // async PS exclusive writer (PSComm.excl_gate / excl_mirror): the update gated on the admission word, the
+  // new weights mirrored into the rank's shard
+  TORCH_CHECK((gate == 0) == (mirror == 0), "sgd_multi: gate and mirror go together");
+  TORCH_CHECK(gate == 0 || (apply_update && !is.frag), "sgd_multi: a gated update without LeNet fragments");
+  is.gate = reinterpret_cast<const unsigned*>(gate);
+  is.mirror = reinterpret_cast<float*>(mirror);
+  const bool any = is.src || is.frag || is.run_stats || is.gate;
+  check_hip(dfa::sgd_multi(reinterpret_cast<const dfa::ParamDesc*>(descs.data_ptr()), (int)ndesc, (int)total_blocks,
+                           master.data_ptr<float>(), grad.data_ptr<float>(), mp, (dfa::bf16*)wbf.data_ptr(),
+                           hyper.data_ptr<float>(), apply_update ? 1 : 0, cur_stream(), any ? &is : nullptr, hd),
+            "sgd_multi");
+}
+
+// Adam / AdamW twin of sgd_multi (csrc/adam.hip).  The LeNet-5 fragment rebuild is SGD-only (no argument
+// for it here) and so are the async parameter server's gate / mirror, which are rejected.
+void adam_multi_py(torch::Tensor descs, int64_t ndesc, int64_t total_blocks, torch::Tensor master, torch::Tensor grad,
+                   torch::Tensor m, torch::Tensor v, torch::Tensor wbf, torch::Tensor hyper, torch::Tensor state,
+                   torch::Tensor tickets, c10::optional<torch::Tensor> idx_stream, c10::optional<torch::Tensor> idx_cursor,
+                   c10::optional<torch::Tensor> idx_dst, c10::optional<torch::Tensor> descs_host,
+                   c10::optional<torch::Tensor> step_stats, c10::optional<torch::Tensor> run_stats,
+                   uintptr_t gate, uintptr_t mirror) {
+  TORCH_CHECK(gate == 0 && mirror == 0,
+              "adam_multi: the async parameter server's exclusive-writer gate / mirror take SGD only");
+  TORCH_CHECK(descs.is_cuda() && descs.scalar_type() == at::kLong && descs.is_contiguous(), "descs must be int64 GPU");
+  const dfa::ParamDesc* hd = host_descs(descs_host, descs);
+  TORCH_CHECK(ndesc > 0 && total_blocks > 0, "adam_multi: nothing to update");
+  TORCH_CHECK(descs.numel() * 8 >= ndesc * (int64_t)sizeof(dfa::ParamDesc), "descs too small");
+  need(master, at::kFloat, "master");
+  need(grad, at::kFloat, "grad");
+  need(m, at::kFloat, "m");
+  need(v, at::kFloat, "v");
+  need(wbf, at::kBFloat16, "wbf");
+  need(hyper, at::kFloat, "hyper");
+  need(state, at::kLong, "state");
+  TORCH_CHECK(hyper.numel() >= dfa::kAdamHyper,
+              "hyper needs [lr, beta1, beta2, eps, wd, grad_scale, decoupled, 1-beta1, 1-beta2]");
+  TORCH_CHECK(state.numel() >= dfa::kAdamState, "state needs [c1, c2, t, ticket]");
+  need(tickets, at::kLong, "tickets");
+  TORCH_CHECK(tickets.numel() >= dfa::kAdamTicketGroups * dfa::kAdamTicketStride, "ticket buffer too small");
+  TORCH_CHECK(grad.numel() >= master.numel() && m.numel() >= master.numel() && v.numel() >= master.numel(),
+              "grad / m / v smaller than master");
+  dfa::IndexStream is{};
+  fill_index_stream(is, idx_stream, idx_cursor, idx_dst, step_stats, run_stats);
+  const bool any = is.src || is.run_stats;
+  check_hip(dfa::adam_multi(reinterpret_cast<const dfa::ParamDesc*>(descs.data_ptr()), (int)ndesc, (int)total_blocks,
+                            master.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(),
+                            v.data_ptr<float>(), (dfa::bf16*)wbf.data_ptr(), hyper.data_ptr<float>(),
+                            reinterpret_cast<unsigned long long*>(state.data_ptr()),
+                            reinterpret_cast<unsigned long long*>(tickets.data_ptr()), cur_stream(),
+                            any ? &is : nullptr, hd),
+            "adam_multi");
+}
+
+void sum_buffers_py(torch::Tensor ptrs, int64_t nin, torch::Tensor out, double scale) {
+  TORCH_CHECK(ptrs.is_cuda() && ptrs.scalar_type() == at::kLong && ptrs.numel() >= nin, "ptrs must be int64 GPU");
+  need(out, at::kFloat, "out");
+  check_hip(dfa::sum_buffers(reinterpret_cast<const float* const*>(ptrs.data_ptr()), (int)nin, out.data_ptr<float>(),
+                             out.numel(), (float)scale, cur_stream()),
+            "sum_buffers");
+}
+
+void axpby_py(torch::Tensor out, torch::Tensor a, torch::Tensor b, double alpha, double beta) {
+  need(out, at::kFloat, "out");
+  need(a, at::kFloat, "a");
+  need(b, at::kFloat, "b");
+  TORCH_CHECK(a.numel() == out.numel() && b.numel() == out.numel(), "axpby size mismatch");
+  check_hip(dfa::axpby(out.data_ptr<float>(), a.data_ptr<float>(), b.data_ptr<float>(), (float)alpha, (float)beta,
+                       out.numel(), cur_stream()),
+            "axpby");
+}
+
+}  // namespace
+
+void bind_layers(py::module_& m) {
+  m.def("igemm_fwd", &igemm_fwd_py, "implicit-GEMM MFMA (dense/conv fwd, dgrad)", py::arg("src"), py::arg("w"),
+        py::arg("bias"), py::arg("mask"), py::arg("out"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("Kpad"),
+        py::arg("lda"), py::arg("ldc"), py::arg("geom"), py::arg("mode"), py::arg("relu"), py::arg("alpha"),
+        py::arg("res") = py::none(), py::arg("resmask") = py::none(), py::arg("drop_p") = 0.0,
+        py::arg("drop_seed") = 0, py::arg("drop_step") = py::none(), py::arg("pool_code") = py::none(),
+        py::arg("drop_step_add") = 0, py::arg("bn_ws") = py::none(), py::arg("bn_ticket") = py::none(),
+        py::arg("bn_mode") = 0, py::arg("bn_vecs") = std::vector<torch::Tensor>{}, py::arg("bn_x") = py::none(),
+        py::arg("bn_momentum") = 0.1, py::arg("bn_eps") = 1e-5, py::arg("bn_gscale") = 1.0,
+        py::arg("bacc") = py::none(), py::arg("bacc_mode") = 0, py::arg("bacc_in") = std::vector<torch::Tensor>{},
+        py::arg("bacc2") = py::none(), py::arg("bacc2_in") = std::vector<torch::Tensor>{});
+  m.def("igemm_bacc_supported", [](int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector<int64_t> geom,
+                                   int64_t mode, int64_t bacc_mode, bool two, bool has_res, bool has_mask) {
+    // the dispatch decision of igemm_fwd for a launch with these shapes (16-byte aligned operands)
+    dfa::IGemmArgs a{};
+    set_conv_geom(a, geom, (int)mode);
+    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.Kpad = (int)Kpad; a.ldc = (int)N; a.lda = 0;
+    static dfa::bf16 dummy[8] __attribute__((aligned(16)));
+    static double dacc[2] __attribute__((aligned(16)));
+    static float dvec[2] __attribute__((aligned(16)));
+    a.src = dummy; a.w = dummy; a.out = dummy;
+    if (has_res) a.res = dummy;
+    if (has_mask) a.mask = dummy;
+    a.bacc.acc = dacc;
+    a.bacc.nrep = 1;
+    a.bacc.mode = (int)bacc_mode;
+    if (bacc_mode == 1) a.bacc.x = dummy, a.bacc.mean = dvec, a.bacc.invstd = dvec;
+    if (two) a.bacc.acc2 = dacc, a.bacc.x2 = dummy, a.bacc.mean2 = dvec, a.bacc.invstd2 = dvec;
+    return dfa::igemm_bacc_ok(a, (int)mode);
+  });
+  m.def("igemm64_bn_tiles", [](int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector<int64_t> geom, int64_t mode) {
+    dfa::IGemmArgs a{};
+    set_conv_geom(a, geom, (int)mode);
+    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.Kpad = (int)Kpad; a.ldc = (int)N;
+    static dfa::bf16 layout_dummy[8] __attribute__((aligned(16)));
+    a.src = layout_dummy; a.w = layout_dummy; a.out = layout_dummy;
+    int ntn = 0;
+    const int ntm = dfa::igemm64_bn_layout(a, (int)mode, &ntn);
+    return std::make_tuple((int64_t)ntm, (int64_t)ntn);
+  });
+  m.def("igemm64_pool_supported", [](int64_t H, int64_t W, int64_t C, int64_t OH, int64_t OW, int64_t K, int64_t N) {
+    dfa::IGemmArgs a{};
+    a.SH = (int)H; a.SW = (int)W; a.SC = (int)C; a.OH = (int)OH; a.OW = (int)OW; a.M = 4; a.N = (int)N; a.ldc = (int)N;
+    a.K = (int)K; a.Kpad = (int)((K + 31) / 32 * 32);
+    static dfa::bf16 layout_dummy[8] __attribute__((aligned(16)));
+    static uint8_t codep[4] __attribute__((aligned(4)));
+    a.src = layout_dummy; a.w = layout_dummy; a.out = layout_dummy; a.pool_code = codep;
+    return dfa::igemm64_pool_supported(a) && N % 8 == 0;
+  });
+  m.def("unpool2", [](torch::Tensor dyp, torch::Tensor code, torch::Tensor dy) {
+    need(dyp, at::kBFloat16, "unpool dyp");
+    need(dy, at::kBFloat16, "unpool dy");
+    TORCH_CHECK(dy.dim() == 4 && code.is_cuda() && code.is_contiguous() && code.scalar_type() == at::kByte,
+                "unpool2: dy [B][OH][OW][N], code uint8");
+    const int64_t B = dy.size(0), OH = dy.size(1), OW = dy.size(2), N = dy.size(3);
+    TORCH_CHECK(dyp.numel() == B * (OH / 2) * (OW / 2) * N && code.numel() == dyp.numel(), "unpool2: sizes");
+    check_hip(dfa::unpool2(reinterpret_cast<const dfa::bf16*>(dyp.data_ptr()), code.data_ptr<uint8_t>(),
+                           reinterpret_cast<dfa::bf16*>(dy.data_ptr()), (int)B, (int)OH, (int)OW, (int)N,
+                           cur_stream()),
+              "unpool2");
+  });
+  m.def("igemm_wgrad", &igemm_wgrad_py, "implicit-GEMM MFMA weight gradient (split-m slabs + reduce)");
+  m.def("maxpool_fwd", &maxpool_fwd_py, py::arg("x"), py::arg("y"), py::arg("B"), py::arg("H"), py::arg("W"),
+        py::arg("C"), py::arg("P"), py::arg("drop_p") = 0.0, py::arg("drop_seed") = 0,
+        py::arg("drop_step") = py::none(), py::arg("drop_step_add") = 0);
+  m.def("maxpool_bwd", &maxpool_bwd_py);
+  m.def("softmax_ce", &softmax_ce_py);
+  m.def("dropout", &dropout_py);
+  m.def("gather_batch", &gather_batch_py, py::arg("data"), py::arg("labels"), py::arg("idx"), py::arg("out"),
+        py::arg("out_labels"), py::arg("B"), py::arg("row"), py::arg("scale"), py::arg("step_inc") = py::none());
+  m.def("add_act", &add_act_py);
+  m.def("merge_fwd", &merge_fwd_py, "Keras merge layer forward (Add / Subtract / Multiply / Average / Maximum / "
+        "Minimum / Concatenate)");
+  m.def("merge_bwd", &merge_bwd_py, "Keras merge layer: gradient of every input");
+  m.def("relu_bwd", &relu_bwd_py);
+  m.def("gap_fwd", &gap_fwd_py);
+  m.def("gap_bwd", &gap_bwd_py);
+  m.def("classifier_metrics", &classifier_metrics_py,
+        "[loss sum, correct] of a classifier batch (one launch); out_act 0 logits, 1 softmax, 2 sigmoid output");
+  m.def("act_fwd", &act_fwd_py, "standalone activation y = act(x) (csrc/act.hip)");
+  m.def("act_bwd", &act_bwd_py, "dx = dy * act'(x) [* relu'(x)]");
+  m.def("sigmoid_ce", &sigmoid_ce_py, "sigmoid cross-entropy on logits vs one-hot labels (+ dlogits)");
+  m.def("pool2d_fwd", &pool2d_fwd_py, "general 2-D max / average pooling, any window / stride / padding");
+  m.def("pool2d_bwd", &pool2d_bwd_py, "backward of pool2d_fwd (input-centric, no atomics)");
+  m.def("gather_labels", &gather_labels_py);
+  m.def("bn_finalize_partials", [](torch::Tensor part, int64_t ntm, int64_t C, int64_t M, torch::Tensor mean,
+                                   torch::Tensor invstd, c10::optional<torch::Tensor> run_mean,
+                                   c10::optional<torch::Tensor> run_var, double momentum, double eps) {
+    need(part, at::kFloat, "bn part");
+    need(mean, at::kFloat, "bn mean");
+    need(invstd, at::kFloat, "bn invstd");
+    TORCH_CHECK(part.numel() >= ntm * 2 * C && mean.numel() >= C && invstd.numel() >= C, "bn_finalize: sizes");
+    check_hip(dfa::bn_finalize_partials(part.data_ptr<float>(), (int)ntm, (int)C, M, mean.data_ptr<float>(),
+                                        invstd.data_ptr<float>(), const_cast<float*>(cptr<float>(run_mean)),
+                                        const_cast<float*>(cptr<float>(run_var)),
+                                        (float)momentum, (float)eps, cur_stream()),
+              "bn_finalize_partials");
+  });
+  m.def("bn_stats_fwd", &bn_stats_fwd_py, "BN forward statistics (partials + last-workgroup finalize, one launch)");
+  m.def("bn_stats_bwd", &bn_stats_bwd_py, "BN backward statistics: dgamma, dbeta and dx coefficients");
+  m.def("bn_apply", &bn_apply_py, "BN normalize (+ residual join, + ReLU)");
+  m.def("bn_dx", &bn_dx_py, "BN input gradient dx = k1*g + k2*x + k3");
+  m.def("bn_apply_acc", &bn_apply_acc_py, "BN training apply, statistics finalised from epilogue-accumulated sums");
+  m.def("bn_dx_acc", &bn_dx_acc_py, "BN input gradient, coefficients finalised from epilogue-accumulated sums");
+  m.def("gap_bwd_bn", &gap_bwd_bn_py, "GAP backward with relu' and BatchNorm backward sums");
+  m.def("bn_fwd_fused", &bn_fwd_fused_py, "BN training forward: statistics + apply in one launch");
+  m.def("bn_bwd_fused", &bn_bwd_fused_py, "BN backward: statistics + dx in one launch");
+  m.def("bn_stats_grid", &dfa::bn_stats_grid, "partial-slab count of a BN statistics launch");
+  m.def("sgd_multi", &sgd_multi_py, py::arg("descs"), py::arg("ndesc"), py::arg("total_blocks"), py::arg("master"),
+        py::arg("grad"), py::arg("mom"), py::arg("wbf"), py::arg("hyper"), py::arg("apply_update"),
+        py::arg("idx_stream") = py::none(), py::arg("idx_cursor") = py::none(), py::arg("idx_dst") = py::none(),
+        py::arg("descs_host") = py::none(), py::arg("lenet_frag") = py::none(), py::arg("frag_w1") = 0,
+        py::arg("frag_w2") = 0, py::arg("lenet_snap") = py::none(), py::arg("step_stats") = py::none(),
+        py::arg("run_stats") = py::none(), py::arg("gate") = 0, py::arg("mirror") = 0);
+  m.def("adam_multi", &adam_multi_py, py::arg("descs"), py::arg("ndesc"), py::arg("total_blocks"), py::arg("master"),
+        py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("wbf"), py::arg("hyper"), py::arg("state"),
+        py::arg("tickets"), py::arg("idx_stream") = py::none(), py::arg("idx_cursor") = py::none(), py::arg("idx_dst") = py::none(),
+        py::arg("descs_host") = py::none(), py::arg("step_stats") = py::none(), py::arg("run_stats") = py::none(),
+        py::arg("gate") = 0, py::arg("mirror") = 0,
+        "Fused multi-tensor Adam / AdamW: master, m, v, bf16 compute copies and the step state in one launch");
+  m.attr("ADAM_TICKET_WORDS") = dfa::kAdamTicketGroups * dfa::kAdamTicketStride;
+  m.def("sum_buffers", &sum_buffers_py);
+  m.def("graph_upload", [](uintptr_t exec) {
+    // stage an instantiated graph's kernel arguments / launch packets on the device now, outside any
+    // timed region, instead of on its first hipGraphLaunch
+    check_hip(hipGraphUpload(reinterpret_cast<hipGraphExec_t>(exec), cur_stream()), "hipGraphUpload");
+  }, "hipGraphUpload of a captured graph (torch.cuda.CUDAGraph.raw_cuda_graph_exec()) on the current stream");
+  m.def("axpby", &axpby_py);
+}
+
+}  // namespace dfa_py

@@ -48,6 +48,7 @@ constexpr unsigned kFedAdmit = 1, kFedStale = 2, kFedFull = 3, kFedFailed = 4;
 constexpr int kFedDecision = 0, kFedSlot = 1, kFedEpoch = 2, kFedUpDone = 3, kFedApDone = 4, kFedApplier = 5,
               kFedTorn = 6, kFedFullV = 7, kFedFullT = 8, kFedApEp = 10, kFedApDec = 11, kFedRecov = 12,
               kFedPulled = 64;
+static_assert(kFedRecov < kFedPulled && kFedPulled + kPSMaxGrid <= kFedScratchWords, "PSLocal::fed_scratch (ps_layout.h)");
 // error bits (stats[7]): 1 pull timed out, 2 admission CAS timed out, 4 decision wait timed out, 8 torn upload
 // landed as a bad slot, 16 a version stayed full past twice the timeout even after a recovery
 constexpr unsigned kFedErrTorn = 8u, kFedErrStuck = 16u;

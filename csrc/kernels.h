@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "ps_layout.h"
+
 namespace dfa {
 typedef __bf16 bf16;
 }
@@ -356,7 +358,6 @@ hipError_t slab_reduce_multi(SlabSegs segs, hipStream_t st);
 // One-shot xGMI all-reduce (csrc/allreduce_p2p.hip).  Each rank's IPC buffer: flags
 // [max_blocks][kP2PMaxRanks] u32 (flag_bytes, 4 KB aligned) followed by two staging halves of
 // half_floats fp32 each.  Workgroup b always owns elements [b*kP2PChunk, (b+1)*kP2PChunk).
-constexpr int kP2PMaxRanks = 8;
 constexpr int kP2PChunk = 2048;
 struct P2PArgs {
   char* bases[kP2PMaxRanks];  // bases[r] = rank r's buffer mapped into this process (bases[rank] local)
@@ -391,7 +392,8 @@ hipError_t ll_selftest(const LLComm& c, const float* in, float* out, int nslots,
 
 
 
-// Device-resident async parameter server (csrc/async_ps.hip, protocol csrc/ps_device.h).  The fp32 master is
+// Device-resident async parameter server (csrc/async_ps.hip, protocol csrc/ps_device.h; the layout of the
+// control and local buffers behind these pointers: csrc/ps_layout.h).  The fp32 master is
 // SHARDED by contiguous parameter range: element i lives in shard i >> shard_shift, in that rank's HBM
 // (IPC-mapped into every rank), so the appliers of different ranks update different shards -- and, inside a
 // shard, different elements -- in parallel with lock-free per-element compare-and-swap adds (or plain
@@ -445,7 +447,6 @@ struct PSArgs {
   int claim_given;
   long long claim_bid;
 };
-constexpr int kPSMaxGrid = 64;
 
 // Device FedSGD count barrier on the parameter server's shards (csrc/fedsgd_ps.hip): the reference
 // FederatedServer's version gate and K-upload barrier, K < W allowed (late uploads are dropped).
@@ -475,9 +476,6 @@ struct FedArgs {
 hipError_t fed_pull(const FedArgs& a, hipStream_t st);
 hipError_t fed_upload(const FedArgs& a, hipStream_t st);
 hipError_t fed_apply(const FedArgs& a, hipStream_t st);
-constexpr int kPSVMinWord = 4;  // scratch word of the refresh minimum (ps_device.h kPSVMin)
-constexpr int kPSDecisionWord = 3;  // scratch word of the tagged admission decision (ps_device.h kPSDecision)
-constexpr long long kPSMaxBatches = 1 << 20;  // capacity of the shared completion arrays
 hipError_t ps_fetch_pull(const PSArgs& a, hipStream_t st);
 // apply-path calibration: mode 0 per-element CAS adds of 0, mode 1 owner-applies stores / loads (async_ps.hip)
 hipError_t ps_calibrate(const PSArgs& a, int mode, hipStream_t st);
@@ -512,7 +510,7 @@ struct LeNetArgs {
   int prep;                   // 1: launch the fragment prep kernel first (0: the optimizer rebuilt them)
   const void* frag;           // [37][64] x 8 bf16 conv weight fragments of this step (written by the prep launch)
   const unsigned char* ftab;  // [98][2][16] conv2 dgrad gather table (lenet_tables)
-  const unsigned short* pxtab;  // [800] conv2 output row -> pool1 pixel (lenet_tables)
+  const unsigned short* pxtab;  // [832] conv2 output row -> pool1 pixel (lenet_tables)
   unsigned long long* stamps; // diagnostic phase clocks [grid][16] (lenet_set_stamps), or null
   int B, ldt;
   float grad_scale;
@@ -682,6 +680,7 @@ struct KHeadWgradArgs {
 };
 hipError_t khead_wgrad(KHeadWgradArgs a, hipStream_t st);
 size_t khead_ws_floats(int B, int K);
+size_t khead_err_offset(int B);  // float offset of the sticky error word in that workspace
 size_t khead_lds(int K);
 bool khead_supported(int K, int C);
 hipError_t khead_train(KHeadArgs a, hipStream_t st);

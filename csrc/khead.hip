@@ -694,10 +694,15 @@ hipError_t khead_wgrad(KHeadWgradArgs a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// workspace floats: split-K slabs, dz1, then the words at KHeadArgs::sync: 2 per row tile (tickets, flags), the
+// launch tag (tagp = sync + 2 * ntiles), the done counter (tagp + 1) and the error word (tagp + 2)
+size_t khead_err_offset(int B) {
+  const size_t nt = (size_t)cdiv(B, KR);
+  return nt * KCH * SLAB + nt * KR * N1 / 2 + 2 * nt + 2;
+}
 size_t khead_ws_floats(int B, int K) {
   (void)K;
-  const size_t nt = (size_t)cdiv(B, KR);
-  return nt * KCH * SLAB + nt * KR * N1 / 2 + 2 * nt + 3;  // ... tickets, flags, tag, done counter, error word
+  return khead_err_offset(B) + 1;
 }
 
 size_t khead_lds(int K) {

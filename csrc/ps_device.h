@@ -38,6 +38,7 @@ constexpr int kPSSeq = 5, kPSPullEp = 6, kPSDrain = 7, kPSDrainP = 8, kPSDrainN 
 // exclusive-writer step (async_ps.hip ps_excl_step): its claim workgroup's step counter, and the admission
 // workgroup's "microbatch id read" flag (= counter + 1) the claim waits for before overwriting the id
 constexpr int kPSStepCtr = 24, kPSBidRead = 25;  // kPSBidRead: "id read and completed" flag
+static_assert(kPSBidRead < kPSSlots && kPSSlots + kPSMaxGrid <= kPSScratchWords, "PSLocal::scratch (ps_layout.h)");
 constexpr unsigned kPSNoVer = 0xffffffffu;
 // the decision word is (launch epoch << 3) | code: compare epochs modulo 2^29
 __device__ __forceinline__ bool ps_epoch_eq(unsigned word, unsigned ep) { return (word >> 3) == (ep & 0x1fffffffu); }
@@ -76,6 +77,7 @@ __device__ __forceinline__ unsigned* ps_inbox_flags(const PSArgs& a, int k) {
 // owner-applies drain decisions of the fused LeNet-5 step (csrc/lenet_fused.hip mode 4): one u64 per shard in
 // the local scratch (u32 words 32..47), (launch epoch & 0xffffff) << 40 | count << 32 | first sequence number
 constexpr int kPSOwnerDrainWords = 32;
+static_assert(kPSOwnerDrainWords + 2 * kP2PMaxRanks <= kPSSlots, "drain words overlap the per-workgroup words");
 __device__ __forceinline__ unsigned long long* ps_owner_drain_words(const PSArgs& a) {
   return reinterpret_cast<unsigned long long*>(a.scratch + kPSOwnerDrainWords);
 }
