@@ -56,27 +56,16 @@ void igemm_fwd_py(torch::Tensor src, torch::Tensor w, c10::optional<torch::Tenso
   a.out_f32 = out.scalar_type() == at::kFloat ? 1 : 0;
   a.alpha = (float)alpha;
   a.drop = drop_from(drop_p, drop_seed, drop_step, drop_step_add);
-  if (pooled) {
-    a.pool_code = pool_code->data_ptr<uint8_t>();
-    TORCH_CHECK(dfa::igemm64_pool_supported(a), "pooled conv: unsupported geometry / alignment");
-  }
+  if (pooled) a.pool_code = pool_code->data_ptr<uint8_t>();
   if (has(bn_ws)) {
     // BatchNorm statistics finalised inside this launch (kernels.h BnEpi)
     need(*bn_ws, at::kFloat, "bn_ws");
     TORCH_CHECK(has(bn_ticket), "bn_ws needs bn_ticket");
     need(*bn_ticket, at::kInt, "bn_ticket");
-    int ntn = 0;
-    const int ntm = dfa::igemm64_bn_layout(a, (int)mode, &ntn);
-    TORCH_CHECK(ntm > 0, "bn: this conv launch cannot finalise BatchNorm statistics");
-    const int ngrp = (ntm + 15) / 16;
-    TORCH_CHECK(bn_ws->numel() >= (int64_t)(ntm + ngrp) * 2 * N, "bn_ws too small");
-    TORCH_CHECK(bn_ticket->numel() >= (int64_t)ntn * (1 + ngrp), "bn_ticket too small");
     TORCH_CHECK(out.scalar_type() == at::kBFloat16, "bn: bf16 output");
     dfa::BnEpi& e = a.bn;
     e.part = bn_ws->data_ptr<float>();
     e.ticket = reinterpret_cast<unsigned*>(bn_ticket->data_ptr<int>());
-    e.ntm = ntm;
-    e.ngrp = ngrp;
     e.mode = (int)bn_mode;
     e.momentum = (float)bn_momentum;
     e.eps = (float)bn_eps;
@@ -135,18 +124,61 @@ void igemm_fwd_py(torch::Tensor src, torch::Tensor w, c10::optional<torch::Tenso
       e.acc2 = bacc2->data_ptr<double>();
       inputs(bacc2_in, &e.x2, &e.mean2, &e.invstd2);
     }
-    TORCH_CHECK(dfa::igemm_bacc_ok(a, (int)mode), "bacc: this launch cannot accumulate BatchNorm sums");
   }
   TORCH_CHECK(!a.drop.on || (ldc == N && !a.out_f32), "folded dropout needs a dense bf16 output (ldc == N)");
+  // the one plan of this launch: what it may carry, the BatchNorm tiles, the scratch
+  const dfa::ConvPlan plan = dfa::conv_plan(a, (int)mode);
+  TORCH_CHECK(!pooled || plan.pool, "pooled conv: unsupported geometry / alignment");
+  if (has(bn_ws)) {
+    TORCH_CHECK(plan.bn_ntm > 0, "bn: this conv launch cannot finalise BatchNorm statistics");
+    a.bn.ntm = plan.bn_ntm;
+    a.bn.ngrp = (plan.bn_ntm + 15) / 16;
+    TORCH_CHECK(bn_ws->numel() >= (int64_t)(a.bn.ntm + a.bn.ngrp) * 2 * N, "bn_ws too small");
+    TORCH_CHECK(bn_ticket->numel() >= (int64_t)plan.bn_ntn * (1 + a.bn.ngrp), "bn_ticket too small");
+  }
+  TORCH_CHECK(!has(bacc) || plan.bacc_ok, "bacc: this launch cannot accumulate BatchNorm sums");
   // split-K partials for the under-filled (small-M, long-K) shapes: PyTorch's caching allocator is
   // stream ordered and graph-capture aware, so the scratch is safe to drop right after the launch
   torch::Tensor splitk;
-  const long long skf = dfa::igemm64_splitk_floats(a, (int)mode);
-  if (skf > 0) {
-    splitk = torch::empty({skf}, out.options().dtype(at::kFloat));
+  if (plan.splitk_floats > 0) {
+    splitk = torch::empty({plan.splitk_floats}, out.options().dtype(at::kFloat));
     a.splitk_ws = splitk.data_ptr<float>();
   }
-  check_hip(dfa::igemm_fwd(a, (int)mode, cur_stream()), "igemm_fwd");
+  check_hip(dfa::igemm_fwd(a, plan, (int)mode, cur_stream()), "igemm_fwd");
+}
+
+// The plan of a launch with these shapes before any tensor exists: 16-byte aligned dummy operands stand in
+// for the real ones (torch allocations are at least that aligned).  bacc_mode >= 0: with BatchNorm sums.
+py::dict conv_plan_py(int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector<int64_t> geom, int64_t mode,
+                      int64_t bacc_mode, bool two, bool has_res, bool has_mask, bool pooled, int64_t lda, bool drop,
+                      bool bn) {
+  static dfa::bf16 dummy[8] __attribute__((aligned(16)));
+  static double dacc[2] __attribute__((aligned(16)));
+  static float dvec[2] __attribute__((aligned(16)));
+  dfa::IGemmArgs a{};
+  set_conv_geom(a, geom, (int)mode);
+  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.Kpad = (int)Kpad; a.ldc = (int)N; a.lda = (int)lda;
+  a.src = dummy; a.w = dummy; a.out = dummy;
+  if (has_res) a.res = dummy;
+  if (has_mask) a.mask = dummy;
+  if (pooled) a.pool_code = reinterpret_cast<uint8_t*>(dummy);
+  if (drop) a.drop.on = 1;
+  if (bn) a.bn.part = dvec;
+  if (bacc_mode >= 0) {
+    a.bacc.acc = dacc;
+    a.bacc.nrep = 1;
+    a.bacc.mode = (int)bacc_mode;
+    if (bacc_mode == 1) a.bacc.x = dummy, a.bacc.mean = dvec, a.bacc.invstd = dvec;
+    if (two) a.bacc.acc2 = dacc, a.bacc.x2 = dummy, a.bacc.mean2 = dvec, a.bacc.invstd2 = dvec;
+  }
+  const dfa::ConvPlan p = dfa::conv_plan(a, (int)mode);
+  static const char* const kFamily[] = {"nop", "invalid", "halo_c64", "halo", "igemm64", "smallc", "generic"};
+  using namespace pybind11::literals;
+  return py::dict("family"_a = kFamily[p.family], "BM"_a = p.BM, "BN"_a = p.BN, "fast"_a = p.fast, "par"_a = p.par,
+                  "pool"_a = p.pool, "splits"_a = p.splits, "wide"_a = p.wide, "row"_a = p.row, "fold"_a = p.fold,
+                  "ks"_a = p.ks, "vec"_a = p.vec, "grid"_a = p.grid, "block"_a = p.block, "combine"_a = p.combine,
+                  "drop_after"_a = p.drop_after, "splitk_floats"_a = p.splitk_floats, "bn_ntm"_a = p.bn_ntm,
+                  "bn_ntn"_a = p.bn_ntn, "bacc_ok"_a = p.bacc_ok);
 }
 
 void igemm_wgrad_py(torch::Tensor dy, torch::Tensor src, torch::Tensor gw, c10::optional<torch::Tensor> gb,
@@ -891,44 +923,10 @@ void bind_layers(py::module_& m) {
         py::arg("bn_momentum") = 0.1, py::arg("bn_eps") = 1e-5, py::arg("bn_gscale") = 1.0,
         py::arg("bacc") = py::none(), py::arg("bacc_mode") = 0, py::arg("bacc_in") = std::vector<torch::Tensor>{},
         py::arg("bacc2") = py::none(), py::arg("bacc2_in") = std::vector<torch::Tensor>{});
-  m.def("igemm_bacc_supported", [](int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector<int64_t> geom,
-                                   int64_t mode, int64_t bacc_mode, bool two, bool has_res, bool has_mask) {
-    // the dispatch decision of igemm_fwd for a launch with these shapes (16-byte aligned operands)
-    dfa::IGemmArgs a{};
-    set_conv_geom(a, geom, (int)mode);
-    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.Kpad = (int)Kpad; a.ldc = (int)N; a.lda = 0;
-    static dfa::bf16 dummy[8] __attribute__((aligned(16)));
-    static double dacc[2] __attribute__((aligned(16)));
-    static float dvec[2] __attribute__((aligned(16)));
-    a.src = dummy; a.w = dummy; a.out = dummy;
-    if (has_res) a.res = dummy;
-    if (has_mask) a.mask = dummy;
-    a.bacc.acc = dacc;
-    a.bacc.nrep = 1;
-    a.bacc.mode = (int)bacc_mode;
-    if (bacc_mode == 1) a.bacc.x = dummy, a.bacc.mean = dvec, a.bacc.invstd = dvec;
-    if (two) a.bacc.acc2 = dacc, a.bacc.x2 = dummy, a.bacc.mean2 = dvec, a.bacc.invstd2 = dvec;
-    return dfa::igemm_bacc_ok(a, (int)mode);
-  });
-  m.def("igemm64_bn_tiles", [](int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector<int64_t> geom, int64_t mode) {
-    dfa::IGemmArgs a{};
-    set_conv_geom(a, geom, (int)mode);
-    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.Kpad = (int)Kpad; a.ldc = (int)N;
-    static dfa::bf16 layout_dummy[8] __attribute__((aligned(16)));
-    a.src = layout_dummy; a.w = layout_dummy; a.out = layout_dummy;
-    int ntn = 0;
-    const int ntm = dfa::igemm64_bn_layout(a, (int)mode, &ntn);
-    return std::make_tuple((int64_t)ntm, (int64_t)ntn);
-  });
-  m.def("igemm64_pool_supported", [](int64_t H, int64_t W, int64_t C, int64_t OH, int64_t OW, int64_t K, int64_t N) {
-    dfa::IGemmArgs a{};
-    a.SH = (int)H; a.SW = (int)W; a.SC = (int)C; a.OH = (int)OH; a.OW = (int)OW; a.M = 4; a.N = (int)N; a.ldc = (int)N;
-    a.K = (int)K; a.Kpad = (int)((K + 31) / 32 * 32);
-    static dfa::bf16 layout_dummy[8] __attribute__((aligned(16)));
-    static uint8_t codep[4] __attribute__((aligned(4)));
-    a.src = layout_dummy; a.w = layout_dummy; a.out = layout_dummy; a.pool_code = codep;
-    return dfa::igemm64_pool_supported(a) && N % 8 == 0;
-  });
+  m.def("conv_plan", &conv_plan_py, "the launch plan of igemm_fwd for these shapes (csrc/conv_plan.hip), as a dict",
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("Kpad"), py::arg("geom"), py::arg("mode"),
+        py::arg("bacc_mode") = -1, py::arg("two") = false, py::arg("has_res") = false, py::arg("has_mask") = false,
+        py::arg("pooled") = false, py::arg("lda") = 0, py::arg("drop") = false, py::arg("bn") = false);
   m.def("unpool2", [](torch::Tensor dyp, torch::Tensor code, torch::Tensor dy) {
     need(dyp, at::kBFloat16, "unpool dyp");
     need(dy, at::kBFloat16, "unpool dy");

@@ -46,11 +46,7 @@ __device__ __forceinline__ u32x4_t cload16(const void* p) {
   return r;
 }
 
-constexpr int kCP = 128;              // output pixels per workgroup
-constexpr int kCS = 72;               // halo row stride (bf16)
-constexpr int kCXP = 9;               // halo staging passes of 32 rows
-constexpr int kCXR = 32 * kCXP;       // staged halo pixels (>= TI * (R+2) * (W+2))
-constexpr int kCXL = 320;             // LDS halo rows (>= TI * (R+2) * HWP)
+constexpr int kCS = 72;               // halo row stride (bf16); kCP, kCXP, kCXR, kCXL: kernels.h
 
 struct C3P {
   const bf16* src;   // NHWC [.][H][W][Cin]
@@ -83,7 +79,7 @@ __device__ __forceinline__ int wswz(int row, int chunk) { return row * 64 + ((ch
 struct C3Pre {
   bf16x4_t rv, rm, mk;
 };
-// (every tensor the epilogue touches is [M][ldc] bf16 under 4 GB -- conv3_halo_supported -- so one 32-bit
+// (every tensor the epilogue touches is [M][ldc] bf16 under 4 GB -- csrc/conv_plan.hip -- so one 32-bit
 // byte offset per element serves all of them: an SGPR base + VGPR offset per load instead of a 64-bit
 // address register pair per pointer and element)
 template <typename T>
@@ -437,8 +433,7 @@ __global__ void __launch_bounds__(256, 2) conv3_halo_kernel(C3P p) {
 // barrier.  A persistent workgroup of two 4-wave groups walks 2 x tpw 128-pixel tiles; each group owns
 // one halo buffer and prefetches its next tile's halo into registers while it computes the current one
 // (the per-tile setup and the halo latency were most of a 9-step workgroup's life in the tiled kernel).
-constexpr int kC64XP = 7;             // halo staging passes per group (224 rows)
-constexpr int kC64XR = 32 * kC64XP;
+// (kC64XP halo staging passes per group, kC64XR = 224 rows: kernels.h)
 
 // Barrier of one 4-wave group of a workgroup (the workgroup-wide s_barrier would keep the two groups in
 // lockstep, so both would sit in their epilogues -- memory latency, no MFMA -- at the same time).  Lane 0
@@ -654,7 +649,6 @@ __global__ void __launch_bounds__(512, 1) conv3_halo_c64_kernel(C3P p) {
 // the device's first request (null -- the combine launch -- if that request comes during a capture or
 // the pool is used up); a capture stream takes a pool buffer without any allocation.  Folded convs on
 // one stream run in stream order, so they share that stream's buffer safely.
-constexpr int kC3Tickets = 1024;
 constexpr int kC3Pool = 64;  // buffers per device (torch's stream pools are finite, so are the keys)
 unsigned* c3_tickets(hipStream_t st) {
   static std::mutex mu;
@@ -684,42 +678,15 @@ unsigned* c3_tickets(hipStream_t st) {
   return t;
 }
 
-bool c3_geom(int H, int W, int& R, int& TI) {
-  if (W < 4 || W > 64 || kCP % W != 0) return false;
-  const int rpt = kCP / W;
-  if (rpt <= H) {
-    if (H % rpt != 0) return false;
-    R = rpt, TI = 1;
-  } else {
-    if (rpt % H != 0) return false;
-    R = H, TI = rpt / H;
-  }
-  return TI * (R + 2) * (W + 2) <= kCXR && TI * (R + 2) * (W == 16 ? 32 : W + 2) <= kCXL;
-}
-
 }  // namespace
 
-bool conv3_halo_supported(const IGemmArgs& a, int mode) {
-  static const int on = diag_int("conv_halo", 1);
-  int R, TI;
-  if (!on || (mode != MODE_FWD && mode != MODE_DGRAD)) return false;
-  return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.SH == a.OH && a.SW == a.OW && a.SC % 64 == 0 &&
-         a.N % 64 == 0 && a.K == 9 * a.SC && a.Kpad >= a.K && a.Kpad % 8 == 0 && a.ldc % 4 == 0 && !a.bias &&
-         !a.out_f32 && !a.drop.on && !a.pool_code && !a.bn.part &&
-         a.M % kCP == 0 && a.M % (a.OH * a.OW) == 0 && c3_geom(a.OH, a.OW, R, TI) &&
-         (long long)a.M * a.ldc * 2 < (1LL << 32) &&  // one 32-bit byte offset per epilogue element
-         ((uintptr_t)a.src & 15) == 0 && ((uintptr_t)a.w & 15) == 0 && ((uintptr_t)a.out & 7) == 0 &&
-         (((uintptr_t)a.res | (uintptr_t)a.resmask | (uintptr_t)a.mask) & 7) == 0;
-}
-
-hipError_t conv3_halo(const IGemmArgs& a, int mode, hipStream_t st) {
+// the kernel the plan names (csrc/conv_plan.hip: 64 -> 64, tile width, splits, fold)
+hipError_t conv3_halo(const IGemmArgs& a, const ConvPlan& pl, int mode, hipStream_t st) {
   C3P p;
-  int R = 0, TI = 0;
-  c3_geom(a.OH, a.OW, R, TI);
   p.src = a.src, p.w = a.w, p.res = a.res, p.resmask = a.resmask, p.mask = a.mask;
   p.out = reinterpret_cast<bf16*>(a.out);
   p.H = a.OH, p.W = a.OW, p.Cin = a.SC, p.Cout = a.N, p.Kpad = a.Kpad, p.ldc = a.ldc;
-  p.R = R, p.HW2 = a.OW + 2, p.HR2 = R + 2, p.hrows = TI * (R + 2) * (a.OW + 2), p.rows_per_tile = kCP / a.OW;
+  p.R = pl.R, p.HW2 = a.OW + 2, p.HR2 = pl.R + 2, p.hrows = pl.TI * (pl.R + 2) * (a.OW + 2), p.rows_per_tile = kCP / a.OW;
   // W = 16: the 32 pixels of a pixel-interleaved MFMA tile span two image rows; an image-row pitch of
   // W + 16 halo rows keeps their bank slots 16 apart, so the two-chunk ds_read_b128 groups stay
   // conflict-free (24 % conflict cycles on layer 2 with the W + 2 pitch)
@@ -729,56 +696,15 @@ hipError_t conv3_halo(const IGemmArgs& a, int mode, hipStream_t st) {
   p.relu = a.relu;
   p.alpha = a.alpha;
   p.bacc = a.bacc;
-  static const int c64 = diag_int("conv_halo_c64", 1);
-  if (c64 && a.SC == 64 && a.N == 64 && p.hrows <= kC64XR && p.ntiles >= 512) {
-    // weights resident: one 8-wave workgroup per CU, tiles split evenly (an even count per workgroup)
-    p.tps = 2 * cdiv(p.ntiles, 2 * 256);
-    p.nco = 1, p.ks = 1, p.cbs = 1, p.ws = nullptr;
-    const dim3 grid(cdiv(p.ntiles, p.tps));
-    if (mode == MODE_DGRAD) hipLaunchKernelGGL(conv3_halo_c64_kernel<true>, grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL(conv3_halo_c64_kernel<false>, grid, dim3(512), 0, st, p);
-    return hipGetLastError();
-  }
-  // 128-channel tiles while that still gives >= 2 workgroups per CU
-  const bool wide = a.N % 128 == 0 && (long long)p.ntiles * (a.N / 128) >= 512;
+  p.tps = pl.tps, p.nco = a.N / pl.BN;
+  p.ks = pl.ks, p.cbs = a.SC / 64 / pl.ks, p.ws = pl.ks > 1 ? a.splitk_ws : nullptr;
+  p.tick = pl.fold ? c3_tickets(st) : nullptr;  // (null: the pool is used up, the combine launch instead)
   const bool flip = mode == MODE_DGRAD;
-  p.nco = a.N / (wide ? 128 : 64);
-  // under-filled launches (ResNet layer 4: 256 workgroups of 72 steps) split the input channel blocks
-  // over workgroups when the caller provides igemm64's split-K workspace; a fixed-order combine applies
-  // the epilogue
-  const int ncb = a.SC / 64;
-  p.ks = 1, p.cbs = ncb, p.ws = nullptr;
-  static const int ksplit = diag_int("conv_halo_splitk", 1);
-  if (ksplit && a.splitk_ws && p.ntiles * p.nco < 512) {
-    const long long wsf = igemm64_splitk_floats(a, mode);  // what the caller allocated
-    static const int ksmax = diag_int("conv_halo_ks", 2);  // 2 measured faster than 4 (layer 4: 38.4 vs 43.1 us)
-    int ks = 1;
-    while (ks < ksmax && ncb % (2 * ks) == 0 && (long long)p.ntiles * p.nco * ks * 2 <= 1024 &&
-           (long long)(2 * ks) * a.M * a.N <= wsf)
-      ks *= 2;
-    if (ks > 1) p.ks = ks, p.cbs = ncb / ks, p.ws = a.splitk_ws;
-  }
-  // two splits: the tile's last arriver combines and runs the epilogue in this launch (c3_tickets); the
-  // combine launch otherwise
-  p.tick = nullptr;
-  static const int fold = diag_int("conv_halo_fold", 1);
-  if (fold && p.ks == 2 && p.ntiles * p.nco <= kC3Tickets &&
-      (long long)p.ks * p.ntiles * kCP * p.Cout * 4 < (1LL << 31))
-    p.tick = c3_tickets(st);
-  const dim3 grid(p.ntiles * p.nco * p.ks);
-  if (wide) {
-    if (flip) hipLaunchKernelGGL((conv3_halo_kernel<128, true, false>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv3_halo_kernel<128, false, false>), grid, dim3(256), 0, st, p);
-  } else {
-    static const int row = diag_int("conv_halo_row", 1);  // a kernel row per step (conv3_halo_kernel ROW)
-    if (row) {
-      if (flip) hipLaunchKernelGGL((conv3_halo_kernel<64, true, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((conv3_halo_kernel<64, false, true>), grid, dim3(256), 0, st, p);
-    } else {
-      if (flip) hipLaunchKernelGGL((conv3_halo_kernel<64, true, false>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((conv3_halo_kernel<64, false, false>), grid, dim3(256), 0, st, p);
-    }
-  }
+  void (*k)(C3P) = flip ? conv3_halo_c64_kernel<true> : conv3_halo_c64_kernel<false>;
+  if (pl.family == CONV_HALO && pl.wide) k = flip ? conv3_halo_kernel<128, true, false> : conv3_halo_kernel<128, false, false>;
+  else if (pl.family == CONV_HALO && pl.row) k = flip ? conv3_halo_kernel<64, true, true> : conv3_halo_kernel<64, false, true>;
+  else if (pl.family == CONV_HALO) k = flip ? conv3_halo_kernel<64, true, false> : conv3_halo_kernel<64, false, false>;
+  hipLaunchKernelGGL(k, dim3(pl.grid), dim3(pl.block), 0, st, p);
   DFA_HIP_CHECK(hipGetLastError());
   if (p.ks > 1 && p.tick == nullptr) {  // the combine applies the epilogue (and the BatchNorm sums)
     IGemmArgs c = a;

@@ -540,79 +540,47 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ partial, float* __
 // ------------------------------------------------------------------------------------------
 // host launchers
 template <int BM, int BN, int WM, int WN, int MODE, bool VEC>
-static hipError_t launch_fwd_cfg(const IGemmArgs& a, hipStream_t st) {
-  const int blocks = cdiv(a.M, BM) * cdiv(a.N, BN);
+static hipError_t launch_fwd_cfg(const IGemmArgs& a, const ConvPlan& p, hipStream_t st) {
   size_t lds = (size_t)2 * (BM + BN) * LDS_ROW * sizeof(bf16);
   if (MODE != MODE_DIRECT && !VEC) lds += (size_t)a.Kpad * sizeof(int);
-  hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, MODE, VEC>), dim3(blocks), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, MODE, VEC>), dim3(p.grid), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
+// the generic kernel on the plan's tile (csrc/conv_plan.hip plan_generic)
+template <int BM, int MODE, bool VEC>
+static hipError_t launch_fwd_bm(const IGemmArgs& a, const ConvPlan& p, hipStream_t st) {
+  if (p.BN == 16) return launch_fwd_cfg<BM, 16, 4, 1, MODE, VEC>(a, p, st);
+  if (p.BN == 32) return launch_fwd_cfg<BM, 32, 4, 1, MODE, VEC>(a, p, st);
+  if (p.BN == 64) return launch_fwd_cfg<BM, 64, 2, 2, MODE, VEC>(a, p, st);
+  return launch_fwd_cfg<BM, 128, BM == 64 ? 1 : 2, BM == 64 ? 4 : 2, MODE, VEC>(a, p, st);
+}
 template <int MODE, bool VEC>
-static hipError_t launch_fwd_mode(const IGemmArgs& a, hipStream_t st) {
-  // Tile choice: N fits one tile where possible; shrink BM when M alone cannot fill 256 CUs.
-  const bool small_m = cdiv(a.M, 128) < 512;
-  if (a.N <= 16) {
-    if (small_m) return launch_fwd_cfg<64, 16, 4, 1, MODE, VEC>(a, st);
-    return launch_fwd_cfg<128, 16, 4, 1, MODE, VEC>(a, st);
-  }
-  if (a.N <= 32) {
-    if (small_m) return launch_fwd_cfg<64, 32, 4, 1, MODE, VEC>(a, st);
-    return launch_fwd_cfg<128, 32, 4, 1, MODE, VEC>(a, st);
-  }
-  if (a.N <= 64) {
-    if (small_m) return launch_fwd_cfg<64, 64, 2, 2, MODE, VEC>(a, st);
-    return launch_fwd_cfg<128, 64, 2, 2, MODE, VEC>(a, st);
-  }
-  if (small_m) return launch_fwd_cfg<64, 128, 1, 4, MODE, VEC>(a, st);
-  return launch_fwd_cfg<128, 128, 2, 2, MODE, VEC>(a, st);
+static hipError_t launch_fwd_mode(const IGemmArgs& a, const ConvPlan& p, hipStream_t st) {
+  return p.BM == 64 ? launch_fwd_bm<64, MODE, VEC>(a, p, st) : launch_fwd_bm<128, MODE, VEC>(a, p, st);
 }
 
-static hipError_t igemm_fwd_nodrop(const IGemmArgs& a, int mode, hipStream_t st);
-
-// Can this igemm_fwd call accumulate BatchNorm sums of its output (a.bacc, csrc/bn_acc.h)?  The halo and
-// igemm64 kernels (and their split-K combine) in both modes, with the vectorised bf16 epilogue; the
-// generic kernel the forward sums only.
-bool igemm_bacc_ok(const IGemmArgs& a, int mode) {
-  if (mode == MODE_DIRECT || a.out_f32 || a.drop.on || a.pool_code || a.bn.part || a.M <= 0 || a.N <= 0) return false;
-  if (a.bacc.nrep < 1 || a.bacc.nrep > kBnAccMaxRep || (a.bacc.mode == 1 && (!a.bacc.x || !a.bacc.mean))) return false;
-  if (a.bacc.acc2 && (a.bacc.mode != 1 || !a.bacc.x2 || !a.bacc.mean2)) return false;
-  if (!a.irregular && (conv3_halo_supported(a, mode) || igemm64_supported(a, mode))) {
-    if ((a.ldc & 3) || (a.N & 3) || ((uintptr_t)a.out & 15) ||
-        (((uintptr_t)a.res | (uintptr_t)a.resmask | (uintptr_t)a.mask | (uintptr_t)a.bacc.x | (uintptr_t)a.bacc.x2) & 7))
-      return false;
-    return a.N <= 1024 && 256 % (a.N / 4) == 0;  // (a split-K combine may apply the epilogue)
-  }
-  return mode == MODE_FWD && a.bacc.mode == 0 && (a.irregular || !smallc_fwd_supported(a, mode));
+static hipError_t igemm_fwd_generic(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st) {
+  if (mode == MODE_DIRECT)
+    return p.vec ? launch_fwd_mode<MODE_DIRECT, true>(a, p, st) : launch_fwd_mode<MODE_DIRECT, false>(a, p, st);
+  if (mode == MODE_FWD)
+    return p.vec ? launch_fwd_mode<MODE_FWD, true>(a, p, st) : launch_fwd_mode<MODE_FWD, false>(a, p, st);
+  return p.vec ? launch_fwd_mode<MODE_DGRAD, true>(a, p, st) : launch_fwd_mode<MODE_DGRAD, false>(a, p, st);
 }
 
-hipError_t igemm_fwd(const IGemmArgs& a, int mode, hipStream_t st) {
-  if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  if (a.bacc.acc && !igemm_bacc_ok(a, mode)) return hipErrorInvalidValue;
-  if (a.drop.on && (a.out_f32 || a.ldc != a.N)) return hipErrorInvalidValue;
-  if (a.irregular && (a.pool_code || a.bn.part)) return hipErrorInvalidValue;
-  if (a.pool_code) return igemm64_pool_supported(a) && mode == MODE_FWD ? igemm64(a, mode, st) : hipErrorInvalidValue;
-  if (!a.irregular && conv3_halo_supported(a, mode)) return conv3_halo(a, mode, st);
-  if (!a.irregular && igemm64_supported(a, mode)) return igemm64(a, mode, st);  // dropout in its epilogues
-  if (!a.drop.on) return igemm_fwd_nodrop(a, mode, st);
+hipError_t igemm_fwd(const IGemmArgs& a, int mode, hipStream_t st) { return igemm_fwd(a, conv_plan(a, mode), mode, st); }
+
+hipError_t igemm_fwd(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st) {
+  if (p.family == CONV_NOP) return hipSuccess;
+  if (p.family == CONV_INVALID || (p.splitk_floats > 0 && !a.splitk_ws)) return hipErrorInvalidValue;
+  if (p.family == CONV_HALO || p.family == CONV_HALO_C64) return conv3_halo(a, p, mode, st);
+  if (p.family == CONV_IGEMM64) return igemm64(a, p, mode, st);
   IGemmArgs b = a;
-  b.drop = DropSpec{};
-  DFA_HIP_CHECK(igemm_fwd_nodrop(b, mode, st));
+  b.drop = DropSpec{};  // these kernels have no dropout epilogue: its own launch afterwards
+  DFA_HIP_CHECK(p.family == CONV_SMALLC ? smallc_fwd(b, st) : igemm_fwd_generic(b, p, mode, st));
+  if (!p.drop_after) return hipSuccess;
   bf16* o = reinterpret_cast<bf16*>(a.out);
   return dropout(o, o, nullptr, (long long)a.M * a.N, a.drop.p, a.drop.seed, a.drop.step, st);
-}
-
-static hipError_t igemm_fwd_nodrop(const IGemmArgs& a, int mode, hipStream_t st) {
-  if (!a.irregular && smallc_fwd_supported(a, mode)) return smallc_fwd(a, st);
-  const bool aligned = ((uintptr_t)a.src & 15) == 0;
-  if (mode == MODE_DIRECT) {
-    const bool vec = aligned && a.lda % 8 == 0 && a.K % 8 == 0;
-    return vec ? launch_fwd_mode<MODE_DIRECT, true>(a, st) : launch_fwd_mode<MODE_DIRECT, false>(a, st);
-  }
-  const bool vec = aligned && a.SC % 8 == 0;
-  if (mode == MODE_FWD)
-    return vec ? launch_fwd_mode<MODE_FWD, true>(a, st) : launch_fwd_mode<MODE_FWD, false>(a, st);
-  return vec ? launch_fwd_mode<MODE_DGRAD, true>(a, st) : launch_fwd_mode<MODE_DGRAD, false>(a, st);
 }
 
 template <int BN, int BKO, int WN, int WK, int MODE, bool DVEC, bool XVEC>

@@ -21,7 +21,6 @@
 //     the weights as the MFMA A operand so each lane stores 4 adjacent output channels at once
 #include "common.h"
 #include "kernels.h"
-#include "diag.h"
 #include "bn_epi.h"
 #include "bn_acc.h"
 
@@ -800,97 +799,39 @@ static int splitk_epi_grid(const IGemmArgs& a) {
   const long long total4 = (long long)a.M * (a.N / 4);
   return (int)min((total4 + 255) / 256, a.bacc.acc ? 512LL : 4096LL);
 }
-static bool bacc_combine_ok(const IGemmArgs& a) {
-  return a.N % 4 == 0 && a.N <= 1024 && 256 % (a.N / 4) == 0 && !a.out_f32 && !a.drop.on && a.ldc % 4 == 0;
-}
 
-// Split-K for under-filled launches: fewer than ~2 workgroups per CU and a long K (ResNet-18 layers 3-4:
-// M = B*8*8 or B*4*4 with K up to 4608) leave one wave per SIMD waiting on every step
-template <int BM, int BN>
-static int splitk_for(const IGemmArgs& a) {
-  if (a.pool_code || a.bn.part) return 1;
-  const long long tiles = (long long)cdiv(a.M, BM) * cdiv(a.N, BN);
-  const int nk = cdiv(a.K, 64);
-  if (a.N % 4 || a.ldc % 4 || tiles >= 512 || nk < 32) return 1;
-  if (((uintptr_t)a.out & 15) || (((uintptr_t)a.res | (uintptr_t)a.resmask | (uintptr_t)a.mask) & 7)) return 1;
-  int s = 1;
-  while (s < 4 && tiles * s * 2 <= 1024 && nk / (s * 2) >= 16) s *= 2;
-  // severely under-filled (the Keras CNN's 9216 -> 128 dense: 16 tiles): up to 16 splits of >= 4 steps
-  if (tiles * s < 256)
-    while (s < 16 && tiles * s * 2 <= 512 && nk / (s * 2) >= 4) s *= 2;
-  return s;
-}
-
-// FAST gather eligibility (see igemm64_kernel): whole 64-channel blocks per tap, <= 32 taps, stride-1
-// data gradient, and operands addressable with 32-bit byte offsets below the out-of-range marker
-static bool igemm64_fast_ok(const IGemmArgs& a, int mode) {
-  if (mode == MODE_DIRECT || a.SC % 64 || a.K != a.KH * a.KW * a.SC || a.KH * a.KW > 32 || a.Kpad < a.K) return false;
-  if (mode == MODE_DGRAD && a.stride != 1 && a.stride != 2) return false;
-  if (a.OH <= 0 || a.OW <= 0 || a.M % (a.OH * a.OW)) return false;
-  static const bool off = diag_int("igemm_fast", 1) == 0;
-  if (off) return false;
-  const long long sbytes = (long long)(a.M / (a.OH * a.OW)) * a.SH * a.SW * a.SC * 2;
-  const long long wbytes = (long long)round_up(a.N, 16) * a.Kpad * 2;
-  return sbytes < (1LL << 30) && wbytes < (1LL << 30);
-}
-
+// the template instantiation the plan names (csrc/conv_plan.hip chose tile, variant and grid)
 template <int BM, int BN, int MODE>
-hipError_t launch64(IGemmArgs a, hipStream_t st) {
-  const FastDiv d_ow = make_fastdiv((unsigned)max(a.OW, 1)), d_ohw = make_fastdiv((unsigned)max(a.OH * a.OW, 1));
-  const int blocks = cdiv(a.M, BM) * cdiv(a.N, BN);
-  constexpr int D = kIgemm64Stages;
-  if (MODE == MODE_FWD && a.pool_code != nullptr) {
-    hipLaunchKernelGGL((igemm64_kernel<BM, BN, MODE_FWD, D, false, true>), dim3(blocks), dim3(256), 0, st, a,
-                       make_fastdiv((unsigned)max(a.OW / 2, 1)), d_ohw);
-    return hipGetLastError();
+hipError_t launch64(IGemmArgs a, const ConvPlan& p, hipStream_t st) {
+  FastDiv d_ow = make_fastdiv((unsigned)max(a.OW, 1));
+  const FastDiv d_ohw = make_fastdiv((unsigned)max(a.OH * a.OW, 1));
+  constexpr int D = kIgemm64Stages;  // (prefetch depths 3 and 4 measured equal to 2 on every ResNet-18 shape)
+  constexpr bool kFast = MODE != MODE_DIRECT;
+  constexpr int kParMode = MODE == MODE_DGRAD ? MODE_DGRAD : MODE_FWD;
+  const bool fast = kFast && p.fast;
+  void (*k)(IGemmArgs, FastDiv, FastDiv) = igemm64_kernel<BM, BN, MODE, D, false>;
+  if (MODE == MODE_FWD && p.pool) {
+    k = igemm64_kernel<BM, BN, MODE_FWD, D, false, true>;
+    d_ow = make_fastdiv((unsigned)max(a.OW / 2, 1));
+  } else if (MODE == MODE_DGRAD && p.par) {
+    k = igemm64_kernel<BM, BN, kParMode, D, false, false, true, MODE == MODE_DGRAD>;
+  } else if (p.splits > 1) {
+    a.splits = p.splits;
+    k = fast ? igemm64_kernel<BM, BN, MODE, D, true, false, kFast> : igemm64_kernel<BM, BN, MODE, D, true>;
+  } else if (fast) {
+    k = igemm64_kernel<BM, BN, MODE, D, false, false, kFast>;
   }
-  constexpr bool kFastMode = MODE != MODE_DIRECT;
-  const bool fast = kFastMode && igemm64_fast_ok(a, MODE);
-  if (MODE == MODE_DGRAD && a.stride == 2) {
-    if (!fast) {
-      hipLaunchKernelGGL((igemm64_kernel<BM, BN, MODE, D, false>), dim3(blocks), dim3(256), 0, st, a, d_ow, d_ohw);
-      return hipGetLastError();
-    }
-    // parity classes: grid = sum of the 4 classes' tiles (no split-K)
-    const int nimg = a.M / (a.OH * a.OW);
-    int grid = 0;
-    for (int cl = 0; cl < 4; ++cl) {
-      const int hc = (a.OH - (cl >> 1) + 1) >> 1, wc = (a.OW - (cl & 1) + 1) >> 1;
-      grid += cdiv(nimg * hc * wc, BM) * cdiv(a.N, BN);
-    }
-    constexpr int kParMode = MODE == MODE_DGRAD ? MODE_DGRAD : MODE_FWD;
-    hipLaunchKernelGGL((igemm64_kernel<BM, BN, kParMode, D, false, false, true, MODE == MODE_DGRAD>), dim3(grid),
-                       dim3(256), 0, st, a, d_ow, d_ohw);
-    return hipGetLastError();
-  }
-  const int s = a.splitk_ws ? splitk_for<BM, BN>(a) : 1;
-  if (s > 1) {
-    a.splits = s;
-    if (fast)
-      hipLaunchKernelGGL((igemm64_kernel<BM, BN, MODE, D, true, false, kFastMode>), dim3(blocks * s), dim3(256), 0, st, a, d_ow, d_ohw);
-    else
-      hipLaunchKernelGGL((igemm64_kernel<BM, BN, MODE, D, true>), dim3(blocks * s), dim3(256), 0, st, a, d_ow, d_ohw);
-    DFA_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(igemm64_splitk_epilogue_kernel, dim3(splitk_epi_grid(a)), dim3(256), 0, st, a);
-    return hipGetLastError();
-  }
-  // (prefetch depths 3 and 4 measured equal to 2 on every ResNet-18 shape: scripts/convbench.py)
-  if (fast)
-    hipLaunchKernelGGL((igemm64_kernel<BM, BN, MODE, D, false, false, kFastMode>), dim3(blocks), dim3(256), 0, st, a, d_ow, d_ohw);
-  else
-    hipLaunchKernelGGL((igemm64_kernel<BM, BN, MODE, D, false>), dim3(blocks), dim3(256), 0, st, a, d_ow, d_ohw);
-  return hipGetLastError();
+  hipLaunchKernelGGL(k, dim3(p.grid), dim3(256), 0, st, a, d_ow, d_ohw);
+  DFA_HIP_CHECK(hipGetLastError());
+  return p.combine ? igemm64_splitk_combine(a, st) : hipSuccess;
 }
 
 template <int MODE>
-hipError_t launch64_mode(const IGemmArgs& a, hipStream_t st) {
-  if (a.N <= 32) return launch64<128, 32, MODE>(a, st);  // Keras CNN conv2 (32 channels): no half-empty tiles
-  // (a 256 x 64 tile with 4 x 1 waves of 64 x 64 measured 9-16% slower on ResNet layer 1: 8 waves per
-  // CU instead of 12)
-  if (a.N <= 64) return launch64<128, 64, MODE>(a, st);
-  // 128x128 while that still gives >= 2 workgroups per CU, else 64x128
-  if ((long long)cdiv(a.M, 128) * cdiv(a.N, 128) >= 512) return launch64<128, 128, MODE>(a, st);
-  return launch64<64, 128, MODE>(a, st);
+hipError_t launch64_mode(const IGemmArgs& a, const ConvPlan& p, hipStream_t st) {
+  if (p.BN == 32) return launch64<128, 32, MODE>(a, p, st);
+  if (p.BN == 64) return launch64<128, 64, MODE>(a, p, st);
+  if (p.BM == 128) return launch64<128, 128, MODE>(a, p, st);
+  return launch64<64, 128, MODE>(a, p, st);
 }
 
 }  // namespace
@@ -901,45 +842,10 @@ hipError_t igemm64_splitk_combine(const IGemmArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-long long igemm64_splitk_floats(const IGemmArgs& a, int mode) {
-  static const bool off = diag_int("igemm_splitk", 1) == 0;
-  if (off || !igemm64_supported(a, mode) || a.N <= 64) return 0;
-  if ((long long)cdiv(a.M, 128) * cdiv(a.N, 128) >= 512) return 0;  // 128 x 128 tiles: already filled
-  const int s = splitk_for<64, 128>(a);
-  return s > 1 ? (long long)s * a.M * a.N : 0;
-}
-
-// Row tiles (and column ranges) of the launch when it can finalise BatchNorm statistics of its output
-// (kernels.h BnEpi): conv forward or data gradient, bf16 output, no pooling, no split-K (those launches
-// keep the statistics pass) and no parity-class stride-2 data gradient.  0 = it cannot.
-int igemm64_bn_layout(const IGemmArgs& a, int mode, int* ntn) {
-  if (mode == MODE_DIRECT || !igemm64_supported(a, mode) || a.pool_code || a.out_f32) return 0;
-  if (igemm64_splitk_floats(a, mode) > 0) return 0;
-  if (mode == MODE_DGRAD && a.stride == 2 && igemm64_fast_ok(a, mode)) return 0;
-  if (a.N <= 32) return 0;  // 128 x 32 tiles are built without the statistics epilogue
-  // tile shape as launch64_mode picks it
-  const int BN = a.N <= 32 ? 32 : (a.N <= 64 ? 64 : 128);
-  const int BM = (a.N <= 64 || (long long)cdiv(a.M, 128) * cdiv(a.N, 128) >= 512) ? 128 : 64;
-  if (ntn) *ntn = cdiv(a.N, BN);
-  return cdiv(a.M, BM);
-}
-int igemm64_bn_tiles(const IGemmArgs& a, int mode) { return igemm64_bn_layout(a, mode, nullptr); }
-
-bool igemm64_pool_supported(const IGemmArgs& a) {
-  return igemm64_supported(a, MODE_FWD) && a.OH % 2 == 0 && a.OW % 2 == 0 && a.N % 4 == 0 && a.ldc == a.N &&
-         !a.out_f32 && !a.mask && !a.res && ((uintptr_t)a.out & 7) == 0 && ((uintptr_t)a.pool_code & 3) == 0;
-}
-
-bool igemm64_supported(const IGemmArgs& a, int mode) {
-  if (((uintptr_t)a.src & 15) || ((uintptr_t)a.w & 15) || a.Kpad % 8 || a.M <= 0 || a.N <= 0) return false;
-  if (mode == MODE_DIRECT) return a.lda % 8 == 0 && a.K % 8 == 0;
-  return !a.irregular && a.SC % 8 == 0 && a.OH > 0 && a.OW > 0;
-}
-
-hipError_t igemm64(const IGemmArgs& a, int mode, hipStream_t st) {
-  if (mode == MODE_DIRECT) return launch64_mode<MODE_DIRECT>(a, st);
-  if (mode == MODE_FWD) return launch64_mode<MODE_FWD>(a, st);
-  return launch64_mode<MODE_DGRAD>(a, st);
+hipError_t igemm64(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st) {
+  if (mode == MODE_DIRECT) return launch64_mode<MODE_DIRECT>(a, p, st);
+  if (mode == MODE_FWD) return launch64_mode<MODE_FWD>(a, p, st);
+  return launch64_mode<MODE_DGRAD>(a, p, st);
 }
 
 }  // namespace dfa

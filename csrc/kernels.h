@@ -131,22 +131,48 @@ struct ParamDescTable {
   ParamDesc d[kInlineDescs];
 };
 
-hipError_t igemm_fwd(const IGemmArgs& a, int mode, hipStream_t st);
-bool igemm_bacc_ok(const IGemmArgs& a, int mode);  // can the launch accumulate a.bacc (BatchNorm sums)
-// 64-deep-step variant for the vectorizable cases (csrc/igemm64.hip); igemm_fwd dispatches to it
-bool igemm64_supported(const IGemmArgs& a, int mode);
-bool igemm64_pool_supported(const IGemmArgs& a);
-// row tiles (= BatchNorm partial rows) of the igemm64 launch for this problem, 0 if it cannot emit them
-int igemm64_bn_tiles(const IGemmArgs& a, int mode);
-int igemm64_bn_layout(const IGemmArgs& a, int mode, int* ntn);
+// The one decision of a forward / data-gradient launch (csrc/conv_plan.hip): which kernel runs, in which
+// variant, with what launch shape and scratch.  igemm_fwd and the launchers below switch on it and the
+// shape-only queries of the bindings read it; nothing else derives any part of it.
+enum ConvFamily { CONV_NOP, CONV_INVALID, CONV_HALO_C64, CONV_HALO, CONV_IGEMM64, CONV_SMALLC, CONV_GENERIC };
+struct ConvPlan {
+  int family;             // CONV_NOP: M or N <= 0; CONV_INVALID: igemm_fwd returns hipErrorInvalidValue
+  int BM, BN;             // igemm64 / generic tile; halo: BN = 128 (wide) or 64 output channels per workgroup
+  bool fast, par, pool;   // igemm64: FAST gather, parity-class stride-2 data gradient, pooled epilogue
+  int splits;             // igemm64 split-K (1: none)
+  bool wide, row, fold;   // halo: 128-channel tiles, a kernel row per step, the last arriver combines 2 splits
+  int ks, R, TI, tps;     // halo: channel-block splits; image rows / images per 128-pixel tile; tiles per
+                          // workgroup of the weights-resident 64 -> 64 kernel
+  bool vec;               // generic: 16-byte gathers
+  int grid, block;        // the main launch (smallc sizes its own: 0)
+  bool combine;           // a split-K combine launch follows (igemm64_splitk_combine)
+  bool drop_after;        // the folded dropout runs as its own launch afterwards (smallc / generic kernels)
+  long long splitk_floats;  // fp32 scratch the caller provides in IGemmArgs::splitk_ws ([splits][M][N])
+  // row tiles / column ranges of the launch that finalises BatchNorm statistics (a.bn.part set: always
+  // igemm64, whatever runs without it); 0 when it cannot: split-K, pooling, parity classes, 128 x 32 tiles
+  int bn_ntm, bn_ntn;
+  bool bacc_ok;           // the launch can accumulate a.bacc (BatchNorm sums, csrc/bn_acc.h)
+};
+ConvPlan conv_plan(const IGemmArgs& a, int mode);
+// with BatchNorm sums the split-K combine keeps a thread's 4 columns fixed over its grid-stride loop
+bool bacc_combine_ok(const IGemmArgs& a);
+// halo kernel staging limits (csrc/conv3_halo.hip), which bound the geometries the planner gives it
+constexpr int kCP = 128;              // output pixels per workgroup
+constexpr int kCXP = 9;               // halo staging passes of 32 rows
+constexpr int kCXR = 32 * kCXP;       // staged halo pixels (>= TI * (R+2) * (W+2))
+constexpr int kCXL = 320;             // LDS halo rows (>= TI * (R+2) * HWP)
+constexpr int kC64XP = 7;             // 64 -> 64 kernel: halo staging passes per group (224 rows)
+constexpr int kC64XR = 32 * kC64XP;
+constexpr int kC3Tickets = 1024;      // tickets of a folded two-split launch (one per output tile)
+
+hipError_t igemm_fwd(const IGemmArgs& a, int mode, hipStream_t st);  // plans, then launches
+hipError_t igemm_fwd(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st);
 hipError_t bn_finalize_partials(const float* part, int ntm, int C, long long M, float* mean, float* invstd,
                                 float* run_mean, float* run_var, float momentum, float eps, hipStream_t st);
 // dY of a pooled conv from the pooled gradient and the argmax codes (NHWC, 2x2 windows)
 hipError_t unpool2(const bf16* dyp, const uint8_t* code, bf16* dy, int B, int OH, int OW, int N, hipStream_t st);
-hipError_t igemm64(const IGemmArgs& a, int mode, hipStream_t st);
-// fp32 floats of split-K workspace igemm64 wants for this problem (0: no split); the caller allocates
-// them and passes the buffer in IGemmArgs::splitk_ws
-long long igemm64_splitk_floats(const IGemmArgs& a, int mode);
+// 64-deep-step variant for the vectorizable cases (csrc/igemm64.hip)
+hipError_t igemm64(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st);
 // out = epilogue(sum over a.splits of a.splitk_ws[s][M][N]) in a fixed order (igemm64's split-K combine)
 hipError_t igemm64_splitk_combine(const IGemmArgs& a, hipStream_t st);
 hipError_t igemm_wgrad(const WgradArgs& a, int mode, float* workspace, size_t ws_floats, hipStream_t st);
@@ -156,8 +182,7 @@ hipError_t wgrad_tr(const WgradArgs& a, float* workspace, size_t ws_floats, hipS
 // 3x3 stride-1 pad-1 conv weight gradient, halo-tiled LDS staging (csrc/wgrad_halo.hip): C, N % 64 == 0
 bool wgrad_halo_supported(const WgradArgs& a, int mode);
 // 3x3 stride-1 pad-1 conv forward / data gradient, halo-tiled LDS staging (csrc/conv3_halo.hip)
-bool conv3_halo_supported(const IGemmArgs& a, int mode);
-hipError_t conv3_halo(const IGemmArgs& a, int mode, hipStream_t st);
+hipError_t conv3_halo(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st);
 hipError_t wgrad_halo(const WgradArgs& a, float* workspace, size_t ws_floats, hipStream_t st);
 hipError_t maxpool_fwd(const bf16* x, bf16* y, int B, int H, int W, int C, int P, hipStream_t st,
                        DropSpec drop = DropSpec{});

@@ -173,18 +173,22 @@ def _bacc_kwargs(bacc):
     return kw
 
 
+def conv_plan(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad=False, **flags) -> dict:
+    """The launch plan (csrc/conv_plan.hip: kernel family, variant, grid, scratch, BatchNorm tiles) of the conv
+    forward, or of the data gradient with output [B][H][W][C]; {} without the native extension."""
+    m = native.get(build_if_missing=False)
+    g = ((B * H * W, C, KH * KW * N, Kpad, _geom(OH, OW, N, H, W, KH, KW, stride, pad), MODE_DGRAD) if dgrad else
+         (B * OH * OW, N, KH * KW * C, Kpad, _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD))
+    return m.conv_plan(*g, **flags) if m is not None else {}
+
+
 def conv_bacc_ok(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad=False, mode=0, two=False,
                  has_res=False, has_mask=False) -> bool:
     """Can the conv launch (forward, or the data gradient with output [B][H][W][C]) accumulate BatchNorm
-    sums of its output in its epilogue (igemm_bacc_ok on the dispatch the launch will take)?"""
-    m = native.get(build_if_missing=False)
-    if m is None or not hasattr(m, "igemm_bacc_supported"):
-        return False
-    if dgrad:
-        return bool(m.igemm_bacc_supported(B * H * W, C, KH * KW * N, Kpad, _geom(OH, OW, N, H, W, KH, KW, stride, pad),
-                                           MODE_DGRAD, int(mode), bool(two), bool(has_res), bool(has_mask)))
-    return bool(m.igemm_bacc_supported(B * OH * OW, N, KH * KW * C, Kpad, _geom(H, W, C, OH, OW, KH, KW, stride, pad),
-                                       MODE_FWD, int(mode), bool(two), bool(has_res), bool(has_mask)))
+    sums of its output in its epilogue?"""
+    p = conv_plan(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad, bacc_mode=int(mode), two=bool(two),
+                  has_res=bool(has_res), has_mask=bool(has_mask))
+    return bool(p.get("bacc_ok", False))
 
 
 def conv_fwd(x, w, bias, out, KH, KW, stride=1, pad=0, relu=False, bn=None, bacc=None):
@@ -208,14 +212,8 @@ def conv_bn_layout(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad=False
     [B][H][W][C] from an output gradient [B][OH][OW][N]) when it can finalise BatchNorm statistics of
     its output inside the launch; (0, 0) when it cannot.  Sizes: ws (ntm + ceil(ntm / 16)) * 2 * channels
     floats, tickets ntn * (1 + ceil(ntm / 16)) int32 (zero-initialised)."""
-    m = native.get(build_if_missing=False)
-    if m is None or not hasattr(m, "igemm64_bn_tiles"):
-        return 0, 0
-    if dgrad:
-        r = m.igemm64_bn_tiles(B * H * W, C, KH * KW * N, Kpad, _geom(OH, OW, N, H, W, KH, KW, stride, pad), MODE_DGRAD)
-    else:
-        r = m.igemm64_bn_tiles(B * OH * OW, N, KH * KW * C, Kpad, _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD)
-    return int(r[0]), int(r[1])
+    p = conv_plan(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad)
+    return (p["bn_ntm"], p["bn_ntn"]) if p.get("bn_ntm") else (0, 0)
 
 
 def bn_finalize_partials(part, ntm, C, M, mean, invstd, run_mean, run_var, momentum, eps):
@@ -226,11 +224,11 @@ def bn_finalize_partials(part, ntm, C, M, mean, invstd, run_mean, run_var, momen
 
 def conv_pool_supported(H, W, C, KH, KW, stride, pad, N) -> bool:
     """Conv + 2x2 max-pool in the igemm64 epilogue (pooled map + argmax codes only)."""
-    m = native.get(build_if_missing=False)
-    if m is None or not hasattr(m, "igemm64_pool_supported") or stride != 1:
+    if stride != 1 or N % 8:
         return False
     OH, OW = conv_out_hw(H, W, KH, KW, stride, pad)
-    return bool(m.igemm64_pool_supported(H, W, C, OH, OW, KH * KW * C, N))
+    return bool(conv_plan(1, H, W, C, OH, OW, N, KH, KW, stride, pad, -(-KH * KW * C // 32) * 32,
+                          pooled=True).get("pool", False))
 
 
 def conv_pool_fwd(x, w, bias, out, code, KH, KW, stride=1, pad=0, relu=True, drop=None):

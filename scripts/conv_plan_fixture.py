@@ -1,0 +1,166 @@
+"""Record tests/golden/conv_plan.json: the conv / dense launch decisions over a fixed shape list.
+
+    python scripts/conv_plan_fixture.py            # (re)record the query answers, keep recorded launches
+    python scripts/conv_plan_fixture.py --launches profiles/conv_plan/<table>.txt   # add the launch table
+
+The shape list is every Conv2D and Dense of lenet5, keras_cnn and resnet18_cifar at B in {1, 4, 32, 256,
+1024}, forward and data gradient, plus a hand list that reaches each branch of the dispatch at its
+smallest shape (``hand_list``; scripts/conv_plan_trace.py launches it under the profiler).  No GPU needed.
+
+The answers were recorded at the last commit that had the three separate shape-only queries
+(``igemm_bacc_supported``, ``igemm64_bn_tiles``, ``igemm64_pool_supported``), which is what makes them a
+reference for the planner that replaced them.  On a build without those bindings the script keeps every
+recorded answer (new entries get none) and only attaches launch tables.
+"""
+from __future__ import annotations
+
+import argparse
+import itertools
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, "tests", "golden", "conv_plan.json")
+BATCHES = (1, 4, 32, 256, 1024)
+BACC_VARIANTS = list(itertools.product((0, 1), (False, True), (False, True), (False, True)))  # mode two res mask
+
+
+def r32(v):
+    return -(-v // 32) * 32
+
+
+def conv(name, B, H, W, C, N, k, stride=1, pad=0, **flags):
+    """One conv; forward and data-gradient entries.  k / stride / pad: ints or (row, column) pairs."""
+    from distriflow_amd import ops
+    KH, KW = ops._pair(k)
+    OH, OW = ops.conv_out_hw(H, W, KH, KW, stride, pad)
+    if "out_hw" in flags:
+        OH, OW = flags.pop("out_hw")
+    c = dict(B=B, H=H, W=W, C=C, OH=OH, OW=OW, N=N, KH=KH, KW=KW, stride=stride, pad=pad)
+    fwd = dict(name=f"{name}/fwd", mode=1, M=B * OH * OW, N=N, K=KH * KW * C, Kpad=r32(KH * KW * C),
+               geom=ops._geom(H, W, C, OH, OW, KH, KW, stride, pad), conv=dict(c, Kpad=r32(KH * KW * C), dgrad=False))
+    bwd = dict(name=f"{name}/dgrad", mode=2, M=B * H * W, N=C, K=KH * KW * N, Kpad=r32(KH * KW * N),
+               geom=ops._geom(OH, OW, N, H, W, KH, KW, stride, pad), conv=dict(c, Kpad=r32(KH * KW * N), dgrad=True))
+    fwd.update(flags)
+    return [fwd, bwd]
+
+
+def dense(name, B, K, N, **flags):
+    """One dense layer: forward [B][K] -> [B][N] and data gradient [B][N] -> [B][K] (MODE_DIRECT)."""
+    fwd = dict(name=f"{name}/fwd", mode=0, M=B, N=N, K=K, Kpad=r32(K), lda=flags.pop("lda", K), geom=None, conv=None)
+    bwd = dict(name=f"{name}/dgrad", mode=0, M=B, N=K, K=N, Kpad=r32(N), lda=N, geom=None, conv=None)
+    fwd.update(flags)
+    return [fwd, bwd]
+
+
+def model_list():
+    es = []
+    for B in BATCHES:
+        t = f"lenet5/B{B}"
+        es += conv(f"{t}/conv2d_1", B, 28, 28, 1, 6, 5, 1, 2) + conv(f"{t}/conv2d_2", B, 14, 14, 6, 16, 5)
+        es += dense(f"{t}/dense_1", B, 400, 120) + dense(f"{t}/dense_2", B, 120, 84) + dense(f"{t}/dense_3", B, 84, 10)
+        t = f"keras_cnn/B{B}"
+        es += conv(f"{t}/conv2d_1", B, 28, 28, 1, 32, 3) + conv(f"{t}/conv2d_2", B, 26, 26, 32, 32, 3)
+        es += dense(f"{t}/dense_1", B, 4608, 128) + dense(f"{t}/dense_2", B, 128, 5)
+        t = f"resnet18_cifar/B{B}"
+        es += conv(f"{t}/stem", B, 32, 32, 3, 64, 3, 1, 1)
+        cin, hw = 64, 32
+        for stage, (f, s) in enumerate([(64, 1), (128, 2), (256, 2), (512, 2)]):
+            for b in range(2):
+                st = s if b == 0 else 1
+                n = f"{t}/layer{stage + 1}.{b}"
+                es += conv(f"{n}/conv1", B, hw, hw, cin, f, 3, st, 1)
+                if st != 1 or cin != f:
+                    es += conv(f"{n}/proj", B, hw, hw, cin, f, 1, st, 0)
+                hw //= st
+                es += conv(f"{n}/conv2", B, hw, hw, f, f, 3, 1, 1)
+                cin = f
+        es += dense(f"{t}/fc", B, 512, 10)
+    return es
+
+
+def hand_list():
+    """Each branch of the dispatch at its smallest shape."""
+    es = []
+    es += conv("halo_c64", 64, 32, 32, 64, 64, 3, 1, 1)                 # 512 tiles: weights-resident kernel
+    es += conv("halo_wide", 256, 16, 16, 128, 128, 3, 1, 1)             # 512 tiles x 1 channel tile of 128
+    es += conv("halo_narrow_row", 4, 16, 16, 64, 128, 3, 1, 1)          # 8 tiles: 64-channel tiles, a row per step
+    es += conv("halo_ks2_fold", 256, 4, 4, 512, 512, 3, 1, 1)           # 256 workgroups: 2 channel-block splits
+    es += conv("halo_ks2_big", 480, 4, 4, 512, 512, 3, 1, 1)            # 480 workgroups, still 2 splits
+    es += conv("igemm64_128x32", 4, 26, 26, 32, 32, 3)
+    es += conv("igemm64_128x64_slow", 4, 16, 16, 8, 64, 3, 1, 1)        # C = 8: no FAST gather
+    es += conv("igemm64_128x64_fast", 4, 16, 16, 64, 64, 3)             # pad 0: not the halo kernel
+    es += conv("igemm64_128x128", 64, 32, 32, 64, 128, 1)               # 512 tiles of 128 x 128
+    es += conv("igemm64_64x128", 4, 16, 16, 64, 128, 1)
+    es += conv("igemm64_split2", 256, 8, 8, 256, 512, 3, 2, 1)          # layer4.0 conv1: 256 tiles, 36 k steps
+    es += dense("igemm64_split4", 1024, 4608, 512)
+    es += dense("igemm64_split16", 32, 9216, 128)
+    es += conv("stride2_parity", 4, 16, 16, 64, 128, 3, 2, 1)           # dgrad gathers 128 channels: FAST, classes
+    es += conv("stride2_plain", 4, 16, 16, 16, 32, 3, 2, 1)             # dgrad gathers 32 channels: no FAST
+    es += conv("pooled", 4, 26, 26, 32, 32, 3, pooled=True)
+    es += conv("smallc_c1", 4, 28, 28, 1, 32, 3) + conv("smallc_c1_5x5", 4, 28, 28, 1, 8, 5, 1, 2)
+    es += conv("generic_c3", 4, 32, 32, 3, 64, 3, 1, 1)                 # C % 8 != 0: scalar gather
+    es += conv("generic_n16", 4, 14, 14, 6, 16, 5) + conv("generic_big_m", 1024, 8, 8, 3, 16, 1)
+    # the irregular geometries of test_irregular_conv_geometry_refuses_specialised_paths (generic, vectorised)
+    es += conv("irregular_same", 4, 16, 16, 64, 64, 3, 2, (0, 0), out_hw=(8, 8))
+    es += conv("irregular_stride", 4, 16, 16, 64, 64, 3, (2, 1), (1, 1))
+    es += conv("irregular_3x5", 4, 16, 16, 64, 64, (3, 5), 1, (1, 2))
+    es += dense("generic_dropout", 32, 84, 20, drop=True)               # K % 8 != 0: dropout as its own launch
+    es += dense("igemm64_dropout", 32, 128, 64, drop=True)              # folded into the epilogue
+    es += dense("direct_aligned", 32, 400, 120) + dense("direct_k_unaligned", 32, 84, 10)
+    es += dense("direct_lda_unaligned", 32, 120, 84, lda=124)
+    return [dict(e, hand=True) for e in es]
+
+
+def edge_list():
+    return conv("empty_batch", 0, 8, 8, 8, 8, 3, 1, 1)                  # M = 0: nothing to launch
+
+
+def record(e, m):
+    """The parent's answers: the three shape-only queries of the native extension."""
+    geom = e["geom"] if e["geom"] is not None else [1, 1, 1, 1, 1, 1, 1, 1, 0]
+    args = (e["M"], e["N"], e["K"], e["Kpad"], geom, e["mode"])
+    e["bacc"] = "".join("1" if m.igemm_bacc_supported(*args, bm, two, res, mask) else "0"
+                        for bm, two, res, mask in BACC_VARIANTS)
+    e["bn"] = [int(v) for v in m.igemm64_bn_tiles(*args)]
+    c = e["conv"]
+    if e["mode"] == 1 and c["KH"] == c["KW"] and isinstance(c["stride"], int) and isinstance(c["pad"], int):
+        from distriflow_amd import ops  # (the pool query knows regular geometries only: Net asks it for no other)
+        e["pool"] = bool(ops.conv_pool_supported(c["H"], c["W"], c["C"], c["KH"], c["KW"], c["stride"], c["pad"], e["N"]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launches", help="reduced launch table (scripts/conv_plan_trace.py --reduce) to attach")
+    a = ap.parse_args()
+    from distriflow_amd import native
+    m = native.get(build_if_missing=False)
+    entries = model_list() + hand_list() + edge_list()
+    old = {}
+    if os.path.exists(OUT):
+        with open(OUT) as f:
+            old = {e["name"]: e for e in json.load(f)["entries"]}
+    for e in entries:
+        if hasattr(m, "igemm_bacc_supported"):
+            record(e, m)
+        else:  # the three queries are gone: keep what was recorded
+            for k in ("bacc", "bn", "pool"):
+                if k in old.get(e["name"], {}):
+                    e[k] = old[e["name"]][k]
+        if "launch" in old.get(e["name"], {}):
+            e["launch"] = old[e["name"]]["launch"]
+    if a.launches:
+        from conv_plan_trace import read_table
+        for name, rows in read_table(a.launches).items():
+            next(e for e in entries if e["name"] == name)["launch"] = rows
+    with open(OUT, "w") as f:
+        f.write('{"bacc_variants": "bacc_mode two has_res has_mask, in itertools.product order",\n "entries": [\n')
+        f.write(",\n".join("  " + json.dumps(e) for e in entries))
+        f.write("\n]}\n")
+    print(f"{len(entries)} entries -> {OUT}")
+
+
+if __name__ == "__main__":
+    main()

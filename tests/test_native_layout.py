@@ -1,10 +1,14 @@
 """Host-side launch layouts of the native extension that need no GPU: the LeNet-5 images-per-workgroup
 policy (csrc/lenet_fused.hip lenet_ipw / lenet_blocks), the irregular-geometry routing of the conv
 dispatch (csrc/bindings_util.h set_conv_geom: only the generic implicit GEMM takes it), the parameter
-server's buffer layout (csrc/ps_layout.h) and the dense head's error-word offset (csrc/khead.hip)."""
+server's buffer layout (csrc/ps_layout.h), the dense head's error-word offset (csrc/khead.hip) and the
+launch plan of the forward / data-gradient implicit GEMMs (csrc/conv_plan.hip)."""
+import itertools
+import json
 import os
 import shutil
 import subprocess
+import sys
 
 import pytest
 
@@ -62,3 +66,112 @@ def test_irregular_conv_geometry_refuses_specialised_paths():
     assert not ok(3, 3, (2, 1), (1, 1), 8, 16, True)
     assert not ok(3, 5, 1, (1, 2), 16, 16, True)
     assert ok(3, 5, 1, (1, 2), 16, 16, False)            # generic forward: epilogue sums, mode 0
+
+
+# ---------------------------------------------------------------------------- conv launch plan
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plan.json")
+BACC_VARIANTS = list(itertools.product((0, 1), (False, True), (False, True), (False, True)))  # mode two res mask
+FAMILY_OF_KERNEL = {"conv3_halo_c64_kernel": "halo_c64", "conv3_halo_kernel": "halo", "igemm64_kernel": "igemm64",
+                    "c1_fwd_kernel": "smallc", "smallc_fwd_kernel": "smallc", "igemm_fwd_kernel": "generic"}
+
+
+def _plan_args(e):
+    geom = e["geom"] if e["geom"] is not None else [1, 1, 1, 1, 1, 1, 1, 1, 0]
+    return (e["M"], e["N"], e["K"], e["Kpad"], geom, e["mode"]), dict(lda=e.get("lda", 0))
+
+
+def _check_launch(e, p):
+    """The plan against the kernels the parent launched for this entry (name<template flags>, workgroups,
+    workgroup size, LDS bytes; profiles/conv_plan/launches_parent.txt)."""
+    rows = e["launch"]
+    kern, grid, block, _ = rows[0]
+    name, _, targs = kern.partition("<")
+    t = [{"true": True, "false": False}.get(v, v) for v in targs.rstrip(">").split(",")] if targs else []
+    assert p["family"] == FAMILY_OF_KERNEL[name], e["name"]
+    if p["family"] == "igemm64":
+        want = dict(BM=int(t[0]), BN=int(t[1]), fast=t[6], par=t[7], pool=t[5])
+        assert int(t[2]) == e["mode"] and (p["splits"] > 1) == t[4], e["name"]
+    elif p["family"] == "halo":
+        want = dict(BN=int(t[0]), wide=int(t[0]) == 128, row=t[2])
+        assert t[1] == (e["mode"] == 2), e["name"]
+    elif p["family"] == "generic":
+        want = dict(BM=int(t[0]), BN=int(t[1]), vec=t[5])
+        assert int(t[4]) == e["mode"], e["name"]
+    else:
+        want = {}
+    assert {k: p[k] for k in want} == want, e["name"]
+    if p["family"] != "smallc":  # (the C = 1 kernels size their own launch)
+        assert (p["grid"], p["block"]) == (grid, block), e["name"]
+    followers = [r[0] for r in rows[1:]]
+    assert followers == ["igemm64_splitk_epilogue_kernel"] * p["combine"] + ["dropout_kernel"] * p["drop_after"], e["name"]
+
+
+@needs_ext
+def test_conv_plan_matches_recorded_decisions():
+    """Over every Conv2D / Dense of lenet5, keras_cnn and resnet18_cifar at five batch sizes and a hand list
+    that reaches each branch of the dispatch (scripts/conv_plan_fixture.py), the queries answer what the three
+    separate query bindings answered before the planner existed (tests/golden/conv_plan.json: BatchNorm sums
+    in 16 variants, BatchNorm tiles, pooling), and the plan names the kernels, template flags and grids the
+    parent build launched on the GPU for the hand list.  The list keeps reaching every family and both values of
+    every variant flag."""
+    with open(GOLDEN) as f:
+        entries = json.load(f)["entries"]
+    families, flags, launches, base = set(), {}, 0, []
+    for e in entries:
+        args, kw = _plan_args(e)
+        p = m.conv_plan(*args, pooled=bool(e.get("pooled")), drop=bool(e.get("drop")), **kw)
+        plans = [p]
+        base.append(p)
+        for i, (bm, two, res, mask) in enumerate(BACC_VARIANTS):
+            q = m.conv_plan(*args, bacc_mode=bm, two=two, has_res=res, has_mask=mask, **kw)
+            assert q["bacc_ok"] == (e["bacc"][i] == "1"), (e["name"], i)
+            assert (q["family"] == "invalid") == (not q["bacc_ok"] and e["M"] > 0), (e["name"], i)
+            plans.append(q)
+        assert [m.conv_plan(*args, **kw)[k] for k in ("bn_ntm", "bn_ntn")] == e["bn"], e["name"]
+        c = e["conv"]
+        if c is not None:  # the ops wrappers, as the layers call them
+            g = (c["B"], c["H"], c["W"], c["C"], c["OH"], c["OW"], c["N"], c["KH"], c["KW"], c["stride"], c["pad"], c["Kpad"])
+            got = "".join("01"[ops.conv_bacc_ok(*g, dgrad=c["dgrad"], mode=bm, two=two, has_res=res, has_mask=mask)]
+                          for bm, two, res, mask in BACC_VARIANTS)
+            assert got == e["bacc"], e["name"]
+            assert list(ops.conv_bn_layout(*g, dgrad=c["dgrad"])) == e["bn"], e["name"]
+            if "pool" in e:
+                assert ops.conv_pool_supported(c["H"], c["W"], c["C"], c["KH"], c["KW"], c["stride"], c["pad"],
+                                               c["N"]) == e["pool"], e["name"]
+        if "launch" in e:
+            _check_launch(e, p)
+            launches += 1
+        for q in plans:
+            families.add(q["family"])
+            for k in ("fast", "par", "pool", "wide", "row", "fold", "vec", "combine", "drop_after", "bacc_ok"):
+                flags.setdefault(k, set()).add(q[k])
+            flags.setdefault("split", set()).add(q["splits"] > 1)
+            flags.setdefault("ks", set()).add(q["ks"] > 1)
+            flags.setdefault("scratch", set()).add(q["splitk_floats"] > 0)
+            flags.setdefault("bn", set()).add(q["bn_ntm"] > 0)
+    assert families == {"nop", "invalid", "halo_c64", "halo", "igemm64", "smallc", "generic"}
+    assert all(v == {False, True} for v in flags.values()), flags
+    assert {q["splits"] for q in base} >= {1, 2, 4, 16}
+    assert {(q["BM"], q["BN"]) for q in base if q["family"] == "igemm64"} == {(128, 32), (128, 64), (128, 128), (64, 128)}
+    assert launches == 58
+
+
+@needs_ext
+def test_conv_plan_reads_the_diagnostic_switches():
+    """DISTRIFLOW_DIAG is read once per process, so a child: with conv_halo=0 a 3x3 / stride 1 / pad 1 conv of
+    512 channels (a halo shape, two channel-block splits by default) plans as igemm64, and igemm_splitk=0
+    leaves it without split-K scratch."""
+    code = ("from distriflow_amd import ops\n"
+            "p = ops.conv_plan(256, 4, 4, 512, 4, 4, 512, 3, 3, 1, 1, 4608)\n"
+            "print(p['family'], p['splits'], p['splitk_floats'])\n")
+    root = os.path.dirname(CSRC)
+
+    def run(diag):
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=root,
+                           env=dict(os.environ, DISTRIFLOW_DIAG=diag))
+        assert r.returncode == 0, r.stderr
+        return r.stdout.split()
+
+    assert m.conv_plan(4096, 512, 4608, 4608, [4, 4, 512, 4, 4, 3, 3, 1, 1], 1)["family"] == "halo"
+    assert run("conv_halo=0") == ["igemm64", "4", str(4 * 4096 * 512)]
+    assert run("conv_halo=0,igemm_splitk=0") == ["igemm64", "1", "0"]
