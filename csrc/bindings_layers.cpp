@@ -419,6 +419,71 @@ void pool2d_bwd_py(torch::Tensor x, torch::Tensor dy, torch::Tensor dx, std::vec
             "pool2d_bwd");
 }
 
+// ---- depthwise convolution (csrc/dwconv.hip)
+static dfa::DwConvGeom dw_geom(const std::vector<int64_t>& g) {
+  TORCH_CHECK(g.size() == 13, "dwconv: geom = [B, H, W, C, M, OH, OW, KH, KW, sh, sw, pt, pl]");
+  for (int64_t v : g) TORCH_CHECK(v >= 0 && v < (1LL << 30), "dwconv: bad geometry");
+  dfa::DwConvGeom p{};
+  p.B = (int)g[0]; p.H = (int)g[1]; p.W = (int)g[2]; p.C = (int)g[3]; p.M = (int)g[4]; p.OH = (int)g[5];
+  p.OW = (int)g[6]; p.KH = (int)g[7]; p.KW = (int)g[8]; p.sh = (int)g[9]; p.sw = (int)g[10]; p.pt = (int)g[11];
+  p.pl = (int)g[12];
+  TORCH_CHECK(p.B > 0 && p.H > 0 && p.W > 0 && p.C > 0 && p.M > 0 && p.OH > 0 && p.OW > 0 && p.KH > 0 && p.KW > 0 &&
+                  p.sh > 0 && p.sw > 0 && p.pt < p.KH && p.pl < p.KW,
+              "dwconv: bad geometry");
+  // every window starts inside the padded image
+  TORCH_CHECK((int64_t)(p.OH - 1) * p.sh - p.pt < p.H && (int64_t)(p.OW - 1) * p.sw - p.pl < p.W,
+              "dwconv: output too large");
+  return p;
+}
+
+static void dw_sizes(const dfa::DwConvGeom& g, const torch::Tensor& x, const torch::Tensor& y, const torch::Tensor& w) {
+  const int64_t CO = (int64_t)g.C * g.M;
+  TORCH_CHECK(x.numel() == (int64_t)g.B * g.H * g.W * g.C && y.numel() == (int64_t)g.B * g.OH * g.OW * CO &&
+                  w.numel() == (int64_t)g.KH * g.KW * CO,
+              "dwconv: tensor sizes do not match the geometry");
+}
+
+void dwconv_fwd_py(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor y,
+                   std::vector<int64_t> geom, bool relu) {
+  const dfa::DwConvGeom g = dw_geom(geom);
+  need(x, at::kBFloat16, "dwconv x");
+  need(w, at::kFloat, "dwconv kernel");
+  need(y, at::kBFloat16, "dwconv y");
+  dw_sizes(g, x, y, w);
+  const float* bp = opt_ptr<const float>(bias, at::kFloat, "dwconv bias", (int64_t)g.C * g.M, "dwconv bias too small");
+  check_hip(dfa::dwconv_fwd((const dfa::bf16*)x.data_ptr(), w.data_ptr<float>(), bp, (dfa::bf16*)y.data_ptr(), g,
+                            relu ? 1 : 0, cur_stream()),
+            "dwconv_fwd");
+}
+
+void dwconv_dgrad_py(torch::Tensor dy, torch::Tensor w, c10::optional<torch::Tensor> mask, torch::Tensor dx,
+                     std::vector<int64_t> geom) {
+  const dfa::DwConvGeom g = dw_geom(geom);
+  need(dy, at::kBFloat16, "dwconv dy");
+  need(w, at::kFloat, "dwconv kernel");
+  need(dx, at::kBFloat16, "dwconv dx");
+  dw_sizes(g, dx, dy, w);
+  const dfa::bf16* mp = opt_ptr<const dfa::bf16>(mask, at::kBFloat16, "dwconv mask", dx.numel(), "dwconv mask too small");
+  check_hip(dfa::dwconv_dgrad((const dfa::bf16*)dy.data_ptr(), w.data_ptr<float>(), mp, (dfa::bf16*)dx.data_ptr(), g,
+                              cur_stream()),
+            "dwconv_dgrad");
+}
+
+void dwconv_wgrad_py(torch::Tensor dy, torch::Tensor x, torch::Tensor gw, c10::optional<torch::Tensor> gb,
+                     torch::Tensor ws, std::vector<int64_t> geom) {
+  const dfa::DwConvGeom g = dw_geom(geom);
+  need(dy, at::kBFloat16, "dwconv dy");
+  need(x, at::kBFloat16, "dwconv x");
+  need(gw, at::kFloat, "dwconv kernel gradient");
+  need(ws, at::kFloat, "dwconv workspace");
+  dw_sizes(g, x, dy, gw);
+  float* gbp = opt_ptr<float>(gb, at::kFloat, "dwconv bias gradient", (int64_t)g.C * g.M, "dwconv bias gradient too small");
+  TORCH_CHECK(ws.numel() >= dfa::dwconv_wgrad_slab_floats(g), "dwconv_wgrad: the workspace does not hold one slab");
+  check_hip(dfa::dwconv_wgrad((const dfa::bf16*)dy.data_ptr(), (const dfa::bf16*)x.data_ptr(), gw.data_ptr<float>(), gbp,
+                              ws.data_ptr<float>(), (size_t)ws.numel(), g, cur_stream()),
+            "dwconv_wgrad");
+}
+
 void gap_fwd_py(torch::Tensor x, torch::Tensor y, int64_t B, int64_t HW, int64_t C) {
   need(x, at::kBFloat16, "x");
   need(y, at::kBFloat16, "y");
@@ -962,6 +1027,9 @@ void bind_layers(py::module_& m) {
   m.def("sigmoid_ce", &sigmoid_ce_py, "sigmoid cross-entropy on logits vs one-hot labels (+ dlogits)");
   m.def("pool2d_fwd", &pool2d_fwd_py, "general 2-D max / average pooling, any window / stride / padding");
   m.def("pool2d_bwd", &pool2d_bwd_py, "backward of pool2d_fwd (input-centric, no atomics)");
+  m.def("dwconv_fwd", &dwconv_fwd_py, "depthwise conv forward, fp32 kernel [KH][KW][C*M] (csrc/dwconv.hip)");
+  m.def("dwconv_dgrad", &dwconv_dgrad_py, "depthwise conv data gradient [* relu'(mask)]");
+  m.def("dwconv_wgrad", &dwconv_wgrad_py, "depthwise conv weight / bias gradient (fixed-order slab sums)");
   m.def("gather_labels", &gather_labels_py);
   m.def("bn_finalize_partials", [](torch::Tensor part, int64_t ntm, int64_t C, int64_t M, torch::Tensor mean,
                                    torch::Tensor invstd, c10::optional<torch::Tensor> run_mean,

@@ -743,6 +743,24 @@ hipError_t pool2d_fwd(const bf16* x, bf16* y, const Pool2DGeom& g, int avg, hipS
 hipError_t pool2d_bwd(const bf16* x, const bf16* dy, bf16* dx, const Pool2DGeom& g, int avg, int in_relu,
                       hipStream_t st);
 
+// Depthwise convolution (csrc/dwconv.hip): NHWC bf16 activations, fp32 kernel [KH][KW][C*M] read from the
+// master (Keras depthwise_kernel [KH, KW, C, M] flattened); output channel co reads input channel co / M.
+struct DwConvGeom {
+  int B, H, W, C, M, OH, OW;
+  int KH, KW, sh, sw, pt, pl;  // kernel, strides, top / left padding (bottom / right: what the output implies)
+};
+// y = [relu](bias + sum over taps x * w)
+hipError_t dwconv_fwd(const bf16* x, const float* w, const float* bias, bf16* y, const DwConvGeom& g, int relu,
+                      hipStream_t st);
+// dx = [mask > 0] * sum over the taps and output positions that read the pixel, and the M outputs of its channel
+hipError_t dwconv_dgrad(const bf16* dy, const float* w, const bf16* mask, bf16* dx, const DwConvGeom& g,
+                        hipStream_t st);
+// gw [KH][KW][C*M] = sum over (b, oh, ow) of dy * x, gb [C*M] = sum dy (nullable): fp32, fixed summation order
+// (per-workgroup slabs of dwconv_wgrad_slab_floats(g) floats in ws, at least one must fit, then a sum launch)
+long long dwconv_wgrad_slab_floats(const DwConvGeom& g);
+hipError_t dwconv_wgrad(const bf16* dy, const bf16* x, float* gw, float* gb, float* ws, size_t ws_floats,
+                        const DwConvGeom& g, hipStream_t st);
+
 // Direct convolution for C_in <= 4 (csrc/smallc.hip); igemm_fwd / igemm_wgrad dispatch to it.
 bool smallc_fwd_supported(const IGemmArgs& a, int mode);
 hipError_t smallc_fwd(const IGemmArgs& a, hipStream_t st);

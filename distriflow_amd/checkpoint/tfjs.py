@@ -9,7 +9,9 @@ What the reference saves with ``model.save('file://<dir>')`` / loads with ``tf.l
   weights.bin = little-endian float32 values of every weight, concatenated in manifest order.
 
 Keras layouts are converted at this boundary only: Conv2D kernel HWIO [kh][kw][cin][cout] <-> engine
-OHWI [cout][kh][kw][cin]; Dense kernel [in][out] <-> engine [out][in]; BatchNormalization
+OHWI [cout][kh][kw][cin] (a SeparableConv2D's ``pointwise_kernel`` likewise; a ``depthwise_kernel``
+[kh][kw][cin][multiplier] is the engine's [kh][kw][cin*multiplier] reshaped, no permutation); Dense kernel
+[in][out] <-> engine [out][in]; BatchNormalization
 gamma/beta(/moving_mean/moving_variance).  Weights are always stored fp32 on disk even when training
 runs in bf16.  Multi-shard manifests (``group1-shard1of1`` ... as in model.json:1) are read too.
 """
@@ -23,16 +25,23 @@ import numpy as np
 import torch
 
 from ..models.keras import keras_config_from_layers
-from ..models.layers import BatchNorm, Conv2D, ConvPoolGemm, Dense, FusedConvPool, KerasConvBlock, ResidualBlock
+from ..models.layers import (BatchNorm, Conv2D, ConvPoolGemm, Dense, DepthwiseConv2D, FusedConvPool, KerasConvBlock,
+                             ResidualBlock)
 
 FORMAT = "layers-model"
 GENERATED_BY = "distriflow_amd"
 
 
+_CONV_KERNELS = ("/kernel", "/pointwise_kernel")  # HWIO on disk, OHWI in the engine
+
+
 def _engine_to_keras(spec_name: str, value: torch.Tensor, layer) -> np.ndarray:
     v = value.detach().float().cpu()
     conv = isinstance(layer, (Conv2D, FusedConvPool, ConvPoolGemm, KerasConvBlock))
-    if spec_name.endswith("/kernel") and conv:
+    if spec_name.endswith("/depthwise_kernel") and isinstance(layer, DepthwiseConv2D):
+        # engine [KH][KW][C*M] is Keras [KH, KW, C, M] flattened: a reshape, no permutation
+        return v.reshape(layer.kh, layer.kw, layer.in_shape[2], layer.depth_multiplier).contiguous().numpy()
+    if spec_name.endswith(_CONV_KERNELS) and conv:
         return v.permute(1, 2, 3, 0).contiguous().numpy()          # OHWI -> HWIO
     if spec_name.endswith("/kernel") and isinstance(layer, Dense):
         return v.t().contiguous().numpy()                          # [out][in] -> [in][out]
@@ -42,7 +51,7 @@ def _engine_to_keras(spec_name: str, value: torch.Tensor, layer) -> np.ndarray:
 def _keras_to_engine(spec_name: str, arr: np.ndarray, layer, engine_shape) -> torch.Tensor:
     t = torch.from_numpy(np.ascontiguousarray(arr)).float()
     conv = isinstance(layer, (Conv2D, FusedConvPool, ConvPoolGemm, KerasConvBlock))
-    if spec_name.endswith("/kernel") and conv:
+    if spec_name.endswith(_CONV_KERNELS) and conv:
         t = t.permute(3, 0, 1, 2)                                  # HWIO -> OHWI
     elif spec_name.endswith("/kernel") and isinstance(layer, Dense):
         t = t.t()
@@ -52,14 +61,20 @@ def _keras_to_engine(spec_name: str, arr: np.ndarray, layer, engine_shape) -> to
 def _weight_layers(net):
     """[(spec_name, layer)] in parameter order, plus BN moving statistics entries."""
     out = []
+
+    def walk(l):
+        if hasattr(l, "sublayers"):  # composites, possibly nested (a SeparableConv2D inside a graph)
+            for s in l.sublayers():
+                walk(s)
+            return
+        for spec in l.specs():
+            out.append((spec.name, l))
+        if isinstance(l, BatchNorm):
+            out.append((f"{l.name}/moving_mean", l))
+            out.append((f"{l.name}/moving_variance", l))
+
     for l in net.exec_layers:
-        subs = l.sublayers() if hasattr(l, "sublayers") else [l]
-        for s in subs:
-            for spec in s.specs():
-                out.append((spec.name, s))
-            if isinstance(s, BatchNorm):
-                out.append((f"{s.name}/moving_mean", s))
-                out.append((f"{s.name}/moving_variance", s))
+        walk(l)
     return out
 
 

@@ -100,7 +100,10 @@ class GraphLayer(Layer):
     def bind_store(self, store):
         self.store = store
         for l in self.sublayers():
-            l.store = store
+            if hasattr(l, "bind_store"):  # a composite node (SeparableConv2D) hands it to its stages
+                l.bind_store(store)
+            else:
+                l.store = store
 
     def specs(self):
         out = []

@@ -11,16 +11,18 @@ Keras 2.1.4 Sequential (/root/reference/experiment/mnist/model.json:1).  Support
   branching region runs as one :class:`~distriflow_amd.models.graph.GraphLayer`, models/graph.py);
   the logits layer (the output) must be a Dense fed by a single chain;
 * InputLayer, Conv2D (any kernel size / strides pair, 'valid' or 'same' -- an odd 'same' total pads the
-  bottom / right, as TensorFlow does), Dense, Activation (relu, relu6, sigmoid, tanh, elu, selu, softplus, softsign,
-  hard_sigmoid, swish / silu, exponential, linear; softmax / sigmoid as the output), MaxPooling2D and
+  bottom / right, as TensorFlow does), DepthwiseConv2D and SeparableConv2D (same geometries, any
+  depth_multiplier; no dilation), Dense, Activation (relu, relu6, sigmoid, tanh, elu, selu, softplus, softsign,
+  hard_sigmoid, swish / silu, exponential, linear; softmax / sigmoid as the output), the ReLU layer class
+  (max_value None or 6, no negative_slope / threshold), MaxPooling2D and
   AveragePooling2D (any pool / strides, 'valid' or 'same'), GlobalAveragePooling2D,
   GlobalMaxPooling2D, Dropout, Flatten, BatchNormalization — channels_last only.
 """
 from __future__ import annotations
 
 from .graph import GraphLayer, Merge, split_chain
-from .layers import (Activation, AveragePooling2D, BatchNorm, Conv2D, Dense, Dropout, Flatten,
-                     GlobalAveragePooling2D, GlobalMaxPooling2D, Layer, MaxPooling2D)
+from .layers import (Activation, AveragePooling2D, BatchNorm, Conv2D, Dense, DepthwiseConv2D, Dropout, Flatten,
+                     GlobalAveragePooling2D, GlobalMaxPooling2D, Layer, MaxPooling2D, SeparableConv2D)
 
 _MERGES = ("Add", "Subtract", "Multiply", "Average", "Maximum", "Minimum", "Concatenate")
 
@@ -71,8 +73,12 @@ def _graph_order(layer_cfgs: list, model_cfg: dict) -> tuple:
     return [by_name[n] for n in order], parents
 
 
-def _init_name(cfg):
-    ki = cfg.get("kernel_initializer") or {}
+def _pair(v) -> tuple:
+    return (int(v[0]), int(v[1])) if isinstance(v, (list, tuple)) else (int(v), int(v))
+
+
+def _init_name(cfg, key: str = "kernel_initializer"):
+    ki = cfg.get(key) or {}
     cls = ki.get("class_name", "VarianceScaling") if isinstance(ki, dict) else str(ki)
     c = ki.get("config", {}) if isinstance(ki, dict) else {}
     if cls in ("GlorotUniform", "glorot_uniform"):
@@ -101,11 +107,33 @@ def _make_layer(k: str, c: dict) -> Layer:
         return Conv2D(c["filters"], tuple(c["kernel_size"]), tuple(c.get("strides", [1, 1])), c.get("padding", "valid"),
                       c.get("activation", "linear"), c.get("use_bias", True), name=name,
                       kernel_initializer=_init_name(c))
+    if k in ("DepthwiseConv2D", "SeparableConv2D"):
+        if _pair(c.get("dilation_rate", [1, 1])) != (1, 1):
+            raise NotImplementedError(f"dilated {k}")
+        geom = (_pair(c["kernel_size"]), _pair(c.get("strides", [1, 1])), c.get("padding", "valid"),
+                int(c.get("depth_multiplier", 1)), c.get("activation", "linear"), c.get("use_bias", True))
+        dinit = _init_name(c, "depthwise_initializer")
+        if k == "DepthwiseConv2D":
+            return DepthwiseConv2D(*geom, name=name, depthwise_initializer=dinit)
+        return SeparableConv2D(c["filters"], *geom, name=name, depthwise_initializer=dinit,
+                               pointwise_initializer=_init_name(c, "pointwise_initializer"))
     if k == "Dense":
         return Dense(c["units"], c.get("activation", "linear"), c.get("use_bias", True), name=name,
                      kernel_initializer=_init_name(c))
     if k == "Activation":
         return Activation(c["activation"], name=name)
+    if k == "ReLU":
+        # the layer class MobileNet-style models use for relu6; only the two plain forms are implemented
+        if float(c.get("negative_slope") or 0.0) != 0.0:
+            raise NotImplementedError(f"ReLU layer {name!r}: negative_slope {c['negative_slope']!r}")
+        if float(c.get("threshold") or 0.0) != 0.0:
+            raise NotImplementedError(f"ReLU layer {name!r}: threshold {c['threshold']!r}")
+        mv = c.get("max_value")
+        if mv is None:
+            return Activation("relu", name=name)
+        if float(mv) == 6.0:
+            return Activation("relu6", name=name)
+        raise NotImplementedError(f"ReLU layer {name!r}: max_value {mv!r} (supported: None, 6)")
     if k in ("MaxPooling2D", "AveragePooling2D"):
         cls_ = MaxPooling2D if k == "MaxPooling2D" else AveragePooling2D
         return cls_(tuple(c.get("pool_size", [2, 2])), c.get("strides"), c.get("padding", "valid"), name=name)
@@ -159,7 +187,8 @@ def _graph_layers(order: list, parents: dict) -> tuple:
     out, newid = [], {0: 0}
     for j, (l, ins) in enumerate(mid, start=1):
         out.append((l, [newid[i] for i in ins]))
-        act = getattr(l, "activation", None) if isinstance(l, (Dense, Conv2D)) else None
+        act = getattr(l, "activation", None) if isinstance(l, (Dense, Conv2D, DepthwiseConv2D,
+                                                               SeparableConv2D)) else None
         if act not in (None, "linear", "relu"):
             if act == "softmax":
                 raise NotImplementedError("a softmax activation inside a branching region")
@@ -244,6 +273,15 @@ def keras_config_from_layers(layers: list[Layer], input_shape: tuple, name: str 
                                              "config": {"scale": 1.0, "mode": "fan_avg", "distribution": "uniform",
                                                         "seed": None}},
                       "bias_initializer": {"class_name": "Zeros", "config": {}}})
+        elif isinstance(l, (DepthwiseConv2D, SeparableConv2D)):
+            cls = type(l).__name__
+            glorot = {"class_name": "VarianceScaling",
+                      "config": {"scale": 1.0, "mode": "fan_avg", "distribution": "uniform", "seed": None}}
+            c.update(l.config())
+            c.update({"data_format": "channels_last", "dilation_rate": [1, 1], "depthwise_initializer": glorot,
+                      "bias_initializer": {"class_name": "Zeros", "config": {}}})
+            if isinstance(l, SeparableConv2D):
+                c["pointwise_initializer"] = glorot
         elif isinstance(l, Dense):
             cls = "Dense"
             c.update(l.config())

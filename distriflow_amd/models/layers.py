@@ -195,6 +195,15 @@ class Conv2D(Layer):
         elif activation not in ops.ACT_KINDS:
             raise NotImplementedError(f"Conv2D activation {activation!r}")
 
+    # parameter names (the pointwise stage of a SeparableConv2D carries Keras' names for it)
+    @property
+    def kernel_name(self) -> str:
+        return f"{self.name}/kernel"
+
+    @property
+    def bias_name(self) -> str:
+        return f"{self.name}/bias"
+
     def build(self, in_shape):
         H, W, C = in_shape
         self.in_shape = (H, W, C)
@@ -225,11 +234,11 @@ class Conv2D(Layer):
         H, W, C = self.in_shape
         K = self.kh * self.kw * C
         fan_in, fan_out = K, self.kh * self.kw * self.filters
-        s = [ParamSpec(f"{self.name}/kernel", (self.filters, self.kh, self.kw, C), "matrix",
+        s = [ParamSpec(self.kernel_name, (self.filters, self.kh, self.kw, C), "matrix",
                        (self.filters, self.kh * self.kw, C), self.kernel_initializer, (fan_in, fan_out),
                        needs_dgrad=self.need_dx)]
         if self.use_bias:
-            s.append(ParamSpec(f"{self.name}/bias", (self.filters,), "vector", init="zeros"))
+            s.append(ParamSpec(self.bias_name, (self.filters,), "vector", init="zeros"))
         return s
 
     fwd_bn = None  # the BatchNorm that consumes this conv's output in a layer chain (Net._plan)
@@ -279,7 +288,7 @@ class Conv2D(Layer):
         default) or finalises them (``bn_epilogue`` diagnostic) -- no statistics pass over the output."""
         self.x = x
         st = self.store
-        b = st[f"{self.name}/bias"] if self.use_bias else None
+        b = st[self.bias_name] if self.use_bias else None
         bn = bn if bn is not None else self.fwd_bn
         spec = bacc = None
         if bn is not None and training and self._bn_fwd is not None:
@@ -288,7 +297,7 @@ class Conv2D(Layer):
                         momentum=bn.momentum, eps=bn.eps)
         elif bn is not None and training and bn.acc_on and self.bacc_ok(False, 0):
             bacc = dict(acc=bn.acc, mode=0)
-        ops.conv_fwd(x, st.weight(f"{self.name}/kernel"), b, self.out, *self.geom, relu=self.relu, bn=spec,
+        ops.conv_fwd(x, st.weight(self.kernel_name), b, self.out, *self.geom, relu=self.relu, bn=spec,
                      bacc=bacc)
         if spec is not None:
             bn.x = self.out
@@ -310,8 +319,8 @@ class Conv2D(Layer):
 
     def backward_weights(self, dy):
         st = self.store
-        kn = f"{self.name}/kernel"
-        gb = st.gradient(f"{self.name}/bias") if self.use_bias else None
+        kn = self.kernel_name
+        gb = st.gradient(self.bias_name) if self.use_bias else None
         ops.conv_wgrad(dy, self.x, st.grad_matrix(kn), gb, self.ws.wgrad, *self.geom)
 
     def backward_data(self, dy, residual=None, residual_mask=None, dx_mask=None, bn: Optional["BatchNorm"] = None,
@@ -323,7 +332,7 @@ class Conv2D(Layer):
         if not self.need_dx:
             return None
         st = self.store
-        kn = f"{self.name}/kernel"
+        kn = self.kernel_name
         mask = dx_mask if dx_mask is not None else (self.x if self.in_relu else None)
         spec = bacc = None
         if bn is not None:
@@ -350,6 +359,175 @@ class Conv2D(Layer):
         return {"filters": self.filters, "kernel_size": [self.kh, self.kw], "strides": [self.sh, self.sw],
                 "padding": self.padding if isinstance(self.padding, str) else "valid",
                 "activation": self.activation, "use_bias": self.use_bias}
+
+
+class DepthwiseConv2D(Layer):
+    """Keras DepthwiseConv2D: every input channel convolved with its own ``depth_multiplier`` filters (output
+    channel co reads input channel co // depth_multiplier).  Any kernel size / strides pair, 'valid' or
+    'same' (the odd pixel of padding goes bottom / right).  The kernel is stored [KH][KW][C*M] -- Keras'
+    ``depthwise_kernel`` [KH, KW, C, M] flattened -- as a flat fp32 parameter the kernels read straight from
+    the master (csrc/dwconv.hip): it is a few tens of KB, so there is no bf16 compute copy."""
+    has_params = True
+
+    def __init__(self, kernel_size=(3, 3), strides=(1, 1), padding="valid", depth_multiplier=1, activation="linear",
+                 use_bias=True, name=None, depthwise_initializer="glorot_uniform"):
+        super().__init__(name or "depthwise_conv2d")
+        self.kh, self.kw = ops._pair(kernel_size)
+        self.sh, self.sw = ops._pair(strides)
+        if padding not in ("valid", "same"):
+            raise NotImplementedError(f"DepthwiseConv2D padding {padding!r}")
+        self.padding = padding
+        self.depth_multiplier = int(depth_multiplier)
+        if self.depth_multiplier < 1:
+            raise ValueError("depth_multiplier must be >= 1")
+        self.activation = activation
+        self.use_bias = use_bias
+        self.depthwise_initializer = depthwise_initializer
+        if activation == "relu":
+            self.relu = True
+        elif activation not in ops.ACT_KINDS:
+            raise NotImplementedError(f"DepthwiseConv2D activation {activation!r}")
+
+    @property
+    def kernel_name(self) -> str:
+        return f"{self.name}/depthwise_kernel"
+
+    @property
+    def bias_name(self) -> str:
+        return f"{self.name}/bias"
+
+    def build(self, in_shape):
+        H, W, C = in_shape
+        self.in_shape = (H, W, C)
+        g = ops.dwconv_geometry(1, H, W, C, self.depth_multiplier, (self.kh, self.kw), (self.sh, self.sw), self.padding)
+        self.out_shape = (g[5], g[6], C * self.depth_multiplier)
+        return self.out_shape
+
+    def _geom(self, B):
+        H, W, C = self.in_shape
+        return ops.dwconv_geometry(B, H, W, C, self.depth_multiplier, (self.kh, self.kw), (self.sh, self.sw),
+                                   self.padding)
+
+    def can_fuse_relu(self):
+        return True
+
+    def specs(self):
+        CO, M = self.out_shape[2], self.depth_multiplier
+        taps = self.kh * self.kw
+        s = [ParamSpec(self.kernel_name, (self.kh, self.kw, CO), "vector", init=self.depthwise_initializer,
+                       fan=(taps, taps * M))]
+        if self.use_bias:
+            s.append(ParamSpec(self.bias_name, (CO,), "vector", init="zeros"))
+        return s
+
+    def alloc(self, B, device, dtype, ws):
+        super().alloc(B, device, dtype, ws)
+        self.ws = ws
+
+    def forward(self, x, training):
+        self.x = x
+        st = self.store
+        b = st[self.bias_name] if self.use_bias else None
+        ops.dwconv_fwd(x, st[self.kernel_name], b, self.out, self._geom(x.shape[0]), relu=self.relu)
+        return self.out
+
+    def backward_weights(self, dy):
+        st = self.store
+        gb = st.gradient(self.bias_name) if self.use_bias else None
+        ops.dwconv_wgrad(dy.reshape(self.out.shape), self.x, st.gradient(self.kernel_name), gb, self.ws.wgrad,
+                         self._geom(self.x.shape[0]))
+
+    def backward_data(self, dy):
+        if not self.need_dx:
+            return None
+        ops.dwconv_dgrad(dy.reshape(self.out.shape), self.store[self.kernel_name], self.dx, self._geom(self.x.shape[0]),
+                         mask=self.x if self.in_relu else None)
+        return self.dx
+
+    def backward(self, dy):
+        self.backward_weights(dy)
+        return self.backward_data(dy)
+
+    def config(self):
+        return {"kernel_size": [self.kh, self.kw], "strides": [self.sh, self.sw], "padding": self.padding,
+                "depth_multiplier": self.depth_multiplier, "activation": self.activation, "use_bias": self.use_bias}
+
+
+class _PointwiseConv(Conv2D):
+    """The 1x1 stage of a SeparableConv2D: a Conv2D under Keras' parameter names for it."""
+
+    def __init__(self, owner_name: str, *args, **kw):
+        super().__init__(*args, **kw)
+        self.owner_name = owner_name
+
+    @property
+    def kernel_name(self) -> str:
+        return f"{self.owner_name}/pointwise_kernel"
+
+    @property
+    def bias_name(self) -> str:
+        return f"{self.owner_name}/bias"
+
+
+class SeparableConv2D(Layer):
+    """Keras SeparableConv2D: a depthwise conv (no bias, no activation) followed by a 1x1 Conv2D that carries
+    the bias and the activation.  A composite of two engine layers (``sublayers()``): the depthwise stage
+    runs on csrc/dwconv.hip, the pointwise stage on the conv kernels every 1x1 Conv2D uses.  Parameters, in
+    Keras' order: ``<name>/depthwise_kernel``, ``<name>/pointwise_kernel``, ``<name>/bias``."""
+    has_params = True
+
+    def __init__(self, filters: int, kernel_size=(3, 3), strides=(1, 1), padding="valid", depth_multiplier=1,
+                 activation="linear", use_bias=True, name=None, depthwise_initializer="glorot_uniform",
+                 pointwise_initializer="glorot_uniform"):
+        super().__init__(name or "separable_conv2d")
+        self.filters = int(filters)
+        self.activation = activation
+        self.use_bias = use_bias
+        self.depthwise = DepthwiseConv2D(kernel_size, strides, padding, depth_multiplier, "linear", False,
+                                         name=self.name, depthwise_initializer=depthwise_initializer)
+        self.pointwise = _PointwiseConv(self.name, filters, 1, 1, "valid", activation, use_bias,
+                                        name=f"{self.name}/pointwise", kernel_initializer=pointwise_initializer)
+        # the fused output ReLU (the activation, or a following Activation the planner folds in) is the
+        # pointwise stage's epilogue: alloc hands it down with need_dx / in_relu
+        self.relu = self.pointwise.relu
+
+    def bind_store(self, store):
+        self.store = self.depthwise.store = self.pointwise.store = store
+
+    def sublayers(self):
+        return [self.depthwise, self.pointwise]
+
+    def can_fuse_relu(self):
+        return True
+
+    def build(self, in_shape):
+        self.in_shape = tuple(in_shape)
+        self.out_shape = self.pointwise.build(self.depthwise.build(self.in_shape))
+        return self.out_shape
+
+    def specs(self):
+        return self.depthwise.specs() + self.pointwise.specs()
+
+    def alloc(self, B, device, dtype, ws):
+        d, p = self.depthwise, self.pointwise
+        d.need_dx, d.in_relu = self.need_dx, self.in_relu
+        p.need_dx, p.in_relu, p.relu = True, False, self.relu
+        d.alloc(B, device, dtype, ws)
+        p.alloc(B, device, dtype, ws)
+        self.out, self.dx = p.out, d.dx
+
+    def forward(self, x, training):
+        self.x = x
+        self.out = self.pointwise.forward(self.depthwise.forward(x, training), training)
+        return self.out
+
+    def backward(self, dy):
+        return self.depthwise.backward(self.pointwise.backward(dy.reshape(self.pointwise.out.shape)))
+
+    def config(self):
+        d = self.depthwise
+        return {"filters": self.filters, "kernel_size": [d.kh, d.kw], "strides": [d.sh, d.sw], "padding": d.padding,
+                "depth_multiplier": d.depth_multiplier, "activation": self.activation, "use_bias": self.use_bias}
 
 
 def _pair(v, default=None):

@@ -18,9 +18,8 @@ import torch
 
 from .. import ops
 from ..diagnostics import on as diag_on
-from .layers import (Activation, BatchNorm, Conv2D, ConvPoolGemm, Dense, Dropout, Flatten, FusedConvPool,
-                     KerasConvBlock, Layer, MaxPooling2D,
-                     ResidualBlock)
+from .layers import (Activation, BatchNorm, Conv2D, ConvPoolGemm, Dense, DepthwiseConv2D, Dropout, Flatten,
+                     FusedConvPool, KerasConvBlock, Layer, MaxPooling2D, ResidualBlock, SeparableConv2D)
 from .params import ParamStore
 
 
@@ -83,12 +82,14 @@ class Net:
     def _plan(self):
         shape = self.input_shape
         execd: list[Layer] = []
-        # a Dense / Conv2D activation other than relu / linear runs as its own streaming launch right after
-        # the GEMM, unless it ends the model (softmax / sigmoid fold into the loss)
+        # a Dense / Conv2D / DepthwiseConv2D / SeparableConv2D activation other than relu / linear runs as its
+        # own streaming launch right after the layer, unless it ends the model (softmax / sigmoid fold into
+        # the loss)
         pending = []
         for j, l in enumerate(self.layers_all):
             pending.append(l)
-            act = getattr(l, "activation", None) if isinstance(l, (Dense, Conv2D)) else None
+            act = getattr(l, "activation", None) if isinstance(l, (Dense, Conv2D, DepthwiseConv2D,
+                                                                   SeparableConv2D)) else None
             last = j == len(self.layers_all) - 1
             if act not in (None, "linear", "relu") and not (last and act in ("softmax", "sigmoid")):
                 if act == "softmax":
@@ -287,11 +288,15 @@ class Net:
         return out
 
     def _all_leaf_layers(self):
-        for l in self.exec_layers:
-            if hasattr(l, "sublayers"):  # composite layers: ResidualBlock, GraphLayer
-                yield from l.sublayers()
+        def leaves(l):
+            if hasattr(l, "sublayers"):  # composite layers: ResidualBlock, GraphLayer, SeparableConv2D
+                for s in l.sublayers():
+                    yield from leaves(s)
             else:
                 yield l
+
+        for l in self.exec_layers:
+            yield from leaves(l)
 
     # ------------------------------------------------------------------ buffers
     def bind(self, B: int):
@@ -740,6 +745,10 @@ class Net:
             if isinstance(l, Conv2D):
                 OH, OW, N = l.out_shape
                 f = 2 * OH * OW * N * l.kh * l.kw * l.in_shape[2]
+                return f * (3 if l.need_dx else 2)
+            if isinstance(l, DepthwiseConv2D):  # one input channel per output channel (a SeparableConv2D's
+                OH, OW, N = l.out_shape         # stages are leaves: this one and a 1x1 Conv2D)
+                f = 2 * OH * OW * N * l.kh * l.kw
                 return f * (3 if l.need_dx else 2)
             return 0
 

@@ -601,6 +601,54 @@ def pool2d_bwd(x, dy, dx, geom, avg=False, in_relu=False):
     return dx
 
 
+# ---- depthwise convolution (csrc/dwconv.hip): fp32 kernel [KH][KW][C*M], output channel co reads input co // M
+def dwconv_geometry(B, H, W, C, M, kernel, strides, padding):
+    """[B, H, W, C, M, OH, OW, KH, KW, sh, sw, pt, pl] of a Keras DepthwiseConv2D ('valid' | 'same': the odd
+    pixel of padding goes bottom / right, as TensorFlow does)."""
+    (kh, kw), (sh, sw) = _pair(kernel), _pair(strides)
+    if padding == "same":
+        (OH, OW), (pt, pl) = same_padding(H, W, kh, kw, (sh, sw))
+    elif padding == "valid":
+        OH, OW = conv_out_hw(H, W, kh, kw, (sh, sw), 0)
+        pt = pl = 0
+    else:
+        raise ValueError(f"depthwise conv padding {padding!r}")
+    if OH < 1 or OW < 1 or M < 1:
+        raise ValueError(f"depthwise kernel {kh}x{kw} / strides {sh},{sw} does not fit a {H}x{W} input")
+    return [int(B), int(H), int(W), int(C), int(M), OH, OW, kh, kw, sh, sw, pt, pl]
+
+
+def dwconv_fwd(x, w, bias, out, geom, relu=False):
+    """out = [relu](bias + depthwise conv of NHWC ``x`` with ``w`` [KH][KW][C*M] fp32)."""
+    if x.is_cuda:
+        _C().dwconv_fwd(x.contiguous(), w, bias, out, [int(v) for v in geom], bool(relu))
+    else:
+        out.copy_(ref.dwconv_fwd(x, w, bias, geom, relu).reshape(out.shape).to(out.dtype))
+    return out
+
+
+def dwconv_dgrad(dy, w, dx, geom, mask=None):
+    """dx = (transposed depthwise conv of dy) * relu'(mask)."""
+    if dy.is_cuda:
+        _C().dwconv_dgrad(dy.contiguous(), w, mask, dx, [int(v) for v in geom])
+    else:
+        dx.copy_(ref.dwconv_dgrad(dy, w, geom, mask).reshape(dx.shape).to(dx.dtype))
+    return dx
+
+
+def dwconv_wgrad(dy, x, gw, gb, workspace, geom):
+    """gw [KH][KW][C*M] = sum over (b, oh, ow) of dy * x; gb [C*M] = sum dy (None: no bias).  fp32, the same
+    bits for the same inputs (``workspace``: fp32 slab scratch, GPU only)."""
+    if dy.is_cuda:
+        _C().dwconv_wgrad(dy.contiguous(), x.contiguous(), gw, gb, workspace, [int(v) for v in geom])
+    else:
+        w, b = ref.dwconv_wgrad(dy, x, geom, gb is not None)
+        gw.copy_(w.reshape(gw.shape))
+        if gb is not None:
+            gb.copy_(b)
+    return gw
+
+
 def relu_bwd(y, dy, dx):
     if y.is_cuda:
         _C().relu_bwd(y, dy, dx)

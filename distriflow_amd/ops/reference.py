@@ -85,6 +85,44 @@ def conv_wgrad(dy, x, KH, KW, stride, pad, with_bias=True):
     return gw, gb
 
 
+# ---------------------------------------------------------------- depthwise conv
+def _dwconv(xc, w, bias, geom):
+    """NCHW depthwise conv: ``w`` [KH][KW][C*M] (Keras depthwise_kernel flattened) -> torch [C*M][1][KH][KW] with
+    groups = C (output channel co reads input channel co // M), after the explicit TF padding."""
+    B, H, W, C, M, OH, OW, KH, KW, sh, sw, pt, pl = geom
+    w4 = w.float().reshape(KH, KW, C * M).permute(2, 0, 1).unsqueeze(1)
+    return F.conv2d(_conv_pad(xc, KH, KW, (sh, sw), (pt, pl), OH, OW), w4, bias, stride=(sh, sw), groups=C)
+
+
+def dwconv_fwd(x, w, bias, geom, relu=False):
+    y = _dwconv(_nchw(x.float()), w, bias.float() if bias is not None else None, geom)
+    if relu:
+        y = torch.relu(y)
+    return _nhwc(y)
+
+
+def dwconv_dgrad(dy, w, geom, mask=None):
+    B, H, W, C = geom[:4]
+    xz = torch.zeros((dy.shape[0], C, H, W), dtype=torch.float32, device=dy.device, requires_grad=True)
+    with torch.enable_grad():
+        y = _dwconv(xz, w.detach(), None, geom)
+        dx, = torch.autograd.grad(y, xz, _nchw(dy.float()).reshape(y.shape))
+    dx = _nhwc(dx)
+    if mask is not None:
+        dx = dx * (mask.float().reshape(dx.shape) > 0)
+    return dx
+
+
+def dwconv_wgrad(dy, x, geom, with_bias=True):
+    B, H, W, C, M, OH, OW, KH, KW = geom[:9]
+    wz = torch.zeros((KH, KW, C * M), dtype=torch.float32, device=dy.device, requires_grad=True)
+    with torch.enable_grad():
+        y = _dwconv(_nchw(x.float()), wz, None, geom)
+        gw, = torch.autograd.grad(y, wz, _nchw(dy.float()).reshape(y.shape))
+    gb = dy.float().reshape(-1, C * M).sum(0) if with_bias else None
+    return gw, gb
+
+
 def dense_fwd(x, w2d, bias, relu):
     N = bias.shape[0] if bias is not None else w2d.shape[0]
     K = x.shape[-1]
