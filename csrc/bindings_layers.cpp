@@ -10,10 +10,8 @@ void igemm_fwd_py(torch::Tensor src, torch::Tensor w, c10::optional<torch::Tenso
                   int64_t lda, int64_t ldc, std::vector<int64_t> geom, int64_t mode, bool relu, double alpha,
                   c10::optional<torch::Tensor> res, c10::optional<torch::Tensor> resmask, double drop_p,
                   int64_t drop_seed, c10::optional<torch::Tensor> drop_step, c10::optional<torch::Tensor> pool_code,
-                  int64_t drop_step_add, c10::optional<torch::Tensor> bn_ws, c10::optional<torch::Tensor> bn_ticket,
-                  int64_t bn_mode, std::vector<torch::Tensor> bn_vecs, c10::optional<torch::Tensor> bn_x,
-                  double bn_momentum, double bn_eps, double bn_gscale, c10::optional<torch::Tensor> bacc,
-                  int64_t bacc_mode, std::vector<torch::Tensor> bacc_in, c10::optional<torch::Tensor> bacc2,
+                  int64_t drop_step_add, c10::optional<torch::Tensor> bacc, int64_t bacc_mode,
+                  std::vector<torch::Tensor> bacc_in, c10::optional<torch::Tensor> bacc2,
                   std::vector<torch::Tensor> bacc2_in) {
   need(src, at::kBFloat16, "src");
   need(w, at::kBFloat16, "w");
@@ -57,44 +55,6 @@ void igemm_fwd_py(torch::Tensor src, torch::Tensor w, c10::optional<torch::Tenso
   a.alpha = (float)alpha;
   a.drop = drop_from(drop_p, drop_seed, drop_step, drop_step_add);
   if (pooled) a.pool_code = pool_code->data_ptr<uint8_t>();
-  if (has(bn_ws)) {
-    // BatchNorm statistics finalised inside this launch (kernels.h BnEpi)
-    need(*bn_ws, at::kFloat, "bn_ws");
-    TORCH_CHECK(has(bn_ticket), "bn_ws needs bn_ticket");
-    need(*bn_ticket, at::kInt, "bn_ticket");
-    TORCH_CHECK(out.scalar_type() == at::kBFloat16, "bn: bf16 output");
-    dfa::BnEpi& e = a.bn;
-    e.part = bn_ws->data_ptr<float>();
-    e.ticket = reinterpret_cast<unsigned*>(bn_ticket->data_ptr<int>());
-    e.mode = (int)bn_mode;
-    e.momentum = (float)bn_momentum;
-    e.eps = (float)bn_eps;
-    e.gscale = (float)bn_gscale;
-    for (auto& v : bn_vecs) {
-      need(v, at::kFloat, "bn vector");
-      TORCH_CHECK(v.numel() >= N, "bn vector smaller than N");
-    }
-    if (bn_mode == 0) {
-      TORCH_CHECK(bn_vecs.size() == 4, "bn mode 0: [mean, invstd, run_mean, run_var]");
-      e.mean_out = bn_vecs[0].data_ptr<float>();
-      e.invstd_out = bn_vecs[1].data_ptr<float>();
-      e.run_mean = bn_vecs[2].data_ptr<float>();
-      e.run_var = bn_vecs[3].data_ptr<float>();
-    } else {
-      TORCH_CHECK(bn_mode == 1 && bn_vecs.size() == 6, "bn mode 1: [mean, invstd, gamma, dgamma, dbeta, coef]");
-      TORCH_CHECK(has(bn_x), "bn mode 1 needs the BN input");
-      need(*bn_x, at::kBFloat16, "bn_x");
-      TORCH_CHECK(bn_x->numel() >= (M - 1) * ldc + N, "bn_x too small");
-      TORCH_CHECK(bn_vecs[5].numel() >= 3 * N, "bn coef must hold [3][N]");
-      e.x = reinterpret_cast<const dfa::bf16*>(bn_x->data_ptr());
-      e.mean = bn_vecs[0].data_ptr<float>();
-      e.invstd = bn_vecs[1].data_ptr<float>();
-      e.gamma = bn_vecs[2].data_ptr<float>();
-      e.dgamma = bn_vecs[3].data_ptr<float>();
-      e.dbeta = bn_vecs[4].data_ptr<float>();
-      e.coef = bn_vecs[5].data_ptr<float>();
-    }
-  }
   if (has(bacc)) {
     // BatchNorm sums accumulated by the epilogue (kernels.h BnAcc): acc [nrep][2][N] fp64; mode 1 inputs
     // [x, mean, invstd] of the BatchNorm (and of a second one sharing the gradient)
@@ -126,16 +86,9 @@ void igemm_fwd_py(torch::Tensor src, torch::Tensor w, c10::optional<torch::Tenso
     }
   }
   TORCH_CHECK(!a.drop.on || (ldc == N && !a.out_f32), "folded dropout needs a dense bf16 output (ldc == N)");
-  // the one plan of this launch: what it may carry, the BatchNorm tiles, the scratch
+  // the one plan of this launch: what it may carry, the scratch
   const dfa::ConvPlan plan = dfa::conv_plan(a, (int)mode);
   TORCH_CHECK(!pooled || plan.pool, "pooled conv: unsupported geometry / alignment");
-  if (has(bn_ws)) {
-    TORCH_CHECK(plan.bn_ntm > 0, "bn: this conv launch cannot finalise BatchNorm statistics");
-    a.bn.ntm = plan.bn_ntm;
-    a.bn.ngrp = (plan.bn_ntm + 15) / 16;
-    TORCH_CHECK(bn_ws->numel() >= (int64_t)(a.bn.ntm + a.bn.ngrp) * 2 * N, "bn_ws too small");
-    TORCH_CHECK(bn_ticket->numel() >= (int64_t)plan.bn_ntn * (1 + a.bn.ngrp), "bn_ticket too small");
-  }
   TORCH_CHECK(!has(bacc) || plan.bacc_ok, "bacc: this launch cannot accumulate BatchNorm sums");
   // split-K partials for the under-filled (small-M, long-K) shapes: PyTorch's caching allocator is
   // stream ordered and graph-capture aware, so the scratch is safe to drop right after the launch
@@ -150,8 +103,7 @@ void igemm_fwd_py(torch::Tensor src, torch::Tensor w, c10::optional<torch::Tenso
 // The plan of a launch with these shapes before any tensor exists: 16-byte aligned dummy operands stand in
 // for the real ones (torch allocations are at least that aligned).  bacc_mode >= 0: with BatchNorm sums.
 py::dict conv_plan_py(int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector<int64_t> geom, int64_t mode,
-                      int64_t bacc_mode, bool two, bool has_res, bool has_mask, bool pooled, int64_t lda, bool drop,
-                      bool bn) {
+                      int64_t bacc_mode, bool two, bool has_res, bool has_mask, bool pooled, int64_t lda, bool drop) {
   static dfa::bf16 dummy[8] __attribute__((aligned(16)));
   static double dacc[2] __attribute__((aligned(16)));
   static float dvec[2] __attribute__((aligned(16)));
@@ -163,7 +115,6 @@ py::dict conv_plan_py(int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector
   if (has_mask) a.mask = dummy;
   if (pooled) a.pool_code = reinterpret_cast<uint8_t*>(dummy);
   if (drop) a.drop.on = 1;
-  if (bn) a.bn.part = dvec;
   if (bacc_mode >= 0) {
     a.bacc.acc = dacc;
     a.bacc.nrep = 1;
@@ -177,8 +128,8 @@ py::dict conv_plan_py(int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector
   return py::dict("family"_a = kFamily[p.family], "BM"_a = p.BM, "BN"_a = p.BN, "fast"_a = p.fast, "par"_a = p.par,
                   "pool"_a = p.pool, "splits"_a = p.splits, "wide"_a = p.wide, "row"_a = p.row, "fold"_a = p.fold,
                   "ks"_a = p.ks, "vec"_a = p.vec, "grid"_a = p.grid, "block"_a = p.block, "combine"_a = p.combine,
-                  "drop_after"_a = p.drop_after, "splitk_floats"_a = p.splitk_floats, "bn_ntm"_a = p.bn_ntm,
-                  "bn_ntn"_a = p.bn_ntn, "bacc_ok"_a = p.bacc_ok);
+                  "drop_after"_a = p.drop_after, "splitk_floats"_a = p.splitk_floats,
+                  "bacc_ok"_a = p.bacc_ok);
 }
 
 void igemm_wgrad_py(torch::Tensor dy, torch::Tensor src, torch::Tensor gw, c10::optional<torch::Tensor> gb,
@@ -566,14 +517,13 @@ dfa::BnStatsArgs bn_fwd_args(torch::Tensor& x, torch::Tensor& mean, torch::Tenso
   return a;
 }
 
-// checks and launch arguments of the backward statistics; dx: the fused launch's output (checked in its place)
+// checks and launch arguments of the backward statistics
 dfa::BnStatsArgs bn_bwd_args(torch::Tensor& x, c10::optional<torch::Tensor>& mask, torch::Tensor& dy,
-                             const torch::Tensor* dx, torch::Tensor& gamma, torch::Tensor& mean, torch::Tensor& invstd,
-                             torch::Tensor& dgamma, torch::Tensor& dbeta, torch::Tensor& coef, torch::Tensor& ws,
-                             torch::Tensor& counter, int64_t M, int64_t C, double gscale) {
+                             torch::Tensor& gamma, torch::Tensor& mean, torch::Tensor& invstd, torch::Tensor& dgamma,
+                             torch::Tensor& dbeta, torch::Tensor& coef, torch::Tensor& ws, torch::Tensor& counter,
+                             int64_t M, int64_t C, double gscale) {
   bn_check_act(x, M * C, "x");
   bn_check_act(dy, M * C, "dy");
-  if (dx) bn_check_act(*dx, M * C, "dx");
   if (has(mask)) bn_check_act(*mask, M * C, "mask");
   bn_check_vec(gamma, C, "gamma");
   bn_check_vec(mean, C, "mean");
@@ -633,8 +583,7 @@ void bn_stats_fwd_py(torch::Tensor x, torch::Tensor mean, torch::Tensor invstd, 
 void bn_stats_bwd_py(torch::Tensor x, c10::optional<torch::Tensor> mask, torch::Tensor dy, torch::Tensor gamma,
                      torch::Tensor mean, torch::Tensor invstd, torch::Tensor dgamma, torch::Tensor dbeta,
                      torch::Tensor coef, torch::Tensor ws, torch::Tensor counter, int64_t M, int64_t C, double gscale) {
-  dfa::BnStatsArgs a =
-      bn_bwd_args(x, mask, dy, nullptr, gamma, mean, invstd, dgamma, dbeta, coef, ws, counter, M, C, gscale);
+  dfa::BnStatsArgs a = bn_bwd_args(x, mask, dy, gamma, mean, invstd, dgamma, dbeta, coef, ws, counter, M, C, gscale);
   check_hip(dfa::bn_stats(a, 1, cur_stream()), "bn_stats_bwd");
 }
 
@@ -656,47 +605,6 @@ void bn_apply_py(torch::Tensor x, torch::Tensor y, torch::Tensor gamma, torch::T
   bn_set_residual(a, r, rgamma, rbeta, rmean, rinvstd, M, C);
   a.M = (int)M; a.C = (int)C; a.relu = relu ? 1 : 0; a.eval = eval ? 1 : 0; a.eps = (float)eps;
   check_hip(dfa::bn_apply(a, cur_stream()), "bn_apply");
-}
-
-// statistics + apply in one launch (training forward): y = act(bn(x) [+ r | + bn_r(r)]); the generation
-// word of the in-launch hand-off is counter[64]
-void bn_fwd_fused_py(torch::Tensor x, torch::Tensor y, torch::Tensor gamma, torch::Tensor beta, torch::Tensor mean,
-                     torch::Tensor invstd, c10::optional<torch::Tensor> run_mean, c10::optional<torch::Tensor> run_var,
-                     c10::optional<torch::Tensor> r, c10::optional<torch::Tensor> rgamma,
-                     c10::optional<torch::Tensor> rbeta, c10::optional<torch::Tensor> rmean,
-                     c10::optional<torch::Tensor> rinvstd, torch::Tensor ws, torch::Tensor counter, int64_t M,
-                     int64_t C, bool relu, double momentum, double eps) {
-  TORCH_CHECK(dfa::bn_fused_ok((int)C), "bn_fwd_fused: C must be a multiple of 8 (<= 1024)");
-  bn_check_act(x, M * C, "x");
-  bn_check_act(y, M * C, "y");
-  for (auto* t : {&gamma, &beta, &mean, &invstd}) bn_check_vec(*t, C, "bn vector");
-  const bool run = bn_check_run(run_mean, run_var, C);
-  bn_check_stats_ws(ws, counter, M, C);
-  TORCH_CHECK(counter.numel() >= 65, "bn_fwd_fused: counter needs 65 words (generation at 64)");
-  TORCH_CHECK(ws.numel() >= (1008 + 63) * 2 * C, "bn_fwd_fused: workspace needs (1008 + 63) x 2C floats");
-  dfa::BnStatsArgs a = bn_fwd_args(x, mean, invstd, run_mean, run_var, run, ws, counter, M, C, momentum, eps);
-  dfa::BnApplyArgs p{};
-  p.x = a.x;
-  p.y = (dfa::bf16*)y.data_ptr();
-  p.gamma = gamma.data_ptr<float>();
-  p.beta = beta.data_ptr<float>();
-  p.mean = a.mean_out;
-  p.invstd = a.invstd_out;
-  bn_set_residual(p, r, rgamma, rbeta, rmean, rinvstd, M, C);
-  p.M = (int)M; p.C = (int)C; p.relu = relu ? 1 : 0; p.eval = 0; p.eps = (float)eps;
-  check_hip(dfa::bn_fwd_fused(a, p, a.counter + 64, cur_stream()), "bn_fwd_fused");
-}
-
-// backward statistics + dx in one launch; generation word counter[64]
-void bn_bwd_fused_py(torch::Tensor x, c10::optional<torch::Tensor> mask, torch::Tensor dy, torch::Tensor dx,
-                     torch::Tensor gamma, torch::Tensor mean, torch::Tensor invstd, torch::Tensor dgamma,
-                     torch::Tensor dbeta, torch::Tensor coef, torch::Tensor ws, torch::Tensor counter, int64_t M,
-                     int64_t C, double gscale) {
-  TORCH_CHECK(dfa::bn_fused_ok((int)C), "bn_bwd_fused: C must be a multiple of 8 (<= 1024)");
-  dfa::BnStatsArgs a = bn_bwd_args(x, mask, dy, &dx, gamma, mean, invstd, dgamma, dbeta, coef, ws, counter, M, C, gscale);
-  TORCH_CHECK(counter.numel() >= 65, "bn_bwd_fused: counter needs 65 words (generation at 64)");
-  TORCH_CHECK(ws.numel() >= (1008 + 63) * 2 * C, "bn_bwd_fused: workspace needs (1008 + 63) x 2C floats");
-  check_hip(dfa::bn_bwd_fused(a, (dfa::bf16*)dx.data_ptr(), a.counter + 64, cur_stream()), "bn_bwd_fused");
 }
 
 void bn_dx_py(torch::Tensor x, c10::optional<torch::Tensor> mask, torch::Tensor dy, torch::Tensor dx,
@@ -983,15 +891,13 @@ void bind_layers(py::module_& m) {
         py::arg("lda"), py::arg("ldc"), py::arg("geom"), py::arg("mode"), py::arg("relu"), py::arg("alpha"),
         py::arg("res") = py::none(), py::arg("resmask") = py::none(), py::arg("drop_p") = 0.0,
         py::arg("drop_seed") = 0, py::arg("drop_step") = py::none(), py::arg("pool_code") = py::none(),
-        py::arg("drop_step_add") = 0, py::arg("bn_ws") = py::none(), py::arg("bn_ticket") = py::none(),
-        py::arg("bn_mode") = 0, py::arg("bn_vecs") = std::vector<torch::Tensor>{}, py::arg("bn_x") = py::none(),
-        py::arg("bn_momentum") = 0.1, py::arg("bn_eps") = 1e-5, py::arg("bn_gscale") = 1.0,
-        py::arg("bacc") = py::none(), py::arg("bacc_mode") = 0, py::arg("bacc_in") = std::vector<torch::Tensor>{},
+        py::arg("drop_step_add") = 0, py::arg("bacc") = py::none(), py::arg("bacc_mode") = 0,
+        py::arg("bacc_in") = std::vector<torch::Tensor>{},
         py::arg("bacc2") = py::none(), py::arg("bacc2_in") = std::vector<torch::Tensor>{});
   m.def("conv_plan", &conv_plan_py, "the launch plan of igemm_fwd for these shapes (csrc/conv_plan.hip), as a dict",
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("Kpad"), py::arg("geom"), py::arg("mode"),
         py::arg("bacc_mode") = -1, py::arg("two") = false, py::arg("has_res") = false, py::arg("has_mask") = false,
-        py::arg("pooled") = false, py::arg("lda") = 0, py::arg("drop") = false, py::arg("bn") = false);
+        py::arg("pooled") = false, py::arg("lda") = 0, py::arg("drop") = false);
   m.def("unpool2", [](torch::Tensor dyp, torch::Tensor code, torch::Tensor dy) {
     need(dyp, at::kBFloat16, "unpool dyp");
     need(dy, at::kBFloat16, "unpool dy");
@@ -1031,19 +937,6 @@ void bind_layers(py::module_& m) {
   m.def("dwconv_dgrad", &dwconv_dgrad_py, "depthwise conv data gradient [* relu'(mask)]");
   m.def("dwconv_wgrad", &dwconv_wgrad_py, "depthwise conv weight / bias gradient (fixed-order slab sums)");
   m.def("gather_labels", &gather_labels_py);
-  m.def("bn_finalize_partials", [](torch::Tensor part, int64_t ntm, int64_t C, int64_t M, torch::Tensor mean,
-                                   torch::Tensor invstd, c10::optional<torch::Tensor> run_mean,
-                                   c10::optional<torch::Tensor> run_var, double momentum, double eps) {
-    need(part, at::kFloat, "bn part");
-    need(mean, at::kFloat, "bn mean");
-    need(invstd, at::kFloat, "bn invstd");
-    TORCH_CHECK(part.numel() >= ntm * 2 * C && mean.numel() >= C && invstd.numel() >= C, "bn_finalize: sizes");
-    check_hip(dfa::bn_finalize_partials(part.data_ptr<float>(), (int)ntm, (int)C, M, mean.data_ptr<float>(),
-                                        invstd.data_ptr<float>(), const_cast<float*>(cptr<float>(run_mean)),
-                                        const_cast<float*>(cptr<float>(run_var)),
-                                        (float)momentum, (float)eps, cur_stream()),
-              "bn_finalize_partials");
-  });
   m.def("bn_stats_fwd", &bn_stats_fwd_py, "BN forward statistics (partials + last-workgroup finalize, one launch)");
   m.def("bn_stats_bwd", &bn_stats_bwd_py, "BN backward statistics: dgamma, dbeta and dx coefficients");
   m.def("bn_apply", &bn_apply_py, "BN normalize (+ residual join, + ReLU)");
@@ -1051,8 +944,6 @@ void bind_layers(py::module_& m) {
   m.def("bn_apply_acc", &bn_apply_acc_py, "BN training apply, statistics finalised from epilogue-accumulated sums");
   m.def("bn_dx_acc", &bn_dx_acc_py, "BN input gradient, coefficients finalised from epilogue-accumulated sums");
   m.def("gap_bwd_bn", &gap_bwd_bn_py, "GAP backward with relu' and BatchNorm backward sums");
-  m.def("bn_fwd_fused", &bn_fwd_fused_py, "BN training forward: statistics + apply in one launch");
-  m.def("bn_bwd_fused", &bn_bwd_fused_py, "BN backward: statistics + dx in one launch");
   m.def("bn_stats_grid", &dfa::bn_stats_grid, "partial-slab count of a BN statistics launch");
   m.def("sgd_multi", &sgd_multi_py, py::arg("descs"), py::arg("ndesc"), py::arg("total_blocks"), py::arg("master"),
         py::arg("grad"), py::arg("mom"), py::arg("wbf"), py::arg("hyper"), py::arg("apply_update"),

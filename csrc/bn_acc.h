@@ -1,7 +1,8 @@
 // BatchNorm statistics accumulated by the PRODUCING kernel's epilogue (kernels.h BnAcc).
 //
 // Round 3/4 finalised the statistics inside the producing launch with two levels of last-arriver
-// hand-offs (bn_epi.h) or in separate statistics launches (bn.hip): each workgroup waited for its
+// hand-offs (since removed: docs/RESULTS.md) or in separate statistics launches (bn.hip, hand-off in
+// handoff.h): each workgroup waited for its
 // write-through partials and a ticket, or the statistics pass re-read the whole tensor (ResNet-18 B=256:
 // 40 launches, 592 us of a 2.86 ms step, profiles/r4/resnet18_b256_step_breakdown_r4_final.txt).  Here a
 // workgroup reduces the values it STORED (bf16-rounded, masked) in registers, across the 16 lanes that

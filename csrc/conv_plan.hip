@@ -66,7 +66,7 @@ bool conv3_halo_supported(const IGemmArgs& a, int mode, int& R, int& TI) {
   if (!on || (mode != MODE_FWD && mode != MODE_DGRAD)) return false;
   return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.SH == a.OH && a.SW == a.OW && a.SC % 64 == 0 &&
          a.N % 64 == 0 && a.K == 9 * a.SC && a.Kpad >= a.K && a.Kpad % 8 == 0 && a.ldc % 4 == 0 && !a.bias &&
-         !a.out_f32 && !a.drop.on && !a.pool_code && !a.bn.part &&
+         !a.out_f32 && !a.drop.on && !a.pool_code &&
          a.M % kCP == 0 && a.M % (a.OH * a.OW) == 0 && c3_geom(a.OH, a.OW, R, TI) &&
          (long long)a.M * a.ldc * 2 < (1LL << 32) &&  // one 32-bit byte offset per epilogue element
          aligned(a.src, 15) && aligned(a.w, 15) && aligned(a.out, 7) &&
@@ -89,7 +89,7 @@ void plan_igemm64(const IGemmArgs& a, int mode, int s64, ConvPlan& p) {
     }
     return;
   }
-  p.splits = a.bn.part ? 1 : s64;
+  p.splits = s64;
   if (p.splits > 1) p.grid *= p.splits, p.combine = true, p.splitk_floats = (long long)p.splits * a.M * a.N;
 }
 
@@ -142,7 +142,7 @@ void plan_generic(const IGemmArgs& a, int mode, ConvPlan& p) {
 // kernels (and their split-K combine) in both modes, with the vectorised bf16 epilogue; the generic kernel
 // the forward sums only.
 bool bacc_ok(const IGemmArgs& a, int mode, int family) {
-  if (mode == MODE_DIRECT || a.out_f32 || a.drop.on || a.pool_code || a.bn.part) return false;
+  if (mode == MODE_DIRECT || a.out_f32 || a.drop.on || a.pool_code) return false;
   if (a.bacc.nrep < 1 || a.bacc.nrep > kBnAccMaxRep || (a.bacc.mode == 1 && (!a.bacc.x || !a.bacc.mean))) return false;
   if (a.bacc.acc2 && (a.bacc.mode != 1 || !a.bacc.x2 || !a.bacc.mean2)) return false;
   if (family == CONV_GENERIC) return mode == MODE_FWD && a.bacc.mode == 0;
@@ -173,15 +173,8 @@ ConvPlan conv_plan(const IGemmArgs& a, int mode) {
   // ... and its split-K: only the under-filled 64 x 128 launches, never with pooling
   static const bool splitk = diag_int("igemm_splitk", 1) != 0;
   const int s64 = splitk && ok64 && p.BM == 64 && !a.pool_code ? splitk_for(a, 64, 128) : 1;
-  // The launch that finalises BatchNorm statistics in its epilogue (kernels.h BnEpi) is igemm64's: conv
-  // forward or data gradient, bf16 output, no pooling, no split-K (those launches keep the statistics
-  // pass), no stride-2 data gradient on parity classes; 128 x 32 tiles are built without that epilogue.
-  if (mode != MODE_DIRECT && ok64 && !a.pool_code && !a.out_f32 && s64 == 1 && a.N > 32 &&
-      !(mode == MODE_DGRAD && a.stride == 2 && igemm64_fast_ok(a, mode)))
-    p.bn_ntm = cdiv(a.M, p.BM), p.bn_ntn = cdiv(a.N, p.BN);
-
   if (a.drop.on && (a.out_f32 || a.ldc != a.N)) return p;
-  if (a.irregular && (a.pool_code || a.bn.part)) return p;
+  if (a.irregular && a.pool_code) return p;
   if (a.pool_code) {  // the pooled epilogue is igemm64's, plain conv forward only
     if (mode == MODE_FWD && ok64 && a.OH % 2 == 0 && a.OW % 2 == 0 && a.N % 4 == 0 && a.ldc == a.N && !a.out_f32 &&
         !a.mask && !a.res && aligned(a.out, 7) && aligned(a.pool_code, 3))

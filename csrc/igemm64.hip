@@ -21,7 +21,6 @@
 //     the weights as the MFMA A operand so each lane stores 4 adjacent output channels at once
 #include "common.h"
 #include "kernels.h"
-#include "bn_epi.h"
 #include "bn_acc.h"
 
 namespace dfa {
@@ -625,71 +624,6 @@ __global__ void __launch_bounds__(256, (igemm64_occ<BM, BN>())) igemm64_kernel(I
         else
           reinterpret_cast<bf16*>(a.out)[o + r] = f2bf(x);
       }
-    }
-  }
-
-  // BatchNorm statistics of this tile's STORED outputs (kernels.h BnEpi), finalised inside the launch:
-  // the tile's output is re-read (its own stores, still in this XCD's L2) in 8-byte column chunks,
-  // mode 1 with the BN input alongside, reduced over the rows through LDS into one partial row per row
-  // tile, then the hierarchical last-arriver finalisation (csrc/bn_epi.h).
-  if constexpr (!SPLIT && !POOL && !PAR && BN >= 64) {  // (32-column tiles keep their occupancy)
-    if (a.bn.part) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's output stores are complete
-      __syncthreads();
-      typedef __bf16 bf16x4_b __attribute__((ext_vector_type(4)));
-      constexpr int NCH = BN / 4, RPP = 256 / NCH;
-      const int ch = tid % NCH, rs = tid / NCH;
-      const int col = n0 + 4 * ch;
-      float s4[4] = {0.f, 0.f, 0.f, 0.f}, q4[4] = {0.f, 0.f, 0.f, 0.f}, mu[4], is[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        mu[r] = (a.bn.mode == 1 && col + r < a.N) ? a.bn.mean[col + r] : 0.f;
-        is[r] = (a.bn.mode == 1 && col + r < a.N) ? a.bn.invstd[col + r] : 1.f;
-      }
-      const bf16* ob = reinterpret_cast<const bf16*>(a.out);
-      const int rend = min(m0 + BM, a.M);
-      if (col + 3 < a.N && (a.ldc & 3) == 0) {
-#pragma unroll 4
-        for (int row = m0 + rs; row < rend; row += RPP) {
-          const long long o = (long long)row * a.ldc + col;
-          const bf16x4_b yv = *reinterpret_cast<const bf16x4_b*>(ob + o);
-          bf16x4_b xv;
-          if (a.bn.mode == 1) xv = *reinterpret_cast<const bf16x4_b*>(a.bn.x + o);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float y = (float)yv[r];
-            s4[r] += y;
-            q4[r] += a.bn.mode == 1 ? y * (((float)xv[r] - mu[r]) * is[r]) : y * y;
-          }
-        }
-      } else {
-        for (int row = m0 + rs; row < rend; row += RPP)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (col + r < a.N) {
-              const long long o = (long long)row * a.ldc + col + r;
-              const float y = (float)ob[o];
-              s4[r] += y;
-              q4[r] += a.bn.mode == 1 ? y * (((float)a.bn.x[o] - mu[r]) * is[r]) : y * y;
-            }
-      }
-      float* red = reinterpret_cast<float*>(lds);  // the k loop ended with a barrier: LDS is free
-      __syncthreads();
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[(rs * BN + 4 * ch + r) * 2] = s4[r];
-        red[(rs * BN + 4 * ch + r) * 2 + 1] = q4[r];
-      }
-      __syncthreads();
-      for (int t = tid; t < 2 * BN; t += 256) {
-        const int which = t / BN, c = t - which * BN;
-        if (n0 + c >= a.N) continue;
-        float v = 0.f;
-        for (int w = 0; w < RPP; ++w) v += red[(w * BN + c) * 2 + which];  // fixed row-group order
-        st_sc1(a.bn.part + ((long long)tile_m * 2 + which) * a.N + n0 + c, v);
-      }
-      __shared__ int s_last;
-      bn_epi_finalize<256>(a.bn, a.N, a.M, tile_m, tile_n, n0, min(BN, a.N - n0), &s_last);
     }
   }
 }

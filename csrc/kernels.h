@@ -39,25 +39,6 @@ inline DropSpec make_drop(float p, unsigned long long seed, const long long* ste
   return d;
 }
 
-// BatchNorm statistics emitted by the PRODUCING conv launch (csrc/bn_epi.h): every row tile reduces the
-// values it stored into a partial [2][N] row, and the launch's last arrivers (two fixed-order levels)
-// finalise them, so the BatchNorm that consumes the output needs neither a statistics pass over it nor a
-// finalize launch.  mode 0 (forward): sums of y and y^2 -> mean, invstd, running statistics.  mode 1
-// (backward, the conv producing the BN's output gradient g, relu' already applied): sums of g and
-// g * xhat with xhat = (x - mean) * invstd of the BN input x -> dgamma, dbeta and the coefficients of
-// dx = k1 g + k2 x + k3 (bn_dx).
-struct BnEpi {
-  float* part;        // [ntm][2][N] row-tile partials (write-through), then [ngrp][2][N] group partials
-  unsigned* ticket;   // [ncolgroups][1 + ngrp] arrival tickets, zero between launches (last arrivers re-arm)
-  int ntm, ngrp;      // row tiles of the launch, groups of 16 of them
-  int mode;
-  const bf16* x;                         // mode 1: the BN input [M][ldc]
-  const float *mean, *invstd, *gamma;    // mode 1 inputs (forward statistics, scale)
-  float *mean_out, *invstd_out, *run_mean, *run_var;  // mode 0 outputs
-  float *dgamma, *dbeta, *coef;          // mode 1 outputs (coef [3][N])
-  float momentum, eps, gscale;
-};
-
 // BatchNorm statistics accumulated in the PRODUCING kernel's epilogue (csrc/bn_acc.h): every workgroup
 // reduces the values it stored, per channel and in a fixed order, and adds them in fp64 into replica
 // (blockIdx % nrep) of `acc` (no ticket, no wait: the adds are fire-and-forget); the consuming pass
@@ -96,8 +77,6 @@ struct IGemmArgs {
   int splits;
   DropSpec drop;     // dropout after the activation (requires ldc == N, bf16 out)
   uint8_t* pool_code;  // conv forward + 2x2 max-pool (igemm64 POOL): out = pooled [M/4][N], code [M/4][N]
-  BnEpi bn;            // BatchNorm statistics of the stored output, finalised inside the launch (bn.part
-                       // != nullptr: igemm64, no split-K / pooling / parity-class launch)
   BnAcc bacc;          // BatchNorm statistics of the stored output accumulated by the epilogue (bacc.acc)
 };
 
@@ -148,9 +127,6 @@ struct ConvPlan {
   bool combine;           // a split-K combine launch follows (igemm64_splitk_combine)
   bool drop_after;        // the folded dropout runs as its own launch afterwards (smallc / generic kernels)
   long long splitk_floats;  // fp32 scratch the caller provides in IGemmArgs::splitk_ws ([splits][M][N])
-  // row tiles / column ranges of the launch that finalises BatchNorm statistics (a.bn.part set: always
-  // igemm64, whatever runs without it); 0 when it cannot: split-K, pooling, parity classes, 128 x 32 tiles
-  int bn_ntm, bn_ntn;
   bool bacc_ok;           // the launch can accumulate a.bacc (BatchNorm sums, csrc/bn_acc.h)
 };
 ConvPlan conv_plan(const IGemmArgs& a, int mode);
@@ -167,8 +143,6 @@ constexpr int kC3Tickets = 1024;      // tickets of a folded two-split launch (o
 
 hipError_t igemm_fwd(const IGemmArgs& a, int mode, hipStream_t st);  // plans, then launches
 hipError_t igemm_fwd(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st);
-hipError_t bn_finalize_partials(const float* part, int ntm, int C, long long M, float* mean, float* invstd,
-                                float* run_mean, float* run_var, float momentum, float eps, hipStream_t st);
 // dY of a pooled conv from the pooled gradient and the argmax codes (NHWC, 2x2 windows)
 hipError_t unpool2(const bf16* dyp, const uint8_t* code, bf16* dy, int B, int OH, int OW, int N, hipStream_t st);
 // 64-deep-step variant for the vectorizable cases (csrc/igemm64.hip)
@@ -286,11 +260,6 @@ hipError_t bn_stats(const BnStatsArgs& a, int mode, hipStream_t st);  // mode 0 
 hipError_t bn_apply(const BnApplyArgs& a, hipStream_t st);
 hipError_t bn_dx(const bf16* x, const bf16* mask, const bf16* dy, bf16* dx, const float* coef, int M, int C,
                  hipStream_t st);
-// statistics + apply (forward) / statistics + dx (backward) in one launch (C % 8 == 0, training mode);
-// gen: a monotonically increasing generation word (any value to start, never reset)
-bool bn_fused_ok(int C);
-hipError_t bn_fwd_fused(const BnStatsArgs& a, const BnApplyArgs& p, unsigned* gen, hipStream_t st);
-hipError_t bn_bwd_fused(const BnStatsArgs& a, bf16* dx, unsigned* gen, hipStream_t st);
 
 // Consumers that finalise BnAcc sums in their prologue (csrc/bn.hip).  Every workgroup derives the
 // per-channel coefficients from the replicas itself (fixed replica order, fp64); workgroup 0 also writes

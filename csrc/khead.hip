@@ -17,7 +17,7 @@
 //        relu'(H1) * 1/(1-p) = dZ1, writes H1^T / dZ1^T / dZ2^T (weight-gradient operands) and the loss
 //        partials, and publishes dZ1 (sc1 stores) behind a tagged flag
 //     4. all 8 jobs of the row tile: dP_chunk = dZ1 W1_chunk (MFMA), * alpha, relu'(P) -> dp
-//   The hand-off is the fence-free sc1 form of csrc/bn_epi.h (stores drained by s_waitcnt vmcnt(0)
+//   The hand-off is the fence-free sc1 form of csrc/handoff.h (stores drained by s_waitcnt vmcnt(0)
 //   before the relaxed agent-scope ticket / flag; sc1 loads on the reading side).  The grid is
 //   persistent (G <= CU count, a multiple of 8), so the 8 jobs of a row tile always run concurrently
 //   and the flag wait cannot starve; the flags compare against a per-launch tag that the last finishing

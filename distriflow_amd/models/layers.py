@@ -263,53 +263,24 @@ class Conv2D(Layer):
         self.ws = ws
         self._B = B
         self._bacc_cache = {}
-        # BatchNorm statistics finalised inside this conv's own launches (csrc/bn_epi.h): the forward's for
-        # the BN that consumes the output, the data gradient's for the BN that produced the input
-        self._bn_fwd = self._bn_bwd = None
-        if torch.device(device).type == "cuda" and diag_on("bn_epilogue") and self.regular:
-            H, W, C = self.in_shape
-            OH, OW, N = self.out_shape
-            kpad = primary_kpad_of(self)
-            z = lambda n, dt: torch.zeros(n, dtype=dt, device=device)  # noqa: E731
-            ntm, ntn = ops.conv_bn_layout(B, H, W, C, OH, OW, N, self.k, self.k, self.stride, self.pad, kpad)
-            if ntm:
-                ng = -(-ntm // 16)
-                self._bn_fwd = (z((ntm + ng) * 2 * N, torch.float32), z(ntn * (1 + ng), torch.int32))
-            if self.need_dx:
-                ntm, ntn = ops.conv_bn_layout(B, H, W, C, OH, OW, N, self.k, self.k, self.stride, self.pad,
-                                              dgrad_kpad_of(self), dgrad=True)
-                if ntm:
-                    ng = -(-ntm // 16)
-                    self._bn_bwd = (z((ntm + ng) * 2 * C, torch.float32), z(ntn * (1 + ng), torch.int32))
 
     def forward(self, x, training, bn: Optional["BatchNorm"] = None):
         """``bn``: the BatchNorm that consumes this output (default: ``fwd_bn``); in training its batch
-        statistics come from this launch when it can: the epilogue accumulates their sums (csrc/bn_acc.h,
-        default) or finalises them (``bn_epilogue`` diagnostic) -- no statistics pass over the output."""
+        statistics come from this launch when it can: the epilogue accumulates their sums (csrc/bn_acc.h)
+        -- no statistics pass over the output."""
         self.x = x
         st = self.store
         b = st[self.bias_name] if self.use_bias else None
         bn = bn if bn is not None else self.fwd_bn
-        spec = bacc = None
-        if bn is not None and training and self._bn_fwd is not None:
-            ws, tk = self._bn_fwd
-            spec = dict(ws=ws, ticket=tk, mode=0, vecs=[bn.mean, bn.invstd, bn.run_mean, bn.run_var],
-                        momentum=bn.momentum, eps=bn.eps)
-        elif bn is not None and training and bn.acc_on and self.bacc_ok(False, 0):
+        bacc = None
+        if bn is not None and training and bn.acc_on and self.bacc_ok(False, 0):
             bacc = dict(acc=bn.acc, mode=0)
-        ops.conv_fwd(x, st.weight(self.kernel_name), b, self.out, *self.geom, relu=self.relu, bn=spec,
-                     bacc=bacc)
-        if spec is not None:
-            bn.x = self.out
-            bn._stats_ready = True
+        ops.conv_fwd(x, st.weight(self.kernel_name), b, self.out, *self.geom, relu=self.relu, bacc=bacc)
         if bacc is not None:
             bn.x = self.out
             bn._fwd_acc_ready = True
             bn._acc_nz[0] = True
         return self.out
-
-    def can_emit_bn_grad(self) -> bool:
-        return self._bn_bwd is not None
 
     def backward(self, dy, residual=None, residual_mask=None, dx_mask=None):
         """``residual`` / ``residual_mask`` / ``dx_mask``: the ResNet block join fused into the dgrad
@@ -323,24 +294,16 @@ class Conv2D(Layer):
         gb = st.gradient(self.bias_name) if self.use_bias else None
         ops.conv_wgrad(dy, self.x, st.grad_matrix(kn), gb, self.ws.wgrad, *self.geom)
 
-    def backward_data(self, dy, residual=None, residual_mask=None, dx_mask=None, bn: Optional["BatchNorm"] = None,
-                      bn_acc: Optional[list] = None):
-        """``bn``: the BatchNorm whose output this layer consumed; its backward statistics (dgamma, dbeta,
-        dx coefficients) are finalised inside this launch over the stored (masked) gradient.  ``bn_acc``:
-        the (one or two) BatchNorms whose output gradient this data gradient IS (relu' applied by the
-        epilogue mask): the epilogue accumulates their backward sums (csrc/bn_acc.h) when it can."""
+    def backward_data(self, dy, residual=None, residual_mask=None, dx_mask=None, bn_acc: Optional[list] = None):
+        """``bn_acc``: the (one or two) BatchNorms whose output gradient this data gradient IS (relu' applied
+        by the epilogue mask): the epilogue accumulates their backward sums (csrc/bn_acc.h) when it can."""
         if not self.need_dx:
             return None
         st = self.store
         kn = self.kernel_name
         mask = dx_mask if dx_mask is not None else (self.x if self.in_relu else None)
-        spec = bacc = None
-        if bn is not None:
-            ws, tk = self._bn_bwd
-            spec = dict(ws=ws, ticket=tk, mode=1, x=bn.x,
-                        vecs=[bn.mean, bn.invstd, st[f"{bn.name}/gamma"], st.gradient(f"{bn.name}/gamma"),
-                              st.gradient(f"{bn.name}/beta"), bn.coef])
-        elif bn_acc and mask is not None and all(b.acc_on and b.x is not None for b in bn_acc) and len(bn_acc) <= 2 \
+        bacc = None
+        if bn_acc and mask is not None and all(b.acc_on and b.x is not None for b in bn_acc) and len(bn_acc) <= 2 \
                 and self.bacc_ok(True, 1, two=len(bn_acc) == 2, has_res=residual is not None, has_mask=True):
             b0 = bn_acc[0]
             bacc = dict(acc=b0.acc_b, mode=1, x=b0.x, mean=b0.mean, invstd=b0.invstd)
@@ -348,7 +311,7 @@ class Conv2D(Layer):
                 b1 = bn_acc[1]
                 bacc.update(acc2=b1.acc_b, x2=b1.x, mean2=b1.mean, invstd2=b1.invstd)
         ops.conv_dgrad(dy, st.weight(kn), st.weight_t(kn), self.dx, *self.geom, mask=mask, residual=residual,
-                       residual_mask=residual_mask, bn=spec, bacc=bacc)
+                       residual_mask=residual_mask, bacc=bacc)
         if bacc is not None:
             for b in bn_acc:
                 b._bwd_acc_ready = True
@@ -761,22 +724,6 @@ class BatchNorm(Layer):
                      residual.reshape(-1, self.C) if residual is not None else None, rbn, not training, self.eps)
         return out
 
-    _stats_ready = False
-
-    def fused_forward(self, x, out, residual=None, residual_bn=None, relu=None) -> bool:
-        """Training statistics + apply in one launch when the fused kernel covers this shape (the
-        statistics were not already produced by the conv epilogue); False: nothing launched."""
-        if self._stats_ready or not ops.bn_fused_ok(self.C, x.device):
-            return False
-        self.x = x
-        st = self.store
-        rbn = residual_bn.affine(True) if residual_bn is not None else None
-        ops.bn_fwd_fused(x.reshape(-1, self.C), out.view(-1, self.C), st[f"{self.name}/gamma"], st[f"{self.name}/beta"],
-                         self.mean, self.invstd, self.run_mean, self.run_var, self.ws.bn, self.counter[0],
-                         self.relu if relu is None else relu,
-                         residual.reshape(-1, self.C) if residual is not None else None, rbn, self.momentum, self.eps)
-        return True
-
     def apply_acc(self, x, out, residual=None, residual_bn=None, relu=None):
         """Training out = act(bn(x) [+ residual | + residual_bn(residual)]) with the statistics finalised from
         the producers' accumulated sums (this BN's and the residual BN's): one launch, no statistics pass."""
@@ -809,11 +756,8 @@ class BatchNorm(Layer):
             return self.apply_acc(x, self.out)
         if training and self.acc_on:
             self.drop_acc()
-        if training and self.fused_forward(x, self.out):
-            return self.out
-        if training and not self._stats_ready:
+        if training:
             self.stats(x)
-        self._stats_ready = False
         return self.apply(x, self.out, training)
 
     def _dx_from_acc(self, g):
@@ -824,14 +768,6 @@ class BatchNorm(Layer):
         ops.bn_dx_acc(self.x.reshape(-1, self.C), g.reshape(-1, self.C), self.dx.view(-1, self.C), self.acc_b, self.acc,
                       st[f"{self.name}/gamma"], self.mean, self.invstd, st.gradient(f"{self.name}/gamma"),
                       st.gradient(f"{self.name}/beta"), self.coef)
-        return self.dx
-
-    def backward_dx(self, g):
-        """dx from a gradient ``g`` (relu' already applied) whose statistics the producing conv launch
-        finalised (Conv2D.backward_data(bn=self)) or accumulated (bn_acc=[self]): the dx pass only."""
-        if self._bwd_acc_ready:
-            return self._dx_from_acc(g)
-        ops.bn_dx(self.x.reshape(-1, self.C), g.reshape(-1, self.C), self.dx.view(-1, self.C), self.coef)
         return self.dx
 
     def backward(self, dy, mask=None):
@@ -979,9 +915,8 @@ class ResidualBlock(Layer):
     def _proj_forward(self, x, training):
         p = self.proj.forward(x, training, bn=self.proj_bn)
         self.proj_bn.x = p
-        if training and not self.proj_bn._stats_ready and not self.proj_bn._fwd_acc_ready:
+        if training and not self.proj_bn._fwd_acc_ready:
             self.proj_bn.stats(p)
-        self.proj_bn._stats_ready = False
         return p
 
     def forward(self, x, training):
@@ -1006,22 +941,19 @@ class ResidualBlock(Layer):
                 p = self._proj_forward(x, training)
             r, rbn = p, self.proj_bn
         # out = relu(bn2(h) + shortcut), shortcut = x or proj_bn(proj(x)): with the producers' accumulated
-        # sums one streaming launch finalises both BatchNorms' statistics and joins; else bn2's statistics
-        # and this streaming pass in one launch when the fused kernel covers the shape
+        # sums one streaming launch finalises both BatchNorms' statistics and joins; else the statistics
+        # launches and one apply launch
         if training and self.bn2._fwd_acc_ready and (rbn is None or rbn._fwd_acc_ready):
             self.bn2.apply_acc(h, self.out, residual=r, residual_bn=rbn, relu=True)
             return self.out
+        bn2_stats_done = False  # (a projection BN without sums got its statistics in _proj_forward)
         for b in (self.bn2, rbn):  # (only one of the two has accumulated sums: statistics passes instead)
             if training and b is not None and b._fwd_acc_ready:
                 b.drop_acc()
                 b.stats(b.x)
-                if b is self.bn2:
-                    b._stats_ready = True
-        if training and self.bn2.fused_forward(h, self.out, residual=r, residual_bn=rbn, relu=True):
-            return self.out
-        if training and not self.bn2._stats_ready:
+                bn2_stats_done = bn2_stats_done or b is self.bn2
+        if training and not bn2_stats_done:
             self.bn2.stats(h)
-        self.bn2._stats_ready = False
         self.bn2.apply(h, self.out, training, residual=r, residual_bn=rbn, relu=True)
         return self.out
 
@@ -1061,14 +993,9 @@ class ResidualBlock(Layer):
                 and self.conv2.bacc_ok(True, 1, two=False, has_res=False, has_mask=True)):
             # conv2's data gradient applies bn1's relu' and accumulates bn1's backward sums (csrc/bn_acc.h)
             d = self.conv2.backward_data(d, dx_mask=self.bn1.out, bn_acc=[self.bn1])
-            d = self.bn1.backward_dx(d)
-        elif self.conv2.can_emit_bn_grad() and not self.bn1.grad_premasked:
-            # conv2's data gradient applies bn1's relu' and finalises bn1's backward statistics itself
-            d = self.conv2.backward_data(d, dx_mask=self.bn1.out, bn=self.bn1)
-            d = self.bn1.backward_dx(d)
         else:
             d = self.conv2.backward_data(d)
-            d = self.bn1.backward(d)
+        d = self.bn1.backward(d)  # (the dx pass only when conv2 accumulated the sums)
         if self.proj is not None:
             if pev is not None:
                 main.wait_event(pev)

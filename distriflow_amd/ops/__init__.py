@@ -148,17 +148,6 @@ def dense_wgrad(dy, x, gw, gb, workspace=None, scale=1.0):
 
 
 # ----------------------------------------------------------------------------------- conv2d
-def _bn_kwargs(bn):
-    """igemm launch arguments of an in-launch BatchNorm statistics spec (kernels.h BnEpi):
-    ``bn`` = dict(ws, ticket, mode=0, vecs=[mean, invstd, run_mean, run_var], momentum, eps) or
-    dict(ws, ticket, mode=1, x=bn_input, vecs=[mean, invstd, gamma, dgamma, dbeta, coef], gscale)."""
-    if bn is None:
-        return {}
-    return dict(bn_ws=bn["ws"], bn_ticket=bn["ticket"], bn_mode=int(bn.get("mode", 0)), bn_vecs=list(bn["vecs"]),
-                bn_x=bn.get("x"), bn_momentum=float(bn.get("momentum", 0.1)), bn_eps=float(bn.get("eps", 1e-5)),
-                bn_gscale=float(bn.get("gscale", 1.0)))
-
-
 def _bacc_kwargs(bacc):
     """igemm launch arguments of epilogue-accumulated BatchNorm sums (kernels.h BnAcc, csrc/bn_acc.h):
     ``bacc`` = dict(acc=[nrep][2][N] float64, mode=0) or dict(acc, mode=1, x, mean, invstd[, acc2, x2, mean2,
@@ -174,7 +163,7 @@ def _bacc_kwargs(bacc):
 
 
 def conv_plan(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad=False, **flags) -> dict:
-    """The launch plan (csrc/conv_plan.hip: kernel family, variant, grid, scratch, BatchNorm tiles) of the conv
+    """The launch plan (csrc/conv_plan.hip: kernel family, variant, grid, scratch) of the conv
     forward, or of the data gradient with output [B][H][W][C]; {} without the native extension."""
     m = native.get(build_if_missing=False)
     g = ((B * H * W, C, KH * KW * N, Kpad, _geom(OH, OW, N, H, W, KH, KW, stride, pad), MODE_DGRAD) if dgrad else
@@ -191,35 +180,18 @@ def conv_bacc_ok(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad=False, 
     return bool(p.get("bacc_ok", False))
 
 
-def conv_fwd(x, w, bias, out, KH, KW, stride=1, pad=0, relu=False, bn=None, bacc=None):
-    """NHWC conv: out[B][OH][OW][N]; w = [Npad][Kpad] with K = KH*KW*C.  ``bn``: the consuming
-    BatchNorm's statistics are finalised inside this launch (:func:`_bn_kwargs`, :func:`conv_bn_layout`).
+def conv_fwd(x, w, bias, out, KH, KW, stride=1, pad=0, relu=False, bacc=None):
+    """NHWC conv: out[B][OH][OW][N]; w = [Npad][Kpad] with K = KH*KW*C.
     ``bacc``: the consuming BatchNorm's sums are accumulated by the epilogue (:func:`_bacc_kwargs`)."""
     B, H, W, C = x.shape
     _, OH, OW, N = out.shape
     if x.is_cuda:
         K = KH * KW * C
         _C().igemm_fwd(x, w, bias, None, out, B * OH * OW, N, K, w.shape[1], 0, N,
-                       _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD, relu, 1.0, **_bn_kwargs(bn),
-                       **_bacc_kwargs(bacc))
+                       _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD, relu, 1.0, **_bacc_kwargs(bacc))
     else:
         out.copy_(ref.conv_fwd(x, w, bias, KH, KW, stride, pad, relu, out_hw=(OH, OW)))
     return out
-
-
-def conv_bn_layout(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad=False):
-    """(row tiles, column ranges) of the conv launch (forward, or the data gradient whose output is
-    [B][H][W][C] from an output gradient [B][OH][OW][N]) when it can finalise BatchNorm statistics of
-    its output inside the launch; (0, 0) when it cannot.  Sizes: ws (ntm + ceil(ntm / 16)) * 2 * channels
-    floats, tickets ntn * (1 + ceil(ntm / 16)) int32 (zero-initialised)."""
-    p = conv_plan(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad)
-    return (p["bn_ntm"], p["bn_ntn"]) if p.get("bn_ntm") else (0, 0)
-
-
-def bn_finalize_partials(part, ntm, C, M, mean, invstd, run_mean, run_var, momentum, eps):
-    """mean / invstd (+ running statistics) from a conv epilogue's partial sums (csrc/bn.hip)."""
-    _C().bn_finalize_partials(part, int(ntm), int(C), int(M), mean, invstd, run_mean, run_var, float(momentum),
-                              float(eps))
 
 
 def conv_pool_supported(H, W, C, KH, KW, stride, pad, N) -> bool:
@@ -301,21 +273,19 @@ def kcnn_bwd(x, w1, b1, w2t, dyp, code, slabs, g_w1, g_b1, g_w2, g_b2, step_inc=
                   slabs, g_w1, g_b1, g_w2, g_b2, step_inc=step_inc)
 
 
-def conv_dgrad(dy, w, wt, out, KH, KW, stride=1, pad=0, mask=None, residual=None, residual_mask=None, bn=None,
-               bacc=None):
+def conv_dgrad(dy, w, wt, out, KH, KW, stride=1, pad=0, mask=None, residual=None, residual_mask=None, bacc=None):
     """dX (NHWC [B][H][W][C]) of a conv whose output gradient is dy [B][OH][OW][N].
 
     Epilogue (ResNet block join): dX = (conv^T dy + residual * [residual_mask > 0]) * [mask > 0].
-    ``bn`` (mode 1): dX is the output gradient of a BatchNorm; its backward statistics are finalised
-    inside this launch (:func:`_bn_kwargs`).  ``bacc`` (mode 1): its backward sums are accumulated by
-    the epilogue instead (:func:`_bacc_kwargs`)."""
+    ``bacc`` (mode 1): dX is the output gradient of a BatchNorm; its backward sums are accumulated by
+    the epilogue (:func:`_bacc_kwargs`)."""
     B, OH, OW, N = dy.shape
     _, H, W, C = out.shape
     if dy.is_cuda:
         K = KH * KW * N
         _C().igemm_fwd(dy, wt, None, mask, out, B * H * W, C, K, wt.shape[1], 0, C,
                        _geom(OH, OW, N, H, W, KH, KW, stride, pad), MODE_DGRAD, False, 1.0, residual, residual_mask,
-                       **_bn_kwargs(bn), **_bacc_kwargs(bacc))
+                       **_bacc_kwargs(bacc))
     else:
         dx = ref.conv_dgrad(dy, w, out.shape, KH, KW, stride, pad, None)
         if residual is not None:
@@ -675,7 +645,7 @@ def gap_bwd(dy, dx):
     return dx
 
 
-BN_COUNTERS = 65  # ticket counters of one BN statistics launch: 1 global + 1 per group of 16 (<= 1024) workgroups
+BN_COUNTERS = 64  # ticket counters of one BN statistics launch: 1 global + 1 per group of 16 (<= 1008) workgroups
 
 
 def bn_workspace_floats(C: int) -> int:
@@ -720,26 +690,6 @@ def bn_apply(x2d, y2d, gamma, beta, mean, invstd, relu=False, residual=None, res
             r = residual.reshape(M, C)
             y = y + (aff(r, *residual_bn) if residual_bn is not None else r.float())
         y2d.copy_(torch.relu(y) if relu else y)
-    return y2d
-
-
-def bn_fused_ok(C: int, device) -> bool:
-    """Statistics + streaming pass in one launch (csrc/bn.hip bn_fused_kernel): GPU, C % 8 == 0."""
-    from ..diagnostics import on as diag_on
-
-    return torch.device(device).type == "cuda" and C % 8 == 0 and C <= 1024 and diag_on("bn_fused")
-
-
-def bn_fwd_fused(x2d, y2d, gamma, beta, mean, invstd, run_mean, run_var, ws, counter, relu=False, residual=None,
-                 residual_bn=None, momentum=0.1, eps=1e-5):
-    """Training forward in one launch: batch statistics (mean, invstd, running statistics) and
-    y = act(bn(x) [+ r | + bn_r(r)]).  ``counter``: the layer's 65-word ticket row (word 64: generation)."""
-    M, C = x2d.shape
-    rg = rb = rm = ri = None
-    if residual_bn is not None:
-        rg, rb, rm, ri = residual_bn
-    _C().bn_fwd_fused(x2d, y2d, gamma, beta, mean, invstd, run_mean, run_var, residual, rg, rb, rm, ri, ws, counter,
-                      M, C, relu, momentum, eps)
     return y2d
 
 
@@ -788,9 +738,7 @@ def bn_bwd(x2d, mask2d, dy2d, dx2d, gamma, mean, invstd, dgamma, dbeta, ws, coef
     """Backward of y = bn(x): dx, dgamma, dbeta (scaled by gscale) from dy; g = dy * (mask > 0) when a
     mask (relu' source) is given.  GPU: statistics launch (which also writes the dx coefficients) + dx pass."""
     M, C = x2d.shape
-    if x2d.is_cuda and bn_fused_ok(C, x2d.device) and counter.numel() >= BN_COUNTERS:
-        _C().bn_bwd_fused(x2d, mask2d, dy2d, dx2d, gamma, mean, invstd, dgamma, dbeta, coef, ws, counter, M, C, gscale)
-    elif x2d.is_cuda:
+    if x2d.is_cuda:
         _C().bn_stats_bwd(x2d, mask2d, dy2d, gamma, mean, invstd, dgamma, dbeta, coef, ws, counter, M, C, gscale)
         _C().bn_dx(x2d, mask2d, dy2d, dx2d, coef, M, C)
     else:

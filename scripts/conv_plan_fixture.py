@@ -7,10 +7,11 @@ The shape list is every Conv2D and Dense of lenet5, keras_cnn and resnet18_cifar
 1024}, forward and data gradient, plus a hand list that reaches each branch of the dispatch at its
 smallest shape (``hand_list``; scripts/conv_plan_trace.py launches it under the profiler).  No GPU needed.
 
-The answers were recorded at the last commit that had the three separate shape-only queries
-(``igemm_bacc_supported``, ``igemm64_bn_tiles``, ``igemm64_pool_supported``), which is what makes them a
-reference for the planner that replaced them.  On a build without those bindings the script keeps every
-recorded answer (new entries get none) and only attaches launch tables.
+The answers were recorded at the last commit that had the separate shape-only queries
+(``igemm_bacc_supported``, ``igemm64_pool_supported``), which is what makes them a reference for the planner
+that replaced them.  (The third query, the in-launch BatchNorm statistics tiles, left with that route and is
+no longer recorded.)  On a build without those bindings the script keeps every recorded answer (new entries
+get none) and only attaches launch tables.
 """
 from __future__ import annotations
 
@@ -119,12 +120,11 @@ def edge_list():
 
 
 def record(e, m):
-    """The parent's answers: the three shape-only queries of the native extension."""
+    """The parent's answers: the shape-only queries of the native extension (BatchNorm sums, pooling)."""
     geom = e["geom"] if e["geom"] is not None else [1, 1, 1, 1, 1, 1, 1, 1, 0]
     args = (e["M"], e["N"], e["K"], e["Kpad"], geom, e["mode"])
     e["bacc"] = "".join("1" if m.igemm_bacc_supported(*args, bm, two, res, mask) else "0"
                         for bm, two, res, mask in BACC_VARIANTS)
-    e["bn"] = [int(v) for v in m.igemm64_bn_tiles(*args)]
     c = e["conv"]
     if e["mode"] == 1 and c["KH"] == c["KW"] and isinstance(c["stride"], int) and isinstance(c["pad"], int):
         from distriflow_amd import ops  # (the pool query knows regular geometries only: Net asks it for no other)
@@ -145,8 +145,8 @@ def main():
     for e in entries:
         if hasattr(m, "igemm_bacc_supported"):
             record(e, m)
-        else:  # the three queries are gone: keep what was recorded
-            for k in ("bacc", "bn", "pool"):
+        else:  # the recorded queries are gone: keep their answers
+            for k in ("bacc", "pool"):
                 if k in old.get(e["name"], {}):
                     e[k] = old[e["name"]][k]
         if "launch" in old.get(e["name"], {}):

@@ -111,7 +111,7 @@ def test_conv_plan_matches_recorded_decisions():
     """Over every Conv2D / Dense of lenet5, keras_cnn and resnet18_cifar at five batch sizes and a hand list
     that reaches each branch of the dispatch (scripts/conv_plan_fixture.py), the queries answer what the three
     separate query bindings answered before the planner existed (tests/golden/conv_plan.json: BatchNorm sums
-    in 16 variants, BatchNorm tiles, pooling), and the plan names the kernels, template flags and grids the
+    in 16 variants, pooling), and the plan names the kernels, template flags and grids the
     parent build launched on the GPU for the hand list.  The list keeps reaching every family and both values of
     every variant flag."""
     with open(GOLDEN) as f:
@@ -127,14 +127,12 @@ def test_conv_plan_matches_recorded_decisions():
             assert q["bacc_ok"] == (e["bacc"][i] == "1"), (e["name"], i)
             assert (q["family"] == "invalid") == (not q["bacc_ok"] and e["M"] > 0), (e["name"], i)
             plans.append(q)
-        assert [m.conv_plan(*args, **kw)[k] for k in ("bn_ntm", "bn_ntn")] == e["bn"], e["name"]
         c = e["conv"]
         if c is not None:  # the ops wrappers, as the layers call them
             g = (c["B"], c["H"], c["W"], c["C"], c["OH"], c["OW"], c["N"], c["KH"], c["KW"], c["stride"], c["pad"], c["Kpad"])
             got = "".join("01"[ops.conv_bacc_ok(*g, dgrad=c["dgrad"], mode=bm, two=two, has_res=res, has_mask=mask)]
                           for bm, two, res, mask in BACC_VARIANTS)
             assert got == e["bacc"], e["name"]
-            assert list(ops.conv_bn_layout(*g, dgrad=c["dgrad"])) == e["bn"], e["name"]
             if "pool" in e:
                 assert ops.conv_pool_supported(c["H"], c["W"], c["C"], c["KH"], c["KW"], c["stride"], c["pad"],
                                                c["N"]) == e["pool"], e["name"]
@@ -148,7 +146,6 @@ def test_conv_plan_matches_recorded_decisions():
             flags.setdefault("split", set()).add(q["splits"] > 1)
             flags.setdefault("ks", set()).add(q["ks"] > 1)
             flags.setdefault("scratch", set()).add(q["splitk_floats"] > 0)
-            flags.setdefault("bn", set()).add(q["bn_ntm"] > 0)
     assert families == {"nop", "invalid", "halo_c64", "halo", "igemm64", "smallc", "generic"}
     assert all(v == {False, True} for v in flags.values()), flags
     assert {q["splits"] for q in base} >= {1, 2, 4, 16}
