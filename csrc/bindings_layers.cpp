@@ -132,6 +132,15 @@ py::dict conv_plan_py(int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector
                   "bacc_ok"_a = p.bacc_ok);
 }
 
+// the conv / dense geometry and sizes of a weight gradient (operands and outputs: the caller's)
+dfa::WgradArgs wgrad_shape(int64_t M, int64_t N, int64_t K, int64_t ldd, int64_t lda, const std::vector<int64_t>& geom,
+                           int64_t mode) {
+  dfa::WgradArgs a{};
+  set_conv_geom(a, geom, (int)mode);
+  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.ldd = (int)ldd; a.lda = (int)lda;
+  return a;
+}
+
 void igemm_wgrad_py(torch::Tensor dy, torch::Tensor src, torch::Tensor gw, c10::optional<torch::Tensor> gb,
                     torch::Tensor workspace, int64_t M, int64_t N, int64_t K, int64_t ldd, int64_t lda,
                     std::vector<int64_t> geom, int64_t mode, double scale) {
@@ -141,8 +150,7 @@ void igemm_wgrad_py(torch::Tensor dy, torch::Tensor src, torch::Tensor gw, c10::
   need(workspace, at::kFloat, "workspace");
   TORCH_CHECK(gw.numel() >= N * K, "gw too small");
   TORCH_CHECK(dy.numel() >= (M - 1) * ldd + N, "dy too small");
-  dfa::WgradArgs a{};
-  set_conv_geom(a, geom, (int)mode);
+  dfa::WgradArgs a = wgrad_shape(M, N, K, ldd, lda, geom, mode);
   if (mode == 0) {
     TORCH_CHECK(src.numel() >= (M - 1) * lda + K, "src too small");
   } else {
@@ -154,11 +162,33 @@ void igemm_wgrad_py(torch::Tensor dy, torch::Tensor src, torch::Tensor gw, c10::
   a.dy = reinterpret_cast<const dfa::bf16*>(dy.data_ptr());
   a.src = reinterpret_cast<const dfa::bf16*>(src.data_ptr());
   a.gw = gw.data_ptr<float>();
-  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.ldd = (int)ldd; a.lda = (int)lda;
   a.with_bias = a.gb ? 1 : 0;
   a.scale = (float)scale;
-  check_hip(dfa::igemm_wgrad(a, (int)mode, workspace.data_ptr<float>(), (size_t)workspace.numel(), cur_stream()),
-            "igemm_wgrad");
+  // the one plan of this launch: a smaller workspace gives fewer splits, but the C = 1 kernels always
+  // write at least one slab
+  const dfa::WgradPlan plan = dfa::wgrad_plan(a, (int)mode, (size_t)workspace.numel());
+  TORCH_CHECK(workspace.numel() >= plan.scratch_floats, "igemm_wgrad: workspace of ", workspace.numel(),
+              " floats, the launch writes ", plan.scratch_floats);
+  check_hip(dfa::igemm_wgrad(a, plan, (int)mode, workspace.data_ptr<float>(), cur_stream()), "igemm_wgrad");
+}
+
+// The plan of a weight gradient with these shapes and this workspace size, before any tensor exists (16-byte
+// aligned dummy operands, as conv_plan_py).
+py::dict wgrad_plan_py(int64_t M, int64_t N, int64_t K, int64_t ldd, int64_t lda, std::vector<int64_t> geom,
+                       int64_t mode, bool with_bias, int64_t ws_floats) {
+  static dfa::bf16 dummy[8] __attribute__((aligned(16)));
+  static float dvec[4] __attribute__((aligned(16)));
+  dfa::WgradArgs a = wgrad_shape(M, N, K, ldd, lda, geom, mode);
+  a.dy = dummy; a.src = dummy; a.gw = dvec;
+  if (with_bias) a.gb = dvec, a.with_bias = 1;
+  const dfa::WgradPlan p = dfa::wgrad_plan(a, (int)mode, (size_t)std::max<int64_t>(ws_floats, 0));
+  static const char* const kFamily[] = {"nop", "halo", "tr", "c1", "smallc", "generic"};
+  using namespace pybind11::literals;
+  return py::dict("family"_a = kFamily[p.family], "BN"_a = p.BN, "BK"_a = p.BK, "WN"_a = p.WN, "WK"_a = p.WK,
+                  "BM"_a = p.BM, "MAXOCC"_a = p.MAXOCC, "dvec"_a = p.dvec, "xvec"_a = p.xvec, "groups"_a = p.groups,
+                  "R"_a = p.R, "TI"_a = p.TI, "tps"_a = p.tps, "splits"_a = p.splits, "m_per_split"_a = p.m_per_split,
+                  "grid"_a = p.grid, "block"_a = p.block, "reduce"_a = p.reduce, "scratch_floats"_a = p.scratch_floats,
+                  "wanted_floats"_a = p.wanted_floats, "capped"_a = p.capped);
 }
 
 void maxpool_fwd_py(torch::Tensor x, torch::Tensor y, int64_t B, int64_t H, int64_t W, int64_t C, int64_t P,
@@ -911,6 +941,9 @@ void bind_layers(py::module_& m) {
               "unpool2");
   });
   m.def("igemm_wgrad", &igemm_wgrad_py, "implicit-GEMM MFMA weight gradient (split-m slabs + reduce)");
+  m.def("wgrad_plan", &wgrad_plan_py, "the launch plan of igemm_wgrad for these shapes and this workspace size, as a dict",
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("ldd"), py::arg("lda"), py::arg("geom"), py::arg("mode"),
+        py::arg("with_bias"), py::arg("ws_floats"));
   m.def("maxpool_fwd", &maxpool_fwd_py, py::arg("x"), py::arg("y"), py::arg("B"), py::arg("H"), py::arg("W"),
         py::arg("C"), py::arg("P"), py::arg("drop_p") = 0.0, py::arg("drop_seed") = 0,
         py::arg("drop_step") = py::none(), py::arg("drop_step_add") = 0);

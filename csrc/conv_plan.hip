@@ -1,4 +1,5 @@
-// The launch plan of a forward / data-gradient implicit GEMM (kernels.h ConvPlan): host code only.
+// The launch plans of the implicit GEMMs: forward / data gradient (kernels.h ConvPlan) and weight gradient
+// (kernels.h WgradPlan, at the end of this file).  Host code only.
 //
 // Kernel order: pooled epilogue (igemm64 only), the 3x3 halo kernel, igemm64, the C = 1 kernels, the generic
 // kernel.  Every tile shape, split and variant is chosen here, once: the launchers pick the instantiation the
@@ -48,9 +49,11 @@ bool igemm64_fast_ok(const IGemmArgs& a, int mode) {
   return sbytes < (1LL << 30) && wbytes < (1LL << 30);
 }
 
-bool c3_geom(int H, int W, int& R, int& TI) {
-  if (W < 4 || W > 64 || kCP % W != 0) return false;
-  const int rpt = kCP / W;
+// tile geometry of the halo kernels on an H x W image: R rows of TI images per tile of P output pixels;
+// false if the image does not tile (each caller adds its own staging limits)
+bool halo_geom(int H, int W, int P, int& R, int& TI) {
+  if (W < 4 || W > 64 || P % W != 0) return false;
+  const int rpt = P / W;
   if (rpt <= H) {
     if (H % rpt != 0) return false;
     R = rpt, TI = 1;
@@ -58,7 +61,7 @@ bool c3_geom(int H, int W, int& R, int& TI) {
     if (rpt % H != 0) return false;
     R = H, TI = rpt / H;
   }
-  return TI * (R + 2) * (W + 2) <= kCXR && TI * (R + 2) * (W == 16 ? 32 : W + 2) <= kCXL;
+  return true;
 }
 
 bool conv3_halo_supported(const IGemmArgs& a, int mode, int& R, int& TI) {
@@ -67,7 +70,8 @@ bool conv3_halo_supported(const IGemmArgs& a, int mode, int& R, int& TI) {
   return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.SH == a.OH && a.SW == a.OW && a.SC % 64 == 0 &&
          a.N % 64 == 0 && a.K == 9 * a.SC && a.Kpad >= a.K && a.Kpad % 8 == 0 && a.ldc % 4 == 0 && !a.bias &&
          !a.out_f32 && !a.drop.on && !a.pool_code &&
-         a.M % kCP == 0 && a.M % (a.OH * a.OW) == 0 && c3_geom(a.OH, a.OW, R, TI) &&
+         a.M % kCP == 0 && a.M % (a.OH * a.OW) == 0 && halo_geom(a.OH, a.OW, kCP, R, TI) &&
+         TI * (R + 2) * (a.OW + 2) <= kCXR && TI * (R + 2) * (a.OW == 16 ? 32 : a.OW + 2) <= kCXL &&
          (long long)a.M * a.ldc * 2 < (1LL << 32) &&  // one 32-bit byte offset per epilogue element
          aligned(a.src, 15) && aligned(a.w, 15) && aligned(a.out, 7) &&
          (((uintptr_t)a.res | (uintptr_t)a.resmask | (uintptr_t)a.mask) & 7) == 0;
@@ -190,6 +194,114 @@ ConvPlan conv_plan(const IGemmArgs& a, int mode) {
   }
   p.bacc_ok = p.family != CONV_INVALID && bacc_ok(a, mode, p.family);
   if (a.bacc.acc && !p.bacc_ok) p.family = CONV_INVALID;
+  return p;
+}
+
+// ---------------------------------------------------------------------------------- weight gradient
+namespace {
+
+bool wgrad_halo_supported(const WgradArgs& a, int mode, int& R, int& TI) {
+  static const int on = diag_int("wgrad_halo", 1);
+  return on && mode == MODE_FWD && !a.with_bias && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 &&
+         a.OH == a.SH && a.OW == a.SW && a.SC % 64 == 0 && a.N % 64 == 0 && a.K == 9 * a.SC && a.ldd % 8 == 0 &&
+         a.M % kHP == 0 && a.M == a.OH * a.OW * (a.M / (a.OH * a.OW)) && halo_geom(a.SH, a.SW, kHP, R, TI) &&
+         TI * (R + 2) * (a.SW + 2) <= kHXR && aligned(a.dy, 15) && aligned(a.src, 15);
+}
+
+bool wgrad_tr_supported(const WgradArgs& a, int mode) {
+  return mode == MODE_FWD && (!a.with_bias || a.gb != nullptr) && a.SC % 8 == 0 && a.N % 8 == 0 && a.ldd % 8 == 0 && a.M > 0 &&
+         a.OH > 0 && a.OW > 0 && aligned(a.dy, 15) && aligned(a.src, 15);
+}
+
+bool smallc_wgrad_supported(const WgradArgs& a, int mode) {
+  return mode == MODE_FWD && a.SC == 1 && a.K < kSmallMaxK && a.N % 8 == 0 && a.N <= kSmallMaxN &&
+         a.N * (a.K + 1) <= 8 * 256 && a.ldd % 8 == 0 && aligned(a.dy, 15) && a.OH > 0 && a.OW > 0 &&
+         (!a.with_bias || a.gb != nullptr);
+}
+
+// The split of a reduction of `rows` (a launch of `tiles` output tiles) over workgroups: enough splits for
+// `target` workgroups, each reducing at least `min_rows`, as many as `cap` floats of slabs (`slab` each) hold;
+// the rows per split are rounded up to `quantum` and the split count re-rounded to what that leaves.
+int split_rows(int target, int tiles, int rows, int quantum, int min_rows, long long slab, long long cap, int& per) {
+  int s = max(1, min(cdiv(target, tiles), cdiv(rows, min_rows)));
+  while (s > 1 && s * slab > cap) --s;
+  per = round_up(cdiv(rows, s), quantum);
+  return cdiv(rows, per);
+}
+
+}  // namespace
+
+WgradPlan wgrad_plan(const WgradArgs& a, int mode, size_t ws_floats) {
+  WgradPlan p{};
+  p.family = WGRAD_NOP, p.splits = 1, p.block = 256;
+  if (a.M <= 0 || a.N <= 0) return p;
+  const long long unlimited = 1LL << 62, ws = ws_floats < (size_t)unlimited ? (long long)ws_floats : unlimited;
+  const int Kt = a.K + (a.with_bias ? 1 : 0);
+  const long long slab = (long long)a.N * Kt;  // (every family: with_bias is 0 on the halo kernel)
+  // the specialised kernels are conv only (MODE_FWD) and refuse an irregular geometry
+  int target, tiles, rows = a.M, quantum, min_rows, per;
+  if (!a.irregular && wgrad_halo_supported(a, mode, p.R, p.TI)) {
+    // one 8-wave workgroup per CU (140 KB of LDS), the 64-pixel tiles split over them
+    p.family = WGRAD_HALO;
+    static const int groups = diag_int("halo_groups", 2) == 1 ? 1 : 2;
+    static const int halo_wg = diag_int("halo_wg", groups == 2 ? 256 : 512);
+    p.groups = groups, p.block = 256 * groups;
+    target = halo_wg, tiles = (a.N / 64) * (a.SC / 64), rows = a.M / kHP, quantum = 1, min_rows = 1;
+  } else if (!a.irregular && wgrad_tr_supported(a, mode)) {
+    p.family = WGRAD_TR;
+    static const int t128 = diag_int("wgrad128", 32);
+    p.BK = 128, p.WN = 2, p.WK = 2, p.BM = 64, p.MAXOCC = 4;
+    if (a.N >= 128) {
+      // 128 x 128 tiles: 32 rows per step at 3 workgroups per CU (170 VGPRs each: no spills).  At 4 per CU
+      // that needs more than their 128 VGPRs and spills, which the inline-asm loads (destinations unprotected
+      // until their counted wait) cannot tolerate: the 4-per-CU variant stays at 64 rows.
+      p.BN = 128;
+      if (t128 == 32) p.BM = 32, p.MAXOCC = 3;
+    } else if (a.N <= 32) {
+      p.BN = 32, p.WN = 1, p.WK = 4;  // Keras CNN conv2: no empty rows
+    } else {
+      // 64-channel tiles step 32 rows at a time: 36.9 KB of LDS -> 4 workgroups per CU (ResNet layer 1:
+      // 104 -> 82 us)
+      p.BN = 64, p.BM = 32;
+    }
+    // about two workgroups per CU (73.7 KB of LDS each at BM = 64), each reducing >= 256 rows
+    static const int wgrad_wg = diag_int("wgrad_wg", 512);
+    target = wgrad_wg, tiles = cdiv(a.N, p.BN) * cdiv(a.K + (a.with_bias ? 8 : 0), p.BK), quantum = p.BM, min_rows = 256;
+  } else if (!a.irregular && smallc_wgrad_supported(a, mode)) {
+    // one slab per workgroup, always reduced: the image-resident kernel when its slabs fit, else persistent
+    // workgroups, halved until theirs do (a single slab is written whatever the workspace: callers check
+    // scratch_floats)
+    const bool c1 = c1_ok(a.SC, a.KH, a.KW, a.stride, a.pad, a.N, a.SH, a.SW) && a.K == 9;
+    const int nb = cdiv(a.M / (a.OH * a.OW), C1_IMGS);
+    int grid = min(cdiv(a.M, 64), 1024);
+    p.wanted_floats = (c1 ? nb : grid) * slab;
+    if (c1 && nb * slab <= ws) {
+      p.family = WGRAD_C1, grid = nb;
+    } else {
+      p.family = WGRAD_SMALLC;
+      while (grid > 1 && grid * slab > ws) grid /= 2;
+    }
+    p.splits = p.grid = grid, p.reduce = true, p.scratch_floats = grid * slab;
+    p.capped = p.scratch_floats < p.wanted_floats;
+    return p;
+  } else {
+    p.family = WGRAD_GENERIC;
+    p.dvec = aligned(a.dy, 15) && a.ldd % 8 == 0;
+    p.xvec = aligned(a.src, 15) && (mode == MODE_DIRECT ? a.lda : a.SC) % 8 == 0;
+    p.BK = 64, p.WN = 2, p.WK = 2;
+    p.BN = a.N <= 16 ? 16 : a.N <= 32 ? 32 : 64;
+    if (p.BN == 16) p.WN = 1, p.WK = 4;
+    // enough splits to put ~2 workgroups on each of the 256 CUs, each reducing >= 128 rows
+    target = 512, tiles = cdiv(a.N, p.BN) * cdiv(Kt, p.BK), quantum = 32, min_rows = 128;
+  }
+  const int want = split_rows(target, tiles, rows, quantum, min_rows, slab, unlimited, per);
+  p.splits = split_rows(target, tiles, rows, quantum, min_rows, slab, ws, per);
+  (p.family == WGRAD_HALO ? p.tps : p.m_per_split) = per;
+  p.grid = tiles * p.splits;
+  p.reduce = p.splits > 1;
+  p.scratch_floats = p.reduce ? p.splits * slab : 0;
+  p.wanted_floats = want > 1 ? want * slab : 0;
+  p.capped = p.scratch_floats < p.wanted_floats;
   return p;
 }
 

@@ -11,8 +11,8 @@
 //     (relu'(x_prev) fused into dgrad), bf16 or fp32 store.
 //
 //   igemm_wgrad  G[n][k] = sum_m dY[m][n] * A[m][k]  (+ bias column k==K: sum_m dY[m][n])
-//     split over m into fp32 slabs (deterministic), then wgrad_reduce sums the slabs straight
-//     into the flat gradient buffer that RCCL all-reduces.
+//     split over m into fp32 slabs (deterministic), then slab_reduce (csrc/convpool.hip) sums the slabs
+//     straight into the flat gradient buffer that RCCL all-reduces.
 //
 // Tiling: 256-thread workgroups (4 waves of 64), v_mfma_f32_16x16x32_bf16, BK = 32,
 // double-buffered LDS with register prefetch of the next tile (global loads of tile k+1 are in
@@ -522,21 +522,6 @@ __global__ void __launch_bounds__(256) igemm_wgrad_kernel(WgradArgs a) {
   }
 }
 
-__global__ void wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ gw,
-                                    float* __restrict__ gb, int N, int K, int Kt, int splits,
-                                    float scale) {
-  const int total = N * Kt;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-    float s = 0.f;
-    for (int p = 0; p < splits; ++p) s += partial[(long long)p * total + idx];
-    const int n = idx / Kt, k = idx - n * Kt;
-    if (k < K)
-      gw[(long long)n * K + k] = s * scale;
-    else
-      gb[n] = s * scale;
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // host launchers
 template <int BM, int BN, int WM, int WN, int MODE, bool VEC>
@@ -583,55 +568,39 @@ hipError_t igemm_fwd(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_
   return dropout(o, o, nullptr, (long long)a.M * a.N, a.drop.p, a.drop.seed, a.drop.step, st);
 }
 
-template <int BN, int BKO, int WN, int WK, int MODE, bool DVEC, bool XVEC>
-static hipError_t launch_wgrad_cfg(WgradArgs a, float* workspace, size_t ws_floats, hipStream_t st) {
-  const int Kt = a.K + (a.with_bias ? 1 : 0);
-  const int tiles = cdiv(a.N, BN) * cdiv(Kt, BKO);
-  // enough splits to put ~2 workgroups on each of the 256 CUs, each reducing >= 128 rows
-  int splits = cdiv(512, tiles);
-  splits = min(splits, cdiv(a.M, 128));
-  splits = max(splits, 1);
-  while (splits > 1 && (size_t)splits * a.N * Kt > ws_floats) --splits;
-  a.m_per_split = round_up(cdiv(a.M, splits), 32);
-  splits = cdiv(a.M, a.m_per_split);
-  a.splits = splits;
-  a.partial = workspace;
-  hipLaunchKernelGGL((igemm_wgrad_kernel<BN, BKO, WN, WK, MODE, DVEC, XVEC>), dim3(tiles * splits), dim3(256), 0,
-                     st, a);
-  DFA_HIP_CHECK(hipGetLastError());
-  if (splits > 1) DFA_HIP_CHECK(slab_reduce(workspace, a.gw, a.gb, a.N, a.K, Kt, splits, a.scale, st));
-  return hipSuccess;
-}
-
+// the generic weight-gradient kernel in the instantiation the plan names (csrc/conv_plan.hip wgrad_plan)
 template <int MODE, bool DVEC, bool XVEC>
-static hipError_t launch_wgrad_mode(const WgradArgs& a, float* ws, size_t wsf, hipStream_t st) {
-  if (a.N <= 16) return launch_wgrad_cfg<16, 64, 1, 4, MODE, DVEC, XVEC>(a, ws, wsf, st);
-  if (a.N <= 32) return launch_wgrad_cfg<32, 64, 2, 2, MODE, DVEC, XVEC>(a, ws, wsf, st);
-  return launch_wgrad_cfg<64, 64, 2, 2, MODE, DVEC, XVEC>(a, ws, wsf, st);
+static hipError_t launch_wgrad_mode(const WgradArgs& a, const WgradPlan& p, hipStream_t st) {
+  if (p.BN == 16)
+    hipLaunchKernelGGL((igemm_wgrad_kernel<16, 64, 1, 4, MODE, DVEC, XVEC>), dim3(p.grid), dim3(p.block), 0, st, a);
+  else if (p.BN == 32)
+    hipLaunchKernelGGL((igemm_wgrad_kernel<32, 64, 2, 2, MODE, DVEC, XVEC>), dim3(p.grid), dim3(p.block), 0, st, a);
+  else
+    hipLaunchKernelGGL((igemm_wgrad_kernel<64, 64, 2, 2, MODE, DVEC, XVEC>), dim3(p.grid), dim3(p.block), 0, st, a);
+  return hipGetLastError();
 }
 
 template <int MODE>
-static hipError_t launch_wgrad_x(const WgradArgs& a, bool dvec, bool xvec, float* ws, size_t wsf, hipStream_t st) {
-  if (dvec) {
-    return xvec ? launch_wgrad_mode<MODE, true, true>(a, ws, wsf, st) : launch_wgrad_mode<MODE, true, false>(a, ws, wsf, st);
-  }
-  return xvec ? launch_wgrad_mode<MODE, false, true>(a, ws, wsf, st) : launch_wgrad_mode<MODE, false, false>(a, ws, wsf, st);
+static hipError_t launch_wgrad_x(WgradArgs a, const WgradPlan& p, float* ws, hipStream_t st) {
+  a.m_per_split = p.m_per_split, a.splits = p.splits, a.partial = ws;
+  if (p.dvec) return p.xvec ? launch_wgrad_mode<MODE, true, true>(a, p, st) : launch_wgrad_mode<MODE, true, false>(a, p, st);
+  return p.xvec ? launch_wgrad_mode<MODE, false, true>(a, p, st) : launch_wgrad_mode<MODE, false, false>(a, p, st);
 }
 
 hipError_t igemm_wgrad(const WgradArgs& a, int mode, float* workspace, size_t ws_floats, hipStream_t st) {
-  if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  const bool dvec = ((uintptr_t)a.dy & 15) == 0 && a.ldd % 8 == 0;
-  if (mode == MODE_DIRECT) {
-    const bool xvec = ((uintptr_t)a.src & 15) == 0 && a.lda % 8 == 0;
-    return launch_wgrad_x<MODE_DIRECT>(a, dvec, xvec, workspace, ws_floats, st);
-  }
-  if (!a.irregular) {
-    if (wgrad_halo_supported(a, mode)) return wgrad_halo(a, workspace, ws_floats, st);
-    if (wgrad_tr_supported(a, mode)) return wgrad_tr(a, workspace, ws_floats, st);
-    if (smallc_wgrad_supported(a, mode)) return smallc_wgrad(a, workspace, ws_floats, st);
-  }
-  const bool xvec = ((uintptr_t)a.src & 15) == 0 && a.SC % 8 == 0;
-  return launch_wgrad_x<MODE_FWD>(a, dvec, xvec, workspace, ws_floats, st);
+  return igemm_wgrad(a, wgrad_plan(a, mode, ws_floats), mode, workspace, st);
+}
+
+hipError_t igemm_wgrad(const WgradArgs& a, const WgradPlan& p, int mode, float* workspace, hipStream_t st) {
+  if (p.family == WGRAD_NOP) return hipSuccess;
+  if (p.family == WGRAD_HALO) DFA_HIP_CHECK(wgrad_halo(a, p, workspace, st));
+  else if (p.family == WGRAD_TR) DFA_HIP_CHECK(wgrad_tr(a, p, workspace, st));
+  else if (p.family == WGRAD_C1 || p.family == WGRAD_SMALLC) DFA_HIP_CHECK(smallc_wgrad(a, p, workspace, st));
+  else if (mode == MODE_DIRECT) DFA_HIP_CHECK(launch_wgrad_x<MODE_DIRECT>(a, p, workspace, st));
+  else DFA_HIP_CHECK(launch_wgrad_x<MODE_FWD>(a, p, workspace, st));
+  if (!p.reduce) return hipSuccess;
+  const int Kt = a.K + (a.with_bias ? 1 : 0);
+  return slab_reduce(workspace, a.gw, a.with_bias ? a.gb : nullptr, a.N, a.K, Kt, p.splits, a.scale, st);
 }
 
 }  // namespace dfa

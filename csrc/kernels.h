@@ -141,6 +141,32 @@ constexpr int kC64XP = 7;             // 64 -> 64 kernel: halo staging passes pe
 constexpr int kC64XR = 32 * kC64XP;
 constexpr int kC3Tickets = 1024;      // tickets of a folded two-split launch (one per output tile)
 
+// The one decision of a weight-gradient launch (csrc/conv_plan.hip wgrad_plan): the kernel, its template
+// instantiation, the split over m, the launch shape and the fp32 slabs it writes into the workspace.
+// igemm_wgrad and the launchers below switch on it, the bindings check the workspace against it.  The
+// workspace size is an input: a workspace too small for the splits the policy asks for gives fewer splits
+// (another summation order), which `capped` reports.
+enum WgradFamily { WGRAD_NOP, WGRAD_HALO, WGRAD_TR, WGRAD_C1, WGRAD_SMALLC, WGRAD_GENERIC };
+struct WgradPlan {
+  int family;                  // WGRAD_NOP: M or N <= 0
+  int BN, BK, WN, WK;          // tr / generic: output tile and its wave grid
+  int BM, MAXOCC;              // tr: rows per step, workgroups per CU the register cap allows
+  bool dvec, xvec;             // generic: 16-byte loads of dY / the activation
+  int groups, R, TI, tps;      // halo: 4-wave groups per workgroup; image rows / images per 64-pixel tile; tiles
+                               // per split
+  int splits, m_per_split;     // slabs (C1 / smallc: one per workgroup); tr / generic: rows per split
+  int grid, block;
+  bool reduce;                 // a slab_reduce launch follows (else the kernel writes gw itself)
+  long long scratch_floats;    // floats the launch writes into the workspace (0: none)
+  long long wanted_floats;     // the same with an unlimited workspace
+  bool capped;                 // scratch_floats < wanted_floats
+};
+WgradPlan wgrad_plan(const WgradArgs& a, int mode, size_t ws_floats);
+// halo weight-gradient staging limits (csrc/wgrad_halo.hip)
+constexpr int kHP = 64;               // output pixels per tile
+constexpr int kHXP = 5;               // halo staging passes of 32 rows
+constexpr int kHXR = 32 * kHXP;       // halo rows per buffer (>= TI * (R+2) * (W+2))
+
 hipError_t igemm_fwd(const IGemmArgs& a, int mode, hipStream_t st);  // plans, then launches
 hipError_t igemm_fwd(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st);
 // dY of a pooled conv from the pooled gradient and the argmax codes (NHWC, 2x2 windows)
@@ -149,15 +175,15 @@ hipError_t unpool2(const bf16* dyp, const uint8_t* code, bf16* dy, int B, int OH
 hipError_t igemm64(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st);
 // out = epilogue(sum over a.splits of a.splitk_ws[s][M][N]) in a fixed order (igemm64's split-K combine)
 hipError_t igemm64_splitk_combine(const IGemmArgs& a, hipStream_t st);
-hipError_t igemm_wgrad(const WgradArgs& a, int mode, float* workspace, size_t ws_floats, hipStream_t st);
-// conv weight gradient with transposed LDS reads (csrc/wgrad_tr.hip): conv, C % 8 == 0, no bias
-bool wgrad_tr_supported(const WgradArgs& a, int mode);
-hipError_t wgrad_tr(const WgradArgs& a, float* workspace, size_t ws_floats, hipStream_t st);
+hipError_t igemm_wgrad(const WgradArgs& a, int mode, float* workspace, size_t ws_floats, hipStream_t st);  // plans, then launches
+// the workspace holds at least p.scratch_floats floats (the C1 / smallc kernels always write a slab)
+hipError_t igemm_wgrad(const WgradArgs& a, const WgradPlan& p, int mode, float* workspace, hipStream_t st);
+// conv weight gradient with transposed LDS reads (csrc/wgrad_tr.hip): conv, C % 8 == 0
+hipError_t wgrad_tr(WgradArgs a, const WgradPlan& p, float* workspace, hipStream_t st);
 // 3x3 stride-1 pad-1 conv weight gradient, halo-tiled LDS staging (csrc/wgrad_halo.hip): C, N % 64 == 0
-bool wgrad_halo_supported(const WgradArgs& a, int mode);
+hipError_t wgrad_halo(const WgradArgs& a, const WgradPlan& p, float* workspace, hipStream_t st);
 // 3x3 stride-1 pad-1 conv forward / data gradient, halo-tiled LDS staging (csrc/conv3_halo.hip)
 hipError_t conv3_halo(const IGemmArgs& a, const ConvPlan& p, int mode, hipStream_t st);
-hipError_t wgrad_halo(const WgradArgs& a, float* workspace, size_t ws_floats, hipStream_t st);
 hipError_t maxpool_fwd(const bf16* x, bf16* y, int B, int H, int W, int C, int P, hipStream_t st,
                        DropSpec drop = DropSpec{});
 hipError_t maxpool_bwd(const bf16* x, const bf16* dy, bf16* dx, int B, int H, int W, int C, int P, int relu_fused,
@@ -730,10 +756,16 @@ long long dwconv_wgrad_slab_floats(const DwConvGeom& g);
 hipError_t dwconv_wgrad(const bf16* dy, const bf16* x, float* gw, float* gb, float* ws, size_t ws_floats,
                         const DwConvGeom& g, hipStream_t st);
 
-// Direct convolution for C_in <= 4 (csrc/smallc.hip); igemm_fwd / igemm_wgrad dispatch to it.
+// Direct convolution for C_in = 1 (csrc/smallc.hip); igemm_fwd / igemm_wgrad dispatch to it.
+constexpr int kSmallMaxK = 64, kSmallMaxN = 64;
+// the image-resident 3x3 x 32-channel variants: images per workgroup, output channels
+constexpr int C1_IMGS = 2, C1_N = 32;
+inline bool c1_ok(int SC, int KH, int KW, int stride, int pad, int N, int SH, int SW) {
+  return SC == 1 && KH == 3 && KW == 3 && stride == 1 && N == C1_N && pad >= 0 && pad <= 1 &&
+         (SH + 2 * pad) <= 34 && (SW + 2 * pad) <= 34;
+}
 bool smallc_fwd_supported(const IGemmArgs& a, int mode);
 hipError_t smallc_fwd(const IGemmArgs& a, hipStream_t st);
-bool smallc_wgrad_supported(const WgradArgs& a, int mode);
-hipError_t smallc_wgrad(const WgradArgs& a, float* ws, size_t ws_floats, hipStream_t st);
+hipError_t smallc_wgrad(const WgradArgs& a, const WgradPlan& p, float* ws, hipStream_t st);
 
 }  // namespace dfa

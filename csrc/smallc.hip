@@ -18,8 +18,6 @@ namespace dfa {
 
 namespace {
 
-constexpr int kSmallMaxK = 64, kSmallMaxN = 64;
-
 __global__ void __launch_bounds__(256) smallc_fwd_kernel(IGemmArgs a, FastDiv d_ow, FastDiv d_ohw) {
   __shared__ float wl[kSmallMaxK * kSmallMaxN];
   __shared__ float bl[kSmallMaxN];
@@ -157,7 +155,7 @@ __global__ void __launch_bounds__(256) smallc_wgrad_kernel(WgradArgs a, FastDiv 
 //   wgrad  : 80 fp32 accumulators (8 channels x (9 taps + bias)) per thread over the workgroup's
 //            pixels, four dY rows in flight per thread; wave reduction by lane shuffles, workgroup
 //            reduction in LDS, one slab [32][10] per workgroup for slab_reduce (fixed order)
-constexpr int C1_IMGS = 2, C1_N = 32, C1_MAXP = 34 * 34;
+constexpr int C1_MAXP = 34 * 34;  // (C1_IMGS, C1_N, c1_ok: kernels.h)
 
 __device__ __forceinline__ void c1_stage(const bf16* __restrict__ src, int b0, int nimg, int SH, int SW, int pad,
                                          float* xs) {
@@ -286,11 +284,6 @@ __global__ void __launch_bounds__(256) c1_wgrad_kernel(WgradArgs a, int B, FastD
   }
 }
 
-bool c1_ok(int SC, int KH, int KW, int stride, int pad, int N, int SH, int SW) {
-  return SC == 1 && KH == 3 && KW == 3 && stride == 1 && N == C1_N && pad >= 0 && pad <= 1 &&
-         (SH + 2 * pad) <= 34 && (SW + 2 * pad) <= 34;
-}
-
 }  // namespace
 
 bool smallc_fwd_supported(const IGemmArgs& a, int mode) {
@@ -311,30 +304,14 @@ hipError_t smallc_fwd(const IGemmArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-bool smallc_wgrad_supported(const WgradArgs& a, int mode) {
-  return mode == MODE_FWD && a.SC == 1 && a.K < kSmallMaxK && a.N % 8 == 0 && a.N <= kSmallMaxN &&
-         a.N * (a.K + 1) <= 8 * 256 && a.ldd % 8 == 0 && ((uintptr_t)a.dy & 15) == 0 && a.OH > 0 && a.OW > 0 &&
-         (!a.with_bias || a.gb != nullptr);
-}
-
-hipError_t smallc_wgrad(const WgradArgs& a, float* ws, size_t ws_floats, hipStream_t st) {
-  const int Kt = a.K + (a.with_bias ? 1 : 0);
-  const int P = a.N * Kt;
-  if (c1_ok(a.SC, a.KH, a.KW, a.stride, a.pad, a.N, a.SH, a.SW) && a.K == 9) {
-    const int B = a.M / (a.OH * a.OW);
-    const int nb = cdiv(B, C1_IMGS);
-    if ((size_t)nb * P <= ws_floats) {
-      hipLaunchKernelGGL(c1_wgrad_kernel, dim3(nb), dim3(256), 0, st, a, B, make_fastdiv((unsigned)a.OW), ws);
-      DFA_HIP_CHECK(hipGetLastError());
-      return slab_reduce(ws, a.gw, a.with_bias ? a.gb : nullptr, a.N, a.K, Kt, nb, a.scale, st);
-    }
-  }
-  int grid = min(cdiv(a.M, 64), 1024);
-  while (grid > 1 && (size_t)grid * P > ws_floats) grid /= 2;
+// one slab per workgroup of the plan's grid (csrc/conv_plan.hip wgrad_plan); igemm_wgrad reduces them
+hipError_t smallc_wgrad(const WgradArgs& a, const WgradPlan& p, float* ws, hipStream_t st) {
   const FastDiv d_ow = make_fastdiv((unsigned)a.OW), d_ohw = make_fastdiv((unsigned)(a.OH * a.OW));
-  hipLaunchKernelGGL(smallc_wgrad_kernel, dim3(grid), dim3(256), 0, st, a, d_ow, d_ohw, ws);
-  DFA_HIP_CHECK(hipGetLastError());
-  return slab_reduce(ws, a.gw, a.with_bias ? a.gb : nullptr, a.N, a.K, Kt, grid, a.scale, st);
+  if (p.family == WGRAD_C1)
+    hipLaunchKernelGGL(c1_wgrad_kernel, dim3(p.grid), dim3(p.block), 0, st, a, a.M / (a.OH * a.OW), d_ow, ws);
+  else
+    hipLaunchKernelGGL(smallc_wgrad_kernel, dim3(p.grid), dim3(p.block), 0, st, a, d_ow, d_ohw, ws);
+  return hipGetLastError();
 }
 
 }  // namespace dfa

@@ -32,7 +32,6 @@
 //     slab_reduce sums in a fixed order (deterministic)
 #include "common.h"
 #include "kernels.h"
-#include "diag.h"
 
 namespace dfa {
 
@@ -57,10 +56,7 @@ __device__ __forceinline__ u32x4_t hload16(const void* p) {
   return r;
 }
 
-constexpr int kHP = 64;            // output pixels per tile
-constexpr int kHS = 80;            // LDS row stride in bf16 (64 channels + 16)
-constexpr int kHXP = 5;            // halo staging passes of 32 rows
-constexpr int kHXR = 32 * kHXP;    // halo rows per buffer (>= TI * (R+2) * (W+2))
+constexpr int kHS = 80;            // LDS row stride in bf16 (64 channels + 16); kHP, kHXP, kHXR: kernels.h
 constexpr int kHBuf = (kHP + kHXR) * kHS;
 
 struct HaloP {
@@ -251,60 +247,26 @@ __global__ void __launch_bounds__(256 * G, 2 / G) wgrad_halo_kernel(HaloP p) {
       }
 }
 
-// tile geometry of a W x H image: R rows of TI images per 64-pixel tile; false if it does not tile
-bool halo_geom(int H, int W, int& R, int& TI) {
-  if (W < 4 || W > 64 || kHP % W != 0) return false;
-  const int rpt = kHP / W;
-  if (rpt <= H) {
-    if (H % rpt != 0) return false;
-    R = rpt, TI = 1;
-  } else {
-    if (rpt % H != 0) return false;
-    R = H, TI = rpt / H;
-  }
-  return TI * (R + 2) * (W + 2) <= kHXR;
-}
-
 }  // namespace
 
-bool wgrad_halo_supported(const WgradArgs& a, int mode) {
-  static const int on = diag_int("wgrad_halo", 1);
-  int R, TI;
-  return on && mode == MODE_FWD && !a.with_bias && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 &&
-         a.OH == a.SH && a.OW == a.SW && a.SC % 64 == 0 && a.N % 64 == 0 && a.K == 9 * a.SC && a.ldd % 8 == 0 &&
-         a.M % kHP == 0 && a.M == a.OH * a.OW * (a.M / (a.OH * a.OW)) && halo_geom(a.SH, a.SW, R, TI) &&
-         ((uintptr_t)a.dy & 15) == 0 && ((uintptr_t)a.src & 15) == 0;
-}
-
-hipError_t wgrad_halo(const WgradArgs& a, float* ws, size_t ws_floats, hipStream_t st) {
+// the geometry, split and group count the plan names (csrc/conv_plan.hip wgrad_plan)
+hipError_t wgrad_halo(const WgradArgs& a, const WgradPlan& pl, float* ws, hipStream_t st) {
   HaloP p;
-  int R = 0, TI = 0;
-  halo_geom(a.SH, a.SW, R, TI);
   p.dy = a.dy, p.x = a.src;
   p.H = a.SH, p.W = a.SW, p.C = a.SC, p.N = a.N, p.ldd = a.ldd;
-  p.R = R, p.HW2 = a.SW + 2, p.HR2 = R + 2, p.hrows = TI * (R + 2) * (a.SW + 2), p.rows_per_tile = kHP / a.SW;
+  p.R = pl.R, p.HW2 = a.SW + 2, p.HR2 = pl.R + 2, p.hrows = pl.TI * (pl.R + 2) * (a.SW + 2), p.rows_per_tile = kHP / a.SW;
   p.ntiles = a.M / kHP;
   p.cib_n = a.SC / 64;
   p.cblocks = (a.N / 64) * p.cib_n;
   p.scale = a.scale;
-  // one 8-wave workgroup per CU (140 KB of LDS), bounded by the slab workspace
-  static const int groups = diag_int("halo_groups", 2) == 1 ? 1 : 2;
-  static const int target = diag_int("halo_wg", groups == 2 ? 256 : 512);
-  const long long per_split = (long long)a.N * a.K;
-  int splits = max(1, cdiv(target, p.cblocks));
-  splits = min(splits, p.ntiles);
-  while (splits > 1 && (long long)splits * per_split > (long long)ws_floats) --splits;
-  p.tps = cdiv(p.ntiles, splits);
-  splits = cdiv(p.ntiles, p.tps);
-  p.splits = splits;
-  p.out = splits > 1 ? ws : a.gw;
-  if (groups == 2)
-    hipLaunchKernelGGL(wgrad_halo_kernel<2>, dim3(p.cblocks * splits), dim3(512), 0, st, p);
+  p.tps = pl.tps;
+  p.splits = pl.splits;
+  p.out = pl.splits > 1 ? ws : a.gw;
+  if (pl.groups == 2)
+    hipLaunchKernelGGL(wgrad_halo_kernel<2>, dim3(pl.grid), dim3(pl.block), 0, st, p);
   else
-    hipLaunchKernelGGL(wgrad_halo_kernel<1>, dim3(p.cblocks * splits), dim3(256), 0, st, p);
-  DFA_HIP_CHECK(hipGetLastError());
-  if (splits > 1) DFA_HIP_CHECK(slab_reduce(ws, a.gw, nullptr, a.N, a.K, a.K, splits, a.scale, st));
-  return hipSuccess;
+    hipLaunchKernelGGL(wgrad_halo_kernel<1>, dim3(pl.grid), dim3(pl.block), 0, st, p);
+  return hipGetLastError();
 }
 
 }  // namespace dfa

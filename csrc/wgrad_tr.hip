@@ -23,7 +23,6 @@
 //     tails read a 16-byte zero constant instead (address select: no load under a branch)
 #include "common.h"
 #include "kernels.h"
-#include "diag.h"
 
 namespace dfa {
 
@@ -222,44 +221,21 @@ __global__ void __launch_bounds__(256, (wgrad_tr_occ<BN, BK, BM, MAXOCC>())) wgr
 }
 
 template <int BN, int BK, int WN, int WK, int BM = 64, int MAXOCC = 4>
-hipError_t launch_wgrad_tr(WgradArgs a, float* ws, size_t ws_floats, hipStream_t st) {
-  const int Kt = a.K + (a.with_bias ? 1 : 0);
-  const int tiles = cdiv(a.N, BN) * cdiv(a.K + (a.with_bias ? 8 : 0), BK);
-  // about two workgroups per CU (73.7 KB of LDS each at BM = 64), each reducing >= 256 rows
-  static const int target = diag_int("wgrad_wg", 512);
-  int splits = cdiv(target, tiles);
-  splits = min(splits, cdiv(a.M, 256));
-  splits = max(splits, 1);
-  while (splits > 1 && (size_t)splits * a.N * Kt > ws_floats) --splits;
-  a.m_per_split = round_up(cdiv(a.M, splits), BM);
-  splits = cdiv(a.M, a.m_per_split);
-  a.splits = splits;
-  a.partial = ws;
+hipError_t launch_wgrad_tr(const WgradArgs& a, const WgradPlan& p, hipStream_t st) {
   const FastDiv d_ow = make_fastdiv((unsigned)a.OW), d_ohw = make_fastdiv((unsigned)(a.OH * a.OW));
-  hipLaunchKernelGGL((wgrad_tr_kernel<BN, BK, WN, WK, BM, MAXOCC>), dim3(tiles * splits), dim3(256), 0, st, a, d_ow, d_ohw);
-  DFA_HIP_CHECK(hipGetLastError());
-  if (splits > 1) DFA_HIP_CHECK(slab_reduce(ws, a.gw, a.with_bias ? a.gb : nullptr, a.N, a.K, Kt, splits, a.scale, st));
-  return hipSuccess;
+  hipLaunchKernelGGL((wgrad_tr_kernel<BN, BK, WN, WK, BM, MAXOCC>), dim3(p.grid), dim3(p.block), 0, st, a, d_ow, d_ohw);
+  return hipGetLastError();
 }
 
 }  // namespace
 
-bool wgrad_tr_supported(const WgradArgs& a, int mode) {
-  return mode == MODE_FWD && (!a.with_bias || a.gb != nullptr) && a.SC % 8 == 0 && a.N % 8 == 0 && a.ldd % 8 == 0 && a.M > 0 &&
-         a.OH > 0 && a.OW > 0 && ((uintptr_t)a.dy & 15) == 0 && ((uintptr_t)a.src & 15) == 0;
-}
-
-hipError_t wgrad_tr(const WgradArgs& a, float* ws, size_t ws_floats, hipStream_t st) {
-  static const int t128 = diag_int("wgrad128", 32);
-  // 128 x 128 tiles at 32 rows per step, 3 workgroups per CU (170 VGPRs each: no spills)
-  if (a.N >= 128 && t128 == 32) return launch_wgrad_tr<128, 128, 2, 2, 32, 3>(a, ws, ws_floats, st);
-  if (a.N >= 128) return launch_wgrad_tr<128, 128, 2, 2>(a, ws, ws_floats, st);
-  if (a.N <= 32) return launch_wgrad_tr<32, 128, 1, 4>(a, ws, ws_floats, st);  // Keras CNN conv2: no empty rows
-  // 64-channel tiles step 32 rows at a time: 36.9 KB of LDS -> 4 workgroups per CU (ResNet layer 1:
-  // 104 -> 82 us).  The 128 x 128 tile at 32 rows would need more than the 128 VGPRs of 4 workgroups per
-  // CU and spills, which the inline-asm loads (destinations unprotected until their counted wait)
-  // cannot tolerate: it stays at 64 rows.
-  return launch_wgrad_tr<64, 128, 2, 2, 32>(a, ws, ws_floats, st);
+// the instantiation the plan names (csrc/conv_plan.hip wgrad_plan chose tile, rows per step and split)
+hipError_t wgrad_tr(WgradArgs a, const WgradPlan& p, float* ws, hipStream_t st) {
+  a.m_per_split = p.m_per_split, a.splits = p.splits, a.partial = ws;
+  if (p.BN == 128 && p.BM == 32) return launch_wgrad_tr<128, 128, 2, 2, 32, 3>(a, p, st);
+  if (p.BN == 128) return launch_wgrad_tr<128, 128, 2, 2>(a, p, st);
+  if (p.BN == 32) return launch_wgrad_tr<32, 128, 1, 4>(a, p, st);
+  return launch_wgrad_tr<64, 128, 2, 2, 32>(a, p, st);
 }
 
 }  // namespace dfa

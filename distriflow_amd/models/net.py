@@ -299,16 +299,23 @@ class Net:
             yield from leaves(l)
 
     # ------------------------------------------------------------------ buffers
-    def bind(self, B: int):
-        if self._bound_B == B:
-            return
-        # split-m weight-gradient slabs: room for 4 slabs of the largest conv kernel (>= 16 MB)
+    def wgrad_layers(self):
+        """The Conv2D leaves, those inside the fused conv blocks included."""
         convs = [c for l in self._all_leaf_layers()
                  for c in ((l.conv,) if isinstance(l, ConvPoolGemm) else
                            (l.conv1, l.conv2) if isinstance(l, KerasConvBlock) else (l,))]
-        nk = max([l.filters * l.kh * l.kw * l.in_shape[2] for l in convs if isinstance(l, Conv2D)]
-                 + [0])
-        ws_wgrad = torch.empty(max(1 << 22, 4 * nk), dtype=torch.float32, device=self.device)
+        return [l for l in convs if isinstance(l, Conv2D)]
+
+    def wgrad_ws_floats(self) -> int:
+        """Split-m weight-gradient slabs: room for 4 slabs of the largest conv kernel (>= 16 MB).  A launch
+        that asks for more gets fewer splits (ops.wgrad_plan reports it as ``capped``)."""
+        nk = max([l.filters * l.kh * l.kw * l.in_shape[2] for l in self.wgrad_layers()] + [0])
+        return max(1 << 22, 4 * nk)
+
+    def bind(self, B: int):
+        if self._bound_B == B:
+            return
+        ws_wgrad = torch.empty(self.wgrad_ws_floats(), dtype=torch.float32, device=self.device)
         maxC = max([l.C for l in self._all_leaf_layers() if isinstance(l, BatchNorm)] + [8])
         ws_bn = torch.empty(ops.bn_workspace_floats(maxC), dtype=torch.float32, device=self.device)
         self.ws = Workspace(ws_wgrad, ws_bn)

@@ -299,6 +299,23 @@ def conv_dgrad(dy, w, wt, out, KH, KW, stride=1, pad=0, mask=None, residual=None
     return out
 
 
+def wgrad_plan(B, H, W, C, OH, OW, N, KH, KW, stride, pad, with_bias, ws_floats) -> dict:
+    """The launch plan (csrc/conv_plan.hip wgrad_plan: kernel family, tile, splits, grid, the floats it writes
+    into a workspace of ``ws_floats``) of :func:`conv_wgrad`; {} without the native extension.  A workspace
+    smaller than ``wanted_floats`` gives fewer splits (``capped``): another summation order."""
+    m = native.get(build_if_missing=False)
+    if m is None:
+        return {}
+    return m.wgrad_plan(B * OH * OW, N, KH * KW * C, N, 0, _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD,
+                        bool(with_bias), int(ws_floats))
+
+
+def dense_wgrad_plan(B, K, N, with_bias, ws_floats) -> dict:
+    """:func:`wgrad_plan` of :func:`dense_wgrad` (x [B][K], dy [B][N])."""
+    m = native.get(build_if_missing=False)
+    return m.wgrad_plan(B, N, K, N, K, _geom(), MODE_DIRECT, bool(with_bias), int(ws_floats)) if m is not None else {}
+
+
 def conv_wgrad(dy, x, gw, gb, workspace, KH, KW, stride=1, pad=0, scale=1.0):
     B, H, W, C = x.shape
     _, OH, OW, N = dy.shape

@@ -12,6 +12,13 @@ The answers were recorded at the last commit that had the separate shape-only qu
 that replaced them.  (The third query, the in-launch BatchNorm statistics tiles, left with that route and is
 no longer recorded.)  On a build without those bindings the script keeps every recorded answer (new entries
 get none) and only attaches launch tables.
+
+The weight gradients of the same layers are the ``wgrad`` list of the file: every Conv2D / Dense of the three
+models with the workspace ``Net.bind`` gives them (their plan is recorded as it is: a pin, the dispatch that
+preceded the planner had no query to record) and a hand list with one smallest shape per branch, each with
+its workspace size, whose launches at the last commit before the planner are attached with
+
+    python scripts/conv_plan_fixture.py --wgrad-launches profiles/conv_plan/launches_wgrad_parent.txt
 """
 from __future__ import annotations
 
@@ -119,6 +126,71 @@ def edge_list():
     return conv("empty_batch", 0, 8, 8, 8, 8, 3, 1, 1)                  # M = 0: nothing to launch
 
 
+def wgrad(name, B, H, W, C, N, k, stride=1, pad=0, bias=False, ws=1 << 24, **flags):
+    """The weight gradient of one conv with a workspace of ``ws`` floats."""
+    from distriflow_amd import ops
+    KH, KW = ops._pair(k)
+    OH, OW = flags.pop("out_hw", None) or ops.conv_out_hw(H, W, KH, KW, stride, pad)
+    return [dict(name=name, mode=1, M=B * OH * OW, N=N, K=KH * KW * C, ldd=N, lda=0, bias=bias, ws=ws,
+                 geom=ops._geom(H, W, C, OH, OW, KH, KW, stride, pad), **flags)]
+
+
+def wgrad_dense(name, B, K, N, bias=True, ws=1 << 22):
+    return [dict(name=name, mode=0, M=B, N=N, K=K, ldd=N, lda=K, bias=bias, ws=ws, geom=None)]
+
+
+def wgrad_model_list():
+    """The layers of model_list(), with their bias and the workspace Net.bind allocates for the model
+    (max(2^22, 4 x the largest conv kernel): resnet18_cifar 4 x 512 x 4608)."""
+    es = []
+    for e in model_list():
+        if not e["name"].endswith("/fwd"):
+            continue
+        name = e["name"][:-4] + "/wgrad"
+        resnet = name.startswith("resnet18")
+        ws = 4 * 512 * 4608 if resnet else 1 << 22
+        if e["conv"] is None:
+            es += wgrad_dense(name, e["M"], e["K"], e["N"], ws=ws)
+        else:
+            c = e["conv"]
+            es += wgrad(name, c["B"], c["H"], c["W"], c["C"], c["N"], c["KH"], c["stride"], c["pad"], bias=not resnet, ws=ws)
+    return es
+
+
+def wgrad_hand_list():
+    """Each branch of the weight-gradient dispatch at its smallest shape.  ``diag``: the DISTRIFLOW_DIAG the
+    entry is planned and launched under (its own process: the switches are read once)."""
+    es = []
+    es += wgrad("halo_groups2", 4, 16, 16, 64, 64, 3, 1, 1)              # 16 tiles of 64 pixels: 16 splits
+    es += wgrad("halo_ws1", 4, 16, 16, 64, 64, 3, 1, 1, ws=1)            # no slab room: one split writes gw
+    es += wgrad("halo_ws2slabs", 4, 16, 16, 64, 64, 3, 1, 1, ws=2 * 64 * 576)
+    es += wgrad("halo_groups1", 4, 16, 16, 64, 64, 3, 1, 1, diag="halo_groups=1")
+    es += wgrad("tr_128x128_32rows", 8, 16, 16, 64, 128, 3, 2, 1)
+    es += wgrad("tr_n32", 4, 26, 26, 32, 32, 3)
+    es += wgrad("tr_64", 2, 16, 16, 16, 64, 3, 1, 1)
+    es += wgrad("tr_bias", 3, 9, 7, 16, 24, 3, 2, 1, bias=True)
+    es += wgrad("c1", 4, 28, 28, 1, 32, 3, bias=True, ws=1 << 22)
+    es += wgrad("c1_small_ws", 8, 28, 28, 1, 32, 3, bias=True, ws=1000)  # 4 image-pair slabs of 320 do not fit
+    es += wgrad("smallc_5x5", 4, 28, 28, 1, 8, 5, 1, 2, bias=True, ws=1 << 22)
+    es += wgrad("generic_n16", 4, 14, 14, 6, 16, 5, bias=True, ws=1 << 22)   # C % 8 != 0: no XVEC
+    es += wgrad("generic_n32", 4, 8, 8, 3, 32, 3, 1, 1, ws=1 << 22)
+    es += wgrad("generic_n64", 4, 32, 32, 3, 64, 3, 1, 1, ws=1 << 22)
+    es += wgrad("generic_no_dvec", 4, 28, 28, 1, 6, 5, 1, 2, bias=True, ws=1 << 22)  # N % 8 != 0
+    es += wgrad("generic_capped", 8, 14, 14, 6, 16, 5, bias=True, ws=3000)   # 13 splits of 2416 floats wanted
+    es += wgrad_dense("direct_aligned", 32, 400, 120) + wgrad_dense("direct_unaligned", 32, 84, 10)
+    es += wgrad_dense("direct_no_dvec", 32, 400, 10)                     # XVEC without DVEC
+    es += wgrad("irregular_same", 4, 16, 16, 64, 64, 3, 2, (0, 0), out_hw=(8, 8))
+    es += wgrad("irregular_stride", 4, 16, 16, 64, 64, 3, (2, 1), (1, 1))
+    es += wgrad("irregular_3x5", 4, 16, 16, 64, 64, (3, 5), 1, (1, 2))
+    es += wgrad("empty_batch", 0, 8, 8, 8, 8, 3, 1, 1)                   # M = 0: nothing to launch
+    return [dict(e, hand=True) for e in es]
+
+
+def wgrad_plan_of(e, m):
+    geom = e["geom"] if e["geom"] is not None else [1, 1, 1, 1, 1, 1, 1, 1, 0]
+    return m.wgrad_plan(e["M"], e["N"], e["K"], e["ldd"], e["lda"], geom, e["mode"], e["bias"], e["ws"])
+
+
 def record(e, m):
     """The parent's answers: the shape-only queries of the native extension (BatchNorm sums, pooling)."""
     geom = e["geom"] if e["geom"] is not None else [1, 1, 1, 1, 1, 1, 1, 1, 0]
@@ -134,14 +206,18 @@ def record(e, m):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", help="reduced launch table (scripts/conv_plan_trace.py --reduce) to attach")
+    ap.add_argument("--wgrad-launches", help="the same for the weight-gradient hand list (--reduce-wgrad)")
     a = ap.parse_args()
     from distriflow_amd import native
     m = native.get(build_if_missing=False)
     entries = model_list() + hand_list() + edge_list()
-    old = {}
+    wentries = wgrad_model_list() + wgrad_hand_list()
+    old, wold = {}, {}
     if os.path.exists(OUT):
         with open(OUT) as f:
-            old = {e["name"]: e for e in json.load(f)["entries"]}
+            j = json.load(f)
+        old = {e["name"]: e for e in j["entries"]}
+        wold = {e["name"]: e for e in j.get("wgrad", [])}
     for e in entries:
         if hasattr(m, "igemm_bacc_supported"):
             record(e, m)
@@ -155,11 +231,24 @@ def main():
         from conv_plan_trace import read_table
         for name, rows in read_table(a.launches).items():
             next(e for e in entries if e["name"] == name)["launch"] = rows
+    wrows = {}
+    if a.wgrad_launches:
+        from conv_plan_trace import read_table
+        wrows = read_table(a.wgrad_launches)
+    for e in wentries:
+        if e.get("hand"):  # (an entry that launches nothing has no row)
+            e["launch"] = wrows.get(e["name"], []) if a.wgrad_launches else wold.get(e["name"], {}).get("launch")
+        elif hasattr(m, "wgrad_plan"):
+            e["plan"] = wgrad_plan_of(e, m)
+        else:
+            e["plan"] = wold.get(e["name"], {}).get("plan")
     with open(OUT, "w") as f:
         f.write('{"bacc_variants": "bacc_mode two has_res has_mask, in itertools.product order",\n "entries": [\n')
         f.write(",\n".join("  " + json.dumps(e) for e in entries))
+        f.write("\n],\n \"wgrad\": [\n")
+        f.write(",\n".join("  " + json.dumps(e) for e in wentries))
         f.write("\n]}\n")
-    print(f"{len(entries)} entries -> {OUT}")
+    print(f"{len(entries)} + {len(wentries)} entries -> {OUT}")
 
 
 if __name__ == "__main__":

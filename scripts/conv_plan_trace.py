@@ -6,6 +6,15 @@
 ``--launch`` runs every entry once, forward and data gradient, each behind a one-element fill that marks
 it in the trace.  ``--reduce`` prints one line per kernel: entry, kernel, workgroups, workgroup size, LDS
 bytes.  Two builds launch the same kernels exactly when their tables are equal.
+
+``--launch-wgrad`` / ``--reduce-wgrad DIR`` do the same for the weight-gradient hand list (``wgrad_hand_list``),
+each entry with the workspace size it names.  Both take the entries whose ``diag`` is the process's
+DISTRIFLOW_DIAG (the switches are read once per process), so the list takes one profiler run per value:
+
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python scripts/conv_plan_trace.py --launch-wgrad
+    DISTRIFLOW_DIAG=halo_groups=1 rocprofv3 ... -d DIR1 -- python scripts/conv_plan_trace.py --launch-wgrad
+    (python scripts/conv_plan_trace.py --reduce-wgrad DIR;
+     DISTRIFLOW_DIAG=halo_groups=1 python scripts/conv_plan_trace.py --reduce-wgrad DIR1) > <table>.txt
 """
 from __future__ import annotations
 
@@ -53,13 +62,42 @@ def launch():
     torch.cuda.synchronize()
 
 
+def wgrad_entries():
+    from conv_plan_fixture import wgrad_hand_list
+    return [e for e in wgrad_hand_list() if e.get("diag", "") == os.environ.get("DISTRIFLOW_DIAG", "")]
+
+
+def launch_wgrad():
+    import torch
+    from distriflow_amd import native
+    m = native.get(build_if_missing=False)
+    dev = "cuda"
+    jobs = []
+    for e in wgrad_entries():
+        M, N, K = e["M"], e["N"], e["K"]
+        if e["mode"] == 0:
+            geom, nsrc = [1, 1, 1, 1, 1, 1, 1, 1, 0], M * e["lda"]
+        else:
+            geom = e["geom"]
+            nsrc = M // (geom[3] * geom[4]) * geom[0] * geom[1] * geom[2]
+        z = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
+        jobs.append((z(M * e["ldd"], torch.bfloat16), z(nsrc, torch.bfloat16), z(N * K, torch.float32),
+                     z(N, torch.float32) if e["bias"] else None, z(e["ws"], torch.float32), M, N, K, e["ldd"],
+                     e["lda"], geom, e["mode"], 1.0))
+    mark = torch.zeros(1, device=dev)
+    torch.cuda.synchronize()
+    for j in jobs:
+        mark.fill_(1.0)
+        m.igemm_wgrad(*j)
+    torch.cuda.synchronize()
+
+
 def _short(n):
     n = n.replace("void ", "").replace("dfa::", "").replace("(anonymous namespace)::", "")
     return re.sub(r"\(.*\)$", "", n).replace(" ", "")
 
 
-def reduce_trace(d):
-    from conv_plan_fixture import hand_list
+def reduce_trace(d, names):
     recs = []
     for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
@@ -68,7 +106,6 @@ def reduce_trace(d):
             if not r["Kernel_Name"].startswith("__amd_rocclr"):  # (the runtime's own memset of a first-use buffer)
                 recs.append((int(r["Start_Timestamp"]), _short(r["Kernel_Name"]), grid // wg, wg, int(r["LDS_Block_Size"])))
     recs.sort()
-    names = [e["name"] for e in hand_list()]
     marks = [i for i, r in enumerate(recs) if "FillFunctor" in r[1]][-len(names):]
     assert len(marks) == len(names), f"{len(marks)} markers for {len(names)} entries"
     for name, i, j in zip(names, marks, marks[1:] + [len(recs)]):
@@ -89,8 +126,15 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--launch", action="store_true")
     ap.add_argument("--reduce", metavar="DIR")
+    ap.add_argument("--launch-wgrad", action="store_true")
+    ap.add_argument("--reduce-wgrad", metavar="DIR")
     a = ap.parse_args()
     if a.launch:
         launch()
+    if a.launch_wgrad:
+        launch_wgrad()
     if a.reduce:
-        reduce_trace(a.reduce)
+        from conv_plan_fixture import hand_list
+        reduce_trace(a.reduce, [e["name"] for e in hand_list()])
+    if a.reduce_wgrad:
+        reduce_trace(a.reduce_wgrad, [e["name"] for e in wgrad_entries()])

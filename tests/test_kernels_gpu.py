@@ -265,7 +265,84 @@ def test_conv_wgrad_large_m_split():
     _close(gb, eb, 1e-3, 1e-2)
 
 
-POOLS = [(4, 28, 28, 6, 2), (4, 24, 24, 32, 2), (2, 10, 10, 16, 2), (2, 5, 5, 3, 2), (2, 9, 9, 8, 3)]
+WGRAD_PLANNED = [  # family, B, H, W, C, N, k, stride, pad, bias: one shape per kernel family of csrc/conv_plan.hip
+    ("halo", 4, 16, 16, 64, 64, 3, 1, 1, False),
+    ("tr", 3, 9, 7, 16, 24, 3, 2, 1, True),
+    ("c1", 4, 28, 28, 1, 32, 3, 1, 0, True),
+    ("generic", 4, 14, 14, 6, 16, 5, 1, 0, True),
+]
+
+
+def _wgrad_in_planned_workspace(p, run, scale=0.5):
+    """Runs ``run(ws)`` with a NaN workspace of the plan's scratch plus 4096 floats: the launch fills exactly
+    the scratch the plan names and leaves the rest alone."""
+    ws = torch.full((p["scratch_floats"] + 4096,), float("nan"), device=dev)
+    run(ws)
+    assert torch.isnan(ws[p["scratch_floats"]:]).all(), "wrote past the plan's scratch"
+    assert not torch.isnan(ws[:p["scratch_floats"]]).any(), "left some of the plan's scratch unwritten"
+
+
+@pytest.mark.parametrize("family,B,H,W,C,N,k,s,p,bias", WGRAD_PLANNED)
+def test_conv_wgrad_writes_the_planned_scratch(family, B, H, W, C, N, k, s, p, bias):
+    OH, OW = ops.conv_out_hw(H, W, k, k, s, p)
+    plan = ops.wgrad_plan(B, H, W, C, OH, OW, N, k, k, s, p, bias, 1 << 24)
+    assert plan["family"] == family and not plan["capped"]
+    assert ops.wgrad_plan(B, H, W, C, OH, OW, N, k, k, s, p, bias, plan["scratch_floats"] + 4096) == plan
+    dy = torch.randn(B, OH, OW, N, device=dev).to(torch.bfloat16)
+    x = torch.randn(B, H, W, C, device=dev).to(torch.bfloat16)
+    gw = torch.full((N, k * k * C), float("nan"), device=dev)
+    gb = torch.full((N,), float("nan"), device=dev) if bias else None
+    _wgrad_in_planned_workspace(plan, lambda ws: ops.conv_wgrad(dy, x, gw, gb, ws, k, k, s, p, scale=0.5))
+    ew, eb = ref.conv_wgrad(dy.float(), x.float(), k, k, s, p, with_bias=bias)
+    _close(gw, 0.5 * ew, 1e-3, 1e-3)
+    if bias:
+        _close(gb, 0.5 * eb, 1e-3, 1e-3)
+
+
+def test_dense_wgrad_writes_the_planned_scratch():
+    M, K, N = 32, 84, 10
+    plan = ops.dense_wgrad_plan(M, K, N, True, 1 << 24)
+    assert plan["family"] == "generic" and ops.dense_wgrad_plan(M, K, N, True, plan["scratch_floats"] + 4096) == plan
+    dy = torch.randn(M, N, device=dev).to(torch.bfloat16)
+    x = torch.randn(M, K, device=dev).to(torch.bfloat16)
+    gw = torch.full((N, K), float("nan"), device=dev)
+    gb = torch.full((N,), float("nan"), device=dev)
+    _wgrad_in_planned_workspace(plan, lambda ws: ops.dense_wgrad(dy, x, gw, gb, ws))
+    ew, eb = ref.dense_wgrad(dy.float(), x.float())
+    _close(gw, ew, 1e-3, 1e-3)
+    _close(gb, eb, 1e-3, 1e-3)
+
+
+def test_conv_wgrad_halo_capped_to_two_slabs():
+    """A workspace of exactly two slabs: the plan is capped to two splits, the result the same gradient."""
+    B, H, W, C, N = 4, 16, 16, 64, 64
+    ws = torch.full((2 * N * 9 * C,), float("nan"), device=dev)
+    plan = ops.wgrad_plan(B, H, W, C, H, W, N, 3, 3, 1, 1, False, ws.numel())
+    assert (plan["family"], plan["capped"], plan["splits"], plan["scratch_floats"]) == ("halo", True, 2, ws.numel())
+    dy = torch.randn(B, H, W, N, device=dev).to(torch.bfloat16)
+    x = torch.randn(B, H, W, C, device=dev).to(torch.bfloat16)
+    gw = torch.full((N, 9 * C), float("nan"), device=dev)
+    ops.conv_wgrad(dy, x, gw, None, ws, 3, 3, 1, 1, scale=0.5)
+    ew, _ = ref.conv_wgrad(dy.float(), x.float(), 3, 3, 1, 1, with_bias=False)
+    _close(gw, 0.5 * ew, 1e-3, 1e-3)
+    assert not torch.isnan(ws).any()
+
+
+def test_conv_wgrad_refuses_a_workspace_below_one_slab():
+    """The C = 1 kernels always write a slab per workgroup: a workspace smaller than the plan's scratch is an
+    error of the binding, raised before anything is launched."""
+    B, H, W, N = 4, 28, 28, 32
+    dy = torch.randn(B, 26, 26, N, device=dev).to(torch.bfloat16)
+    x = torch.randn(B, H, W, 1, device=dev).to(torch.bfloat16)
+    gw = torch.full((N, 9), float("nan"), device=dev)
+    gb = torch.full((N,), float("nan"), device=dev)
+    assert ops.wgrad_plan(B, H, W, 1, 26, 26, N, 3, 3, 1, 0, True, 1)["scratch_floats"] == N * 10
+    with pytest.raises(RuntimeError, match="workspace"):
+        ops.conv_wgrad(dy, x, gw, gb, torch.empty(1, device=dev), 3, 3, 1, 0)
+    assert torch.isnan(gw).all() and torch.isnan(gb).all()
+
+
+POOLS = [(4, 28, 28, 6, 2),(4, 24, 24, 32, 2), (2, 10, 10, 16, 2), (2, 5, 5, 3, 2), (2, 9, 9, 8, 3)]
 
 
 @pytest.mark.parametrize("B,H,W,C,P", POOLS)

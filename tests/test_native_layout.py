@@ -2,7 +2,7 @@
 policy (csrc/lenet_fused.hip lenet_ipw / lenet_blocks), the irregular-geometry routing of the conv
 dispatch (csrc/bindings_util.h set_conv_geom: only the generic implicit GEMM takes it), the parameter
 server's buffer layout (csrc/ps_layout.h), the dense head's error-word offset (csrc/khead.hip) and the
-launch plan of the forward / data-gradient implicit GEMMs (csrc/conv_plan.hip)."""
+launch plans of the forward / data-gradient and the weight-gradient implicit GEMMs (csrc/conv_plan.hip)."""
 import itertools
 import json
 import os
@@ -172,3 +172,138 @@ def test_conv_plan_reads_the_diagnostic_switches():
     assert m.conv_plan(4096, 512, 4608, 4608, [4, 4, 512, 4, 4, 3, 3, 1, 1], 1)["family"] == "halo"
     assert run("conv_halo=0") == ["igemm64", "4", str(4 * 4096 * 512)]
     assert run("conv_halo=0,igemm_splitk=0") == ["igemm64", "1", "0"]
+
+
+# ---------------------------------------------------------------------------- weight-gradient launch plan
+WGRAD_FAMILY_OF_KERNEL = {"wgrad_halo_kernel": "halo", "wgrad_tr_kernel": "tr", "c1_wgrad_kernel": "c1",
+                          "smallc_wgrad_kernel": "smallc", "igemm_wgrad_kernel": "generic"}
+ROOT = os.path.dirname(CSRC)
+
+
+def _wgrad_args(e):
+    geom = e["geom"] if e["geom"] is not None else [1, 1, 1, 1, 1, 1, 1, 1, 0]
+    return [e["M"], e["N"], e["K"], e["ldd"], e["lda"], geom, e["mode"], e["bias"], e["ws"]]
+
+
+def _wgrad_plans_under(diag, calls):
+    """DISTRIFLOW_DIAG is read once per process: the plans of ``calls`` (_C.wgrad_plan argument lists) in a child."""
+    code = ("import json, sys\nfrom distriflow_amd import native\nm = native.get(build_if_missing=False)\n"
+            "print(json.dumps([m.wgrad_plan(*c) for c in json.load(sys.stdin)]))\n")
+    r = subprocess.run([sys.executable, "-c", code], input=json.dumps(calls), capture_output=True, text=True, cwd=ROOT,
+                       env=dict(os.environ, DISTRIFLOW_DIAG=diag))
+    assert r.returncode == 0, r.stderr
+    return json.loads(r.stdout)
+
+
+def _check_wgrad_launch(e, p):
+    """The plan against what the last commit before the planner launched for this entry
+    (profiles/conv_plan/launches_wgrad_parent.txt): kernel, template arguments, workgroups, workgroup size, and
+    whether a slab_reduce_* launch follows."""
+    rows = e["launch"]
+    if not rows:
+        assert p["family"] == "nop" and e["M"] == 0, e["name"]
+        return
+    kern, grid, block, _ = rows[0]
+    name, _, targs = kern.partition("<")
+    t = [{"true": True, "false": False}.get(v, v) for v in targs.rstrip(">").split(",")] if targs else []
+    assert p["family"] == WGRAD_FAMILY_OF_KERNEL[name], e["name"]
+    if p["family"] == "halo":
+        want = dict(groups=int(t[0]))
+    elif p["family"] == "tr":
+        want = dict(zip(("BN", "BK", "WN", "WK", "BM", "MAXOCC"), map(int, t)))
+    elif p["family"] == "generic":
+        want = dict(BN=int(t[0]), BK=int(t[1]), WN=int(t[2]), WK=int(t[3]), dvec=t[5], xvec=t[6])
+        assert int(t[4]) == e["mode"], e["name"]
+    else:
+        want = {}
+    assert {k: p[k] for k in want} == want, e["name"]
+    assert (p["grid"], p["block"]) == (grid, block), e["name"]
+    followers = [r[0] for r in rows[1:]]
+    assert len(followers) == int(p["reduce"]) and all(f.startswith("slab_reduce_") for f in followers), e["name"]
+
+
+@needs_ext
+def test_wgrad_plan_matches_recorded_launches():
+    """For a hand list with one smallest shape per branch of the weight-gradient dispatch, each with its
+    workspace size (scripts/conv_plan_fixture.py wgrad_hand_list), the plan names the kernel, template
+    arguments, grid and workgroup size that the dispatch launched on the GPU before the planner existed, and
+    says whether a slab reduction follows.  The list keeps reaching every family and both values of capped,
+    reduce, the halo group count, DVEC and XVEC; the scratch is 0 exactly without a reduction and within the
+    workspace wherever the kernel can honour a cap (the C = 1 kernels always write one slab).  Every Conv2D /
+    Dense of the three models plans as recorded (a pin of the plan itself)."""
+    with open(GOLDEN) as f:
+        entries = json.load(f)["wgrad"]
+    hand = [e for e in entries if e.get("hand")]
+    plans = {e["name"]: m.wgrad_plan(*_wgrad_args(e)) for e in hand if not e.get("diag")}
+    for diag in sorted({e["diag"] for e in hand if e.get("diag")}):
+        es = [e for e in hand if e.get("diag") == diag]
+        plans.update(zip([e["name"] for e in es], _wgrad_plans_under(diag, [_wgrad_args(e) for e in es])))
+    seen = {}
+    for e in hand:
+        p = plans[e["name"]]
+        _check_wgrad_launch(e, p)
+        assert p["capped"] == (p["scratch_floats"] < p["wanted_floats"]), e["name"]
+        assert (p["scratch_floats"] == 0) == (not p["reduce"]), e["name"]
+        if p["family"] not in ("c1", "smallc"):
+            assert p["scratch_floats"] <= e["ws"], e["name"]
+        for k in ("family", "capped", "reduce"):
+            seen.setdefault(k, set()).add(p[k])
+        if p["family"] in ("halo", "generic"):
+            for k in ("groups",) if p["family"] == "halo" else ("dvec", "xvec"):
+                seen.setdefault(k, set()).add(p[k])
+    assert seen == dict(family={"nop", "halo", "tr", "c1", "smallc", "generic"}, capped={False, True},
+                        reduce={False, True}, groups={1, 2}, dvec={False, True}, xvec={False, True}), seen
+    assert {e["name"] for e in hand if e["name"].startswith("irregular")} == \
+        {"irregular_same", "irregular_stride", "irregular_3x5"}
+    assert all(plans[e["name"]]["family"] == "generic" for e in hand if e["name"].startswith("irregular"))
+    assert sum(len(e["launch"]) for e in hand) == 38
+    assert (plans["halo_ws1"]["splits"], plans["halo_ws2slabs"]["splits"], plans["c1_small_ws"]["family"]) == (1, 2, "smallc")
+    models = [e for e in entries if not e.get("hand")]
+    assert len(models) == 150
+    for e in models:
+        assert m.wgrad_plan(*_wgrad_args(e)) == e["plan"], e["name"]
+
+
+@needs_ext
+@pytest.mark.parametrize("model,B", [("lenet5", 4096), ("keras_cnn", 1024), ("resnet18_cifar", 256)])
+def test_wgrad_workspace_of_bind_caps_no_layer(model, B):
+    """With the workspace Net.bind allocates (max(2^22, 4 x the largest conv kernel) floats) no Conv2D / Dense
+    of the three benchmark configurations gets fewer splits than its policy asks for.  ResNet-18 only just:
+    its 3x3 64 -> 64 halo layers want 256 slabs of 36 864 floats, exactly 4 x the 512 x 4608 kernel."""
+    from distriflow_amd.models.layers import Conv2D, Dense, FusedConvPool
+    from distriflow_amd.models.zoo import build_model
+    net = build_model(model, device="cpu", seed=0)
+    ws = net.wgrad_ws_floats()
+    leaves = list(net._all_leaf_layers())
+    convs = net.wgrad_layers() + [l.conv for l in leaves if isinstance(l, FusedConvPool)]
+    assert convs or model == "lenet5"
+    wanted = 0
+    for l in convs:
+        assert isinstance(l, Conv2D)
+        (H, W, C), (OH, OW, N) = l.in_shape, l.out_shape
+        p = ops.wgrad_plan(B, H, W, C, OH, OW, N, *l.geom, l.use_bias, ws)
+        assert p["family"] != "nop" and not p["capped"], (l.name, p)
+        wanted = max(wanted, p["wanted_floats"])
+    for l in leaves:
+        if isinstance(l, Dense):
+            p = ops.dense_wgrad_plan(B, l.in_features, l.units, l.use_bias, ws)
+            assert p["family"] == "generic" and not p["capped"], (l.name, p)
+    if model == "resnet18_cifar":
+        assert wanted == ws == 9437184
+        # the sizing is not a bound: a model whose largest 3x3 conv is 64 -> 64 gets 2^22 floats, room for 113
+        # slabs; 4096 tiles in splits of 37 are 111
+        q = ops.wgrad_plan(B, 32, 32, 64, 32, 32, 64, 3, 3, 1, 1, False, 1 << 22)
+        assert q["capped"] and (q["splits"], q["tps"], q["wanted_floats"]) == (111, 37, 9437184)
+
+
+@needs_ext
+def test_wgrad_plan_reads_the_diagnostic_switches():
+    """In a child each (the switches are read once per process): with wgrad_halo=0 a 3x3 / stride 1 / pad 1
+    conv with C = N = 64 plans as transposed-read, with halo_groups=1 it plans 256-thread workgroups."""
+    call = [4 * 16 * 16, 64, 576, 64, 0, [16, 16, 64, 16, 16, 3, 3, 1, 1], 1, False, 1 << 24]
+    p = m.wgrad_plan(*call)
+    assert (p["family"], p["groups"], p["block"]) == ("halo", 2, 512)
+    q = _wgrad_plans_under("wgrad_halo=0", [call])[0]
+    assert (q["family"], q["BN"], q["BM"]) == ("tr", 64, 32)
+    q = _wgrad_plans_under("halo_groups=1", [call])[0]
+    assert (q["family"], q["groups"], q["block"]) == ("halo", 1, 256)
