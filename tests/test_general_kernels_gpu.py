@@ -84,6 +84,81 @@ def test_pool2d(H, C, pool, stride, pad, avg):
         torch.testing.assert_close(dx.float().cpu(), gr, rtol=2e-2, atol=2e-2)
 
 
+# ---- csrc/layers.hip: add_act, relu_bwd, gap_fwd, gap_bwd.  One grid-stride pass of these launches is 8192
+# workgroups of 256 threads = 2 097 152 work items (8-element vectors for the first two, elements for the GAPs).
+PASS = 8192 * 256
+
+
+def _sentinel_out(n):
+    buf = torch.full((n + 64,), 1024.0, dtype=torch.bfloat16, device=dev)
+    return buf, buf[:n]
+
+
+@pytest.mark.parametrize("n8", [1, 1000, PASS, PASS + 3])
+def test_add_act_and_relu_bwd_exact(n8):
+    """Small integers: a + b and its relu are bf16 values, dy * [y > 0] is a selection -- both exact."""
+    n = 8 * n8
+    a, b = (torch.randint(-100, 101, (n,), device=dev).to(torch.bfloat16) for _ in range(2))
+    for relu in (False, True):
+        buf, out = _sentinel_out(n)
+        ops.add_act(a, b, out, relu)
+        exp = a.float() + b.float()
+        assert torch.equal(out.float(), exp.relu() if relu else exp)
+        assert (buf[n:] == 1024.0).all()
+    buf, dx = _sentinel_out(n)
+    ops.relu_bwd(a, b, dx)  # y = a (its sign decides), dy = b
+    assert torch.equal(dx, torch.where(a.float() > 0, b, torch.zeros_like(b)))
+    assert (buf[n:] == 1024.0).all()
+
+
+def test_add_act_against_fp64_within_one_bf16_ulp():
+    g = torch.Generator().manual_seed(5)
+    a, b = (torch.randn(8 * 1001, generator=g).to(torch.bfloat16).to(dev) for _ in range(2))
+    out = torch.empty_like(a)
+    ops.add_act(a, b, out, True)
+    exp = (a.double() + b.double()).relu()
+    assert ((out.double() - exp).abs() <= 2.0 ** -7 * exp.abs()).all()
+
+
+@pytest.mark.parametrize("op", ["add_act", "relu_bwd"])
+def test_add_act_relu_bwd_refuse_a_partial_vector(op):
+    a, b = (torch.ones(8 * 5 + 3, dtype=torch.bfloat16, device=dev) for _ in range(2))
+    out = torch.full_like(a, 1024.0)
+    with pytest.raises(RuntimeError):
+        ops.add_act(a, b, out, True) if op == "add_act" else ops.relu_bwd(a, b, out)
+    torch.cuda.synchronize()
+    assert (out == 1024.0).all()
+
+
+# B, HW, C: C not a multiple of 8; B * C (forward) and B * HW * C (backward) below, at and above one pass
+GAPS = [(3, 16, 5), (1, 1, 1), (7, 49, 37), (4096, 4, 512), (2048, 2, 1025), (4, 64, 8192), (5, 64, 8193)]
+
+
+@pytest.mark.parametrize("B,HW,C", GAPS)
+def test_gap_fwd_bwd(B, HW, C):
+    """Integers in [-8, 8]: the fp32 sum over HW is exact, so is the division by a power of two (equal to fp64
+    after the bf16 rounding of the quotient); HW = 49: within one bf16 ulp of fp64."""
+    g = torch.Generator(device=dev).manual_seed(B + HW + C)
+    x = torch.randint(-8, 9, (B, HW, 1, C), device=dev, generator=g).to(torch.bfloat16)
+    buf, y = _sentinel_out(B * C)
+    ops.gap_fwd(x, y.view(B, C))
+    exp = x.double().mean(dim=(1, 2))
+    if HW & (HW - 1) == 0:
+        assert torch.equal(y.view(B, C).double(), exp.to(torch.bfloat16).double())
+    else:
+        assert ((y.view(B, C).double() - exp).abs() <= (2.0 ** -7 + 2.0 ** -20) * exp.abs()).all()
+    assert (buf[B * C:] == 1024.0).all()
+    dy = torch.randint(-8, 9, (B, C), device=dev, generator=g).to(torch.bfloat16)
+    buf, dx = _sentinel_out(B * HW * C)
+    ops.gap_bwd(dy, dx.view(B, HW, 1, C))
+    exp = (dy.double() / HW).view(B, 1, C).expand(B, HW, C)
+    if HW & (HW - 1) == 0:
+        assert torch.equal(dx.view(B, HW, C).double(), exp)
+    else:
+        assert ((dx.view(B, HW, C).double() - exp).abs() <= (2.0 ** -7 + 2.0 ** -20) * exp.abs()).all()
+    assert (buf[B * HW * C:] == 1024.0).all()
+
+
 def test_general_keras_model_gpu_matches_cpu_engine():
     from distriflow_amd.models.keras import layers_from_keras
     from distriflow_amd.models.net import Net

@@ -1,11 +1,14 @@
 """Numerics of every gfx950 HIP kernel against a plain-PyTorch fp32 reference of the same op.
 
 Inputs are rounded to bf16 first (the kernels consume bf16), the reference computes in fp32 on the
-same rounded values; tolerances cover the bf16 rounding of outputs only.
+same rounded values; tolerances cover the bf16 rounding of outputs only.  The ``*_exact_on_integers`` tests
+compare the conv, dense and weight-gradient kernels with an fp64 reference by ``torch.equal`` instead
+(tests/exact_util.py).
 """
 import pytest
 import torch
 
+import exact_util as xu
 from distriflow_amd import ops
 from distriflow_amd.ops import reference as ref
 
@@ -445,8 +448,11 @@ def test_batchnorm(M, C, relu):
 
 
 @pytest.mark.parametrize("M,C", [(32768, 64), (4096, 512)])
-def test_bn_fused_backward_matches_two_launches(M, C, monkeypatch):
-    """Backward statistics + dx in one launch == the statistics launch + the dx launch."""
+def test_bn_bwd_matches_accumulated_route(M, C):
+    """The statistics-launch backward (bn_bwd) against the accumulated route (bn_dx_acc fed the fp64 sums of the
+    same gradient), and both against fp64.  bn_bwd is launched twice on the same counters (its last workgroups
+    re-arm the tickets) and must agree with itself; its fp32 statistics are held to the bounds of
+    test_batchnorm, bn_dx_acc to the derived ones of tests/exact_util.py."""
     torch.manual_seed(C)
     x = torch.randn(M, C, device=dev).to(torch.bfloat16)
     mask = torch.randn(M, C, device=dev).to(torch.bfloat16)
@@ -454,18 +460,47 @@ def test_bn_fused_backward_matches_two_launches(M, C, monkeypatch):
     g = torch.rand(C, device=dev) + 0.5
     mean, inv = x.float().mean(0), torch.rsqrt(x.float().var(0, unbiased=False) + 1e-5)
     ws = torch.empty(ops.bn_workspace_floats(C), device=dev)
+    cnt = torch.zeros(2, ops.BN_COUNTERS, dtype=torch.int32, device=dev)
     outs = []
-    for fused in ("0", "1"):
-        monkeypatch.setenv("DISTRIFLOW_DIAG", f"bn_fused={fused}")
-        cnt = torch.zeros(2, ops.BN_COUNTERS, dtype=torch.int32, device=dev)
-        dx, dg, db, coef = torch.empty_like(x), torch.empty(C, device=dev), torch.empty(C, device=dev), torch.empty(3 * C, device=dev)
-        for _ in range(2):
-            ops.bn_bwd(x, mask, dy, dx, g, mean, inv, dg, db, ws, coef, cnt[1])
+    for _ in range(2):
+        dx, dg, db, coef = (torch.empty_like(x), torch.empty(C, device=dev), torch.empty(C, device=dev),
+                            torch.empty(3 * C, device=dev))
+        ops.bn_bwd(x, mask, dy, dx, g, mean, inv, dg, db, ws, coef, cnt[1])
         torch.cuda.synchronize()
-        outs.append((dx.float(), dg.clone(), db.clone(), coef.clone()))
+        assert int(cnt[1].abs().sum()) == 0
+        outs.append((dx.float(), dg, db, coef))
     for a, b in zip(outs[0][1:], outs[1][1:]):
         torch.testing.assert_close(b, a, rtol=1e-4, atol=1e-5)
     assert ((outs[1][0] - outs[0][0]).abs() <= outs[0][0].abs() * 2 ** -6 + 1e-4).all()
+    # fp64 reference: g = dy * [mask > 0], xhat from the fp32 mean / invstd the kernels are given
+    gm = (dy.float() * (mask.float() > 0)).to(torch.bfloat16)
+    xd, gd, ga, mu, isd = x.double(), gm.double(), g.double(), mean.double(), inv.double()
+    S, Q = gd.sum(0), (gd * (xd - mu) * isd).sum(0)
+    k1 = ga * isd
+    k2, k3 = -k1 * isd * (Q / M), k1 * (mu * isd * (Q / M) - S / M)
+    edx, terms = k1 * gd + k2 * xd + k3, (k1 * gd).abs() + (k2 * xd).abs() + k3.abs()
+    # the accumulated route, its sums split over 8 replicas
+    accbuf, acc = xu.split_replicas(torch.stack([S, Q]), 8, -1.0)
+    adx, adg, adb, acoef = (torch.empty_like(x), torch.empty(C, device=dev), torch.empty(C, device=dev),
+                            torch.empty(3 * C, device=dev))
+    ops.bn_dx_acc(x, gm, adx, acc, None, g, mean, inv, adg, adb, acoef)
+    Sr, Qr = acc[:, 0].sum(0), acc[:, 1].sum(0)
+    xu.assert_within_ulps(adb, Sr, 2, "bn_dx_acc dbeta")
+    xu.assert_within_ulps(adg, Qr, 2, "bn_dx_acc dgamma")
+    xu.assert_within_ulps(acoef, torch.cat([k1, k2, k3]), 2, "bn_dx_acc coef")
+    xu.assert_close_elem(adx, edx, terms, "bn_dx_acc dx")
+    # bn_bwd: fp32 statistics
+    bdx, bdg, bdb, bcoef = outs[1]
+    _close(bdx, edx, 3e-2, 3e-2)
+    _close(bdg, Q, 1e-2, 1e-2)
+    _close(bdb, S, 1e-3, 1e-3)
+    for i, k in enumerate((k1, k2, k3)):  # (k2, k3 are small: relative to each row's own largest entry)
+        _close(bcoef[i * C:(i + 1) * C], k, 1e-2, 1e-6)
+        _close(bcoef[i * C:(i + 1) * C], acoef[i * C:(i + 1) * C], 1e-2, 1e-6)
+    # ... and the two routes with each other (the sum of the two bounds)
+    _close(bdx, adx, 3e-2, 3e-2)
+    _close(bdg, adg, 1e-2, 1e-2)
+    _close(bdb, adb, 1e-3, 1e-3)
 
 
 @pytest.mark.parametrize("proj", [False, True])
@@ -563,6 +598,89 @@ def test_conv_splitk_fwd_and_dgrad(B, H, W, C, N):
     exp = ref.conv_dgrad(dy.float(), w.to(torch.bfloat16).float(), (B, H, W, C), k, k, 1, 1, None)
     exp = (exp + res.float() * (rmask.float() > 0)) * (mask.float() > 0)
     _close(dx, exp)
+
+
+# ---- exact on integers (tests/exact_util.py): inputs, weights and bias from small integers make every product,
+# every fp32 partial sum in any order and every bf16 / fp32 output exactly representable, so the kernels are
+# compared with an fp64 reference by torch.equal: one lost tap at one border pixel, one wrong halo pixel or one
+# dropped row fails, which the _close tests above (about 0.1 on values of standard deviation 1) let pass.  Those
+# stay: they cover non-integer data and the rounding paths.
+SPLITK = [(16, 4, 4, 512, 512), (8, 8, 8, 256, 256), (3, 4, 4, 256, 512)]
+CONV_EXACT = CONVS + [c + (3, 1, 1) for c in CONV_HALO[:6] + [c for c in SPLITK if c not in CONV_HALO[:6]]]
+
+
+@pytest.mark.parametrize("B,H,W,C,N,k,s,p", CONV_EXACT)
+def test_conv_exact_on_integers(B, H, W, C, N, k, s, p):
+    """Forward with bias + ReLU (and bare: the halo kernels take no bias), data gradient with mask + residual +
+    residual mask.  x, dy in {-1, 0, 1}, about 64 non-zero weights per reduction, so |y| <= 256 holds (asserted)."""
+    g = xu.gen(B + H + W + C + N + k)
+    OH, OW = ops.conv_out_hw(H, W, k, k, s, p)
+    x = xu.ints(g, (B, H, W, C), -1, 1)
+    w = xu.sparse_ints(g, (N, k * k * C), -1, 1, xu.weight_density(k * k * max(C, N)))
+    b = xu.ints(g, (N,), -3, 3)
+    xd, wd, bd = xu.bf16(x, dev), xu.pad_w(w, dev), b.float().to(dev)
+    for bias, relu in ((bd, True), (None, False)):
+        exp = xu.conv_fwd_ref(x.to(dev), w.to(dev), b.to(dev) if bias is not None else None, k, s, p, relu)
+        xu.assert_exact_output(exp)
+        out = torch.full((B, OH, OW, N), float("nan"), device=dev, dtype=torch.bfloat16)
+        ops.conv_fwd(xd, wd, bias, out, k, k, s, p, relu)
+        assert torch.equal(out.double(), exp), f"forward, bias={bias is not None} relu={relu}"
+    dy = xu.ints(g, (B, OH, OW, N), -1, 1)
+    res, rmask, mask = xu.ints(g, (B, H, W, C), -2, 2), xu.ints(g, (B, H, W, C), -1, 1), xu.ints(g, (B, H, W, C), -1, 1)
+    exp = xu.join_ref(xu.conv_dgrad_ref(dy.to(dev), w.to(dev), (B, H, W, C), k, s, p), res.to(dev), rmask.to(dev),
+                      mask.to(dev))
+    xu.assert_exact_output(exp)
+    dx = torch.full((B, H, W, C), float("nan"), device=dev, dtype=torch.bfloat16)
+    ops.conv_dgrad(xu.bf16(dy, dev), None, xu.pad_wt(w, N, k * k, C, dev), dx, k, k, s, p, mask=xu.bf16(mask, dev),
+                   residual=xu.bf16(res, dev), residual_mask=xu.bf16(rmask, dev))
+    assert torch.equal(dx.double(), exp), "data gradient with the block join"
+
+
+@pytest.mark.parametrize("M,N,K", DENSE)
+def test_dense_exact_on_integers(M, N, K):
+    """Forward with bias + ReLU into bf16 and fp32, masked data gradient, weight / bias gradient with scale 0.5."""
+    g = xu.gen(M + N + K)
+    x, w, b = xu.ints(g, (M, K), -1, 1), xu.sparse_ints(g, (N, K), -1, 1, xu.weight_density(max(K, N))), xu.ints(g, (N,), -3, 3)
+    xd, wd, bd = xu.bf16(x, dev), xu.pad_w(w, dev), b.float().to(dev)
+    exp = torch.relu(x.to(dev) @ w.to(dev).t() + b.to(dev))
+    xu.assert_exact_output(exp)
+    for dt in (torch.bfloat16, torch.float32):
+        out = torch.full((M, N), float("nan"), device=dev, dtype=dt)
+        ops.dense_fwd(xd, wd, bd, out, True)
+        assert torch.equal(out.double(), exp), f"forward into {dt}"
+    dy, mask = xu.ints(g, (M, N), -1, 1), xu.ints(g, (M, K), -1, 1)
+    exp = (dy.to(dev) @ w.to(dev)) * (mask.to(dev) > 0)
+    xu.assert_exact_output(exp)
+    dx = torch.full((M, K), float("nan"), device=dev, dtype=torch.bfloat16)
+    ops.dense_dgrad(xu.bf16(dy, dev), None, xu.pad_wt(w, N, 1, K, dev), dx, mask=xu.bf16(mask, dev))
+    assert torch.equal(dx.double(), exp), "data gradient"
+    # every partial sum of dy^T x is an integer of magnitude <= M < 2^24
+    gw, gb = torch.full((N, K), float("nan"), device=dev), torch.full((N,), float("nan"), device=dev)
+    ops.dense_wgrad(xu.bf16(dy, dev), xd, gw, gb, torch.empty(1 << 22, device=dev), scale=0.5)
+    assert M < xu.FP32_INT_MAX
+    assert torch.equal(gw.double(), 0.5 * (dy.to(dev).t() @ x.to(dev))), "weight gradient"
+    assert torch.equal(gb.double(), 0.5 * dy.to(dev).sum(0)), "bias gradient"
+
+
+WGRAD_EXACT = ([c + (True, 1 << 22) for c in CONVS] + [c + (False, 1 << 24) for c in WGRAD_TR] +
+               [c[:5] + (3, 1, 1, False, c[5]) for c in WGRAD_HALO] + [c[1:] + (1 << 24,) for c in WGRAD_PLANNED])
+
+
+@pytest.mark.parametrize("B,H,W,C,N,k,s,p,bias,wsf", WGRAD_EXACT)
+def test_conv_wgrad_exact_on_integers(B, H, W, C, N, k, s, p, bias, wsf):
+    """Weight gradient with scale 0.5 (and bias where the list's own test passes one): the slabs of a split
+    reduction and their fixed-order sum are exact while sum_m |dy * x| < 2^24 per element (asserted)."""
+    g = xu.gen(B + H + W + C + N + k + wsf % 7)
+    OH, OW = ops.conv_out_hw(H, W, k, k, s, p)
+    x, dy = xu.ints(g, (B, H, W, C), -2, 2), xu.ints(g, (B, OH, OW, N), -2, 2)
+    ew, eb, ab = xu.conv_wgrad_ref(dy.to(dev), x.to(dev), k, s, p)
+    assert float(ab.max()) < xu.FP32_INT_MAX and float(dy.abs().sum((0, 1, 2)).max()) < xu.FP32_INT_MAX
+    gw = torch.full((N, k * k * C), float("nan"), device=dev)
+    gb = torch.full((N,), float("nan"), device=dev) if bias else None
+    ops.conv_wgrad(xu.bf16(dy, dev), xu.bf16(x, dev), gw, gb, torch.empty(wsf, device=dev), k, k, s, p, scale=0.5)
+    assert torch.equal(gw.double(), 0.5 * ew), "weight gradient"
+    if bias:
+        assert torch.equal(gb.double(), 0.5 * eb), "bias gradient"
 
 
 CONVPOOL = [  # B, H, W, C, N, k, pad
