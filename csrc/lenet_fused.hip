@@ -7,8 +7,12 @@
 // LeNet-5 is small enough that a workgroup can keep EVERYTHING of its images on chip, so here:
 //
 //   lenet_prep_kernel    the conv weights of this step as ready-made MFMA B fragments (banded conv1,
-//                        conv2 forward, pair-banded conv2 data gradient): 37 x 1 KB, read by every
-//                        workgroup with one 16-byte load per lane and fragment
+//                        conv2 forward, pair-banded conv2 data gradient): 37 x 1 KB.  A workgroup loads the
+//                        22 conv1 / conv2 forward fragments once (16-byte pieces, at most 3 per thread, in
+//                        phase 0) into LDS scratch that later phases overwrite, and its 8 waves take them
+//                        from there with one ds_read_b128 per lane and fragment; the 15 data-gradient
+//                        fragments are still loaded by every wave (no LDS is free while dC2 is live; the
+//                        loads are in flight under the conv2 weight gradient)
 //   lenet_train_kernel   one workgroup = 8 images (fewer at small batches: lenet_ipw), 8 waves, ~78 KB of
 //                        LDS (two workgroups per CU):
 //     conv1 5x5 'same' + bias + ReLU + 2x2 max-pool   MFMA with a banded (Toeplitz) weight operand:
@@ -86,13 +90,24 @@ constexpr int U_G = 32 + XS_ELEMS * 2 + 4 * 16 * 32 * 4;
 // phase F's "no tap" entries read one (dc2_swz(100) = 96).
 __device__ __forceinline__ int dc2_swz(int t) { return t ^ ((t >> 3) & 7); }
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
+// conv1 / conv2 B fragments (FR_C1, FR_C2: 22 x 1 KB, lane-linear), loaded once per workgroup in phase 0
+// and handed to the waves through LDS.  The conv1 image lies under Xs1: every wave has read it before
+// the barrier in front of build_shift1, which overwrites all of it.  The conv2 image has to survive
+// phase A and be readable while other waves already write phase B's outputs, so it sits behind the
+// dense buffers (H0 .. C2); phase D's dC2 is the first to overwrite it.
+constexpr int NFP1 = (FR_C2 - FR_C1) * 64, NFP2 = (FR_DG - FR_C2) * 64;  // 16-byte pieces
+constexpr int OFF_FC1 = OFF_XS1;
+constexpr int OFF_FC2 = OFF_U + U_DENSE;
+constexpr int U_FC2 = U_DENSE + NFP2 * 16;
+static_assert(FR_C1 == 0 && FR_C2 - FR_C1 == 15 && FR_DG - FR_C2 == 7, "phase 0 stages fragments 0 .. 21 as one range");
+static_assert(OFF_FC1 + NFP1 * 16 <= OFF_XS1 + (XS_ELEMS / 8 - 1) * 16, "build_shift1 overwrites the conv1 fragments");
 // dense biases (f32: dense-1 [120], dense-2 [84], dense-3 [10]), staged in phase 0: read from LDS, a
 // bias load never waits behind the weight prefetches issued before it
-constexpr int OFF_DB = OFF_U + (cmax(cmax(U_DENSE, U_DC2), U_G) + 15) / 16 * 16;
+constexpr int OFF_DB = OFF_U + (cmax(cmax(cmax(U_DENSE, U_DC2), U_G), U_FC2) + 15) / 16 * 16;
 constexpr int OFF_ST = OFF_DB + 864;                // u64 [16] diagnostic phase clocks (LN_STAMP)
 constexpr int LDS_BYTES = OFF_ST + 128;
 static_assert(OFF_U == OFF_C1 + IMG * 196 * 4 + 128 + 98 * 2 * 16 + 800 * 2 + 128 && OFF_U % 16 == 0 && OFF_KZ % 16 == 0 && OFF_H1 % 16 == 0 && OFF_ZR % 16 == 0 && OFF_C2 % 16 == 0 && OFF_RED % 16 == 0 && OFF_DB % 16 == 0 && OFF_ST % 16 == 0 &&
-                  OFF_PX % 16 == 0 && OFF_W % 16 == 0,
+                  OFF_PX % 16 == 0 && OFF_W % 16 == 0 && OFF_FC1 % 16 == 0 && OFF_FC2 % 16 == 0,
               "LDS carve must stay 16-byte aligned");
 static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 
@@ -417,8 +432,9 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
 
   // ---------------------------------------------------------------- phase 0: zero fills, staging
   // Global loads in dependency order (a wait for one load also waits for every load issued before it):
-  // first the indices, then the tables / biases, the conv1 fragments and, once its index is back, this
-  // thread's input row; everything lands in registers and is stored to LDS after the zero fills.
+  // first the indices, then the tables / biases, this thread's pieces of the conv1 / conv2 fragments and,
+  // once its index is back, its label and input row; everything lands in registers and is stored to LDS
+  // after the zero fills (the input row after the first barrier: nothing before it waits for it).
   const int ximg = tid / 28, xrow = tid - 28 * (tid / 28);  // input row of this thread
   const bool xload = tid < IMG * 28 && ximg < rows;
   const bool lload = tid >= 256 && tid < 256 + IMG && tid - 256 < rows;  // label of image tid - 256
@@ -432,21 +448,30 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   float biasv = 0.f, dbv = 0.f;
   if (tid >= 448 && tid < 448 + 22) biasv = *(tid < 454 ? a.b1 + (tid - 448) : a.b2 + (tid - 454));
   if (tid < 214) dbv = *(tid < 120 ? a.d1b + tid : (tid < 204 ? a.d2b + (tid - 120) : a.d3b + (tid - 204)));
-  // conv1 B fragments of this step (lenet_prep_kernel)
-  bf16x8 bc[15];
+  // conv1 and conv2 B fragments of this step (lenet_prep_kernel): 1408 pieces of 16 bytes, at most 3 per
+  // thread, once per workgroup (every wave loading all of them for itself was 8 x the traffic, in front
+  // of conv1's and conv2's first MFMA).  Unconditional for the same reason as the label and the row below
+  // (a thread past the last piece re-reads it): the wait for the indices then knows that exactly these
+  // loads follow them and does not wait for a fragment piece.
+  constexpr int NFK = ccdiv(NFP1 + NFP2, NT);
+  bf16x8 fv[NFK];
 #pragma unroll
-  for (int f = 0; f < 15; ++f) bc[f] = frag[(FR_C1 + f) * 64 + lane];
-  int lbl = 0;
-  if (lload) lbl = a.labels[lsrc < 0 ? 0 : (lsrc >= a.nrows ? a.nrows - 1 : lsrc)];
+  for (int k = 0; k < NFK; ++k) fv[k] = frag[FR_C1 * 64 + min(tid + NT * k, NFP1 + NFP2 - 1)];
+  // The label and the input row are loaded by EVERY thread (one without a label / a row reads element 0:
+  // one address per wave, its value unused).  A wait count is a compile-time constant, so behind a
+  // conditional load the fragment pieces' wait had to assume no load followed them and became
+  // vmcnt(0): the first barrier then waited for the input rows as well.
+  const int lbl = a.labels[lsrc < 0 ? 0 : (lsrc >= a.nrows ? a.nrows - 1 : lsrc)];
   unsigned xv[14];
-  if (xload) {
+  {
     const long long src = xsrc < 0 ? 0 : (xsrc >= a.nrows ? a.nrows - 1 : xsrc);
+    const int xr = xload ? xrow : 0;
     if (a.x_u8 != nullptr) {
-      const unsigned* p = reinterpret_cast<const unsigned*>(a.x_u8 + src * 784 + xrow * 28);
+      const unsigned* p = reinterpret_cast<const unsigned*>(a.x_u8 + src * 784 + xr * 28);
 #pragma unroll
       for (int k = 0; k < 7; ++k) xv[k] = p[k];
     } else {
-      const uint2* p = reinterpret_cast<const uint2*>(a.x_bf + src * 784 + xrow * 28);
+      const uint2* p = reinterpret_cast<const uint2*>(a.x_bf + src * 784 + xr * 28);
 #pragma unroll
       for (int k = 0; k < 7; ++k) {
         const uint2 v = p[k];
@@ -463,7 +488,18 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   one6[6] = (bf16)1.f;
   for (int e = tid; e < (OFF_K - OFF_XS) / 16; e += NT)
     st8(Xs + 8 * e, (e >= OFF_P1 / 16 && e < OFF_C1 / 16) ? one6 : z8);
-  for (int e = tid; e < (OFF_DB - OFF_U) / 16; e += NT) st8(reinterpret_cast<bf16*>(smem + OFF_U) + 8 * e, z8);
+  // the union, except the two fragment images (staged below by other threads: no zero may land on them;
+  // build_shift1 and phase D overwrite them before anything else reads those bytes)
+  static_assert(OFF_FC2 + NFP2 * 16 == OFF_DB, "the conv2 fragment image ends the union");
+  if (tid < (OFF_FC1 - OFF_U) / 16) st8(reinterpret_cast<bf16*>(smem + OFF_U) + 8 * tid, z8);
+  for (int e = (OFF_FC1 - OFF_U) / 16 + NFP1 + tid; e < (OFF_FC2 - OFF_U) / 16; e += NT)
+    st8(reinterpret_cast<bf16*>(smem + OFF_U) + 8 * e, z8);
+#pragma unroll
+  for (int k = 0; k < NFK; ++k) {
+    const int p = tid + NT * k;
+    if (p < NFP1) st8(reinterpret_cast<bf16*>(smem + OFF_FC1) + 8 * p, fv[k]);
+    else if (p < NFP1 + NFP2) st8(reinterpret_cast<bf16*>(smem + OFF_FC2) + 8 * (p - NFP1), fv[k]);
+  }
   if (tid < 2) {
     bf16x8 o;
 #pragma unroll
@@ -481,6 +517,11 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   int* LBL = reinterpret_cast<int*>(WS + 24);
   if (tid >= 256 && tid < 256 + IMG) LBL[tid - 256] = lbl;  // clamped where read (no wait for it here)
   __syncthreads();
+  // conv1 B fragments from the workgroup's copy (lane-linear ds_read_b128s); the barrier in front of
+  // build_shift1, which overwrites the copy, also ends these reads
+  bf16x8 bc[15];
+#pragma unroll
+  for (int f = 0; f < 15; ++f) bc[f] = ld8(reinterpret_cast<const bf16*>(smem + OFF_FC1) + 8 * (f * 64 + lane));
   // input rows -> bf16, 2-pixel zero border ('same' padding)
   if (xload) {
     unsigned* dst = reinterpret_cast<unsigned*>(Xs + ximg * 1024 + (xrow + 2) * 32 + 2);
@@ -547,11 +588,11 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   LN_STAMP(2);
 
   // ---------------------------------------------------------------- phase B: conv2 + ReLU + pool
-  // conv2 fragments first, then the dense-1 weights (L2 latency hidden behind conv2): a wait for the
-  // fragments then never waits for the dense-1 loads
+  // conv2 fragments from the workgroup's copy (staged in phase 0; nothing writes it before phase D),
+  // then the dense-1 weights (L2 latency hidden behind conv2)
   bf16x8 bw[7];
 #pragma unroll
-  for (int s = 0; s < 7; ++s) bw[s] = frag[(FR_C2 + s) * 64 + lane];
+  for (int s = 0; s < 7; ++s) bw[s] = ld8(reinterpret_cast<const bf16*>(smem + OFF_FC2) + 8 * (s * 64 + lane));
   DenseFrags<13, ccdiv(8, NW)> f1;
   dense_load(f1, a.d1w, 8);
   {
