@@ -73,6 +73,45 @@ def pad_wt(w2d, N, T, Ci, device):
     return out.to(device)
 
 
+def rowpad_w(w2d, KH, KW, C, H, W, pad, device):
+    """[N][KH*KW*C] -> fused conv+pool forward layout bf16 [Npad16][Kpad2]: column ky*RLp + kx*Cp + c with the
+    kernel's channel stride Cp; pair layout (N <= 8) additionally holds in rows 8+n the kernel of channel n
+    shifted right by one column (RLp = round8((KW+1)*Cp))."""
+    from distriflow_amd import ops
+    N = w2d.shape[0]
+    Cp, kp, pair = ops.convpool_fwd_layout(H, W, C, KH, KW, pad, N)
+    RLp = _r((KW + (1 if pair else 0)) * Cp, 8)
+    out = torch.zeros(_r(N, 16), kp, dtype=torch.bfloat16, device=w2d.device)
+    w4 = w2d.view(N, KH, KW, C).to(torch.bfloat16)
+    for ky in range(KH):
+        for kx in range(KW):
+            out[:N, ky * RLp + kx * Cp: ky * RLp + kx * Cp + C] = w4[:, ky, kx]
+            if pair:
+                out[8:8 + N, ky * RLp + (kx + 1) * Cp: ky * RLp + (kx + 1) * Cp + C] = w4[:, ky, kx]
+    return out.to(device)
+
+
+def cp_wt(w2d, KH, KW, C, H, W, pad, device):
+    """[N][KH*KW*C] -> fused conv+pool data-gradient layout: the plain [Cpad16][K2pad] layout of :func:`pad_wt`,
+    or the pair layout [16][round32(KH*(KW+1)*N)] (row c: tap (a, b) = W[n][KH-1-a][KW-1-b][c]; row 8+c: the
+    same shifted by one column, W[n][KH-1-a][KW-b][c])."""
+    from distriflow_amd import ops
+    N = w2d.shape[0]
+    pair, k2p = ops.convpool_dgrad_layout(H, W, C, KH, KW, pad, N)
+    if not pair:
+        return pad_wt(w2d, N, KH * KW, C, device)
+    out = torch.zeros(16, k2p, dtype=torch.bfloat16, device=w2d.device)
+    w4 = w2d.view(N, KH, KW, C).to(torch.bfloat16)
+    for a in range(KH):
+        for b in range(KW + 1):
+            col = (a * (KW + 1) + b) * N
+            if b < KW:
+                out[:C, col:col + N] = w4[:, KH - 1 - a, KW - 1 - b, :].t()
+            if b >= 1:
+                out[8:8 + C, col:col + N] = w4[:, KH - 1 - a, KW - b, :].t()
+    return out.to(device)
+
+
 def _chunk(B, per_image_elems, budget=1 << 25):
     return max(1, min(B, budget // max(1, per_image_elems)))
 
@@ -137,6 +176,94 @@ def join_ref(dx, res, rmask, mask):
     if mask is not None:
         dx = dx * (mask.double() > 0)
     return dx
+
+
+# ------------------------------------------------------------------------------------- max-pool, ties included
+# The tie rule every argmax kernel documents: the FIRST maximum in row-major window order (j = dy * P + dx).
+def windows(y, P=2):
+    """[B][OH][OW][N] -> [B][OH//P][OW//P][N][P*P] in row-major window order; rows / columns past the last whole
+    window are dropped."""
+    B, OH, OW, N = y.shape
+    PH, PW = OH // P, OW // P
+    return y[:, :PH * P, :PW * P].reshape(B, PH, P, PW, P, N).permute(0, 1, 3, 5, 2, 4).reshape(B, PH, PW, N, P * P)
+
+
+def window_argmax(win):
+    """win [..., P*P] in row-major window order -> (max, index of the first maximum): an explicit scan with a
+    strict ``>``, so nothing rests on the tie behaviour of ``torch.max``."""
+    m = win[..., 0].clone()
+    am = torch.zeros(m.shape, dtype=torch.int64, device=win.device)
+    for j in range(1, win.shape[-1]):
+        v = win[..., j]
+        better = v > m
+        m = torch.where(better, v, m)
+        am = torch.where(better, torch.full_like(am, j), am)
+    return m, am
+
+
+def code_convpool(m, am):
+    """csrc/convpool.hip: argmax | 4 * (max > 0)."""
+    return (am | ((m > 0).to(torch.int64) << 2)).to(torch.uint8)
+
+
+def code_relu4(m, am):
+    """csrc/kcnn_fused.hip, the igemm64 POOL epilogue and unpool2: argmax, or 4 (no gradient) when max <= 0."""
+    return torch.where(m > 0, am, torch.full_like(am, 4)).to(torch.uint8)
+
+
+def unpool_ref(dyp, code, OH, OW, convention):
+    """fp64 full-resolution gradient [B][OH][OW][N] of a 2x2 max-pool from the pooled gradient and the codes of
+    ``convention`` ('convpool' | 'relu4'); zero outside the windows and where the code passes nothing."""
+    B, PH, PW, N = code.shape
+    c = code.long()
+    if convention == "convpool":
+        pos, live = c & 3, (c & 4) > 0
+    elif convention == "relu4":
+        pos, live = c.clamp_max(3), c < 4
+    else:
+        raise ValueError(convention)
+    g = dyp.double().reshape(B, PH, PW, N) * live
+    out = torch.zeros(B, OH, OW, N, dtype=torch.float64, device=code.device)
+    for j in range(4):
+        out[:, j // 2:2 * PH:2, j % 2:2 * PW:2] = g * (pos == j)
+    return out
+
+
+def pool_max_ref(x, geom):
+    """General max-pool of x [B][H][W][C] over ``geom`` (``ops.pool_geometry``): windows clipped to the image, any
+    stride, overlap allowed.  -> (y [B][OH][OW][C] fp64 with 0 for an empty window, max, row and column of the
+    first maximum in row-major scan order; row -1 for an empty window)."""
+    B, H, W, C, OH, OW, ph, pw, sh, sw, pt, pl = geom
+    x = x.double()
+    dev = x.device
+    m = torch.full((B, OH, OW, C), float("-inf"), dtype=torch.float64, device=dev)
+    ah = torch.full((B, OH, OW, C), -1, dtype=torch.int64, device=dev)
+    aw = ah.clone()
+    oh, ow = torch.arange(OH, device=dev), torch.arange(OW, device=dev)
+    for i in range(ph):
+        for j in range(pw):
+            hh, ww = oh * sh - pt + i, ow * sw - pl + j
+            inside = ((hh >= 0) & (hh < H))[:, None] & ((ww >= 0) & (ww < W))[None, :]
+            v = x[:, hh.clamp(0, H - 1)][:, :, ww.clamp(0, W - 1)]
+            better = inside[None, :, :, None] & (v > m)
+            m = torch.where(better, v, m)
+            ah = torch.where(better, hh[None, :, None, None].expand_as(ah), ah)
+            aw = torch.where(better, ww[None, None, :, None].expand_as(aw), aw)
+    return torch.where(ah >= 0, m, torch.zeros_like(m)), m, ah, aw
+
+
+def pool_max_bwd_ref(x, dy, geom, relu):
+    """fp64 gradient of :func:`pool_max_ref`: every window sends its gradient to its first maximum, gradients sum
+    per input pixel; with ``relu`` a window whose maximum is not positive sends nothing."""
+    B, H, W, C, OH, OW = geom[:6]
+    _, m, ah, aw = pool_max_ref(x, geom)
+    live = (ah >= 0) & (m > 0) if relu else ah >= 0
+    b = torch.arange(B, device=m.device)[:, None, None, None]
+    c = torch.arange(C, device=m.device)[None, None, None, :]
+    flat = ((b * H + ah.clamp_min(0)) * W + aw.clamp_min(0)) * C + c
+    dx = torch.zeros(B * H * W * C, dtype=torch.float64, device=m.device)
+    dx.index_add_(0, flat.reshape(-1), (dy.double().reshape(B, OH, OW, C) * live).reshape(-1))
+    return dx.view(B, H, W, C)
 
 
 # ---------------------------------------------------------------------------- conditions of exactness

@@ -78,6 +78,38 @@ def test_pooled_conv_epilogue_equals_conv_then_pool(B, H, C, N, pad, drop):
     assert torch.equal(d_out, d_ref)
 
 
+@pytest.mark.parametrize("B,H,C,N,pad", [(4, 26, 32, 64, 0), (3, 14, 16, 32, 1), (2, 12, 8, 16, 0)])
+def test_pooled_conv_epilogue_exact_on_integers(B, H, C, N, pad):
+    """igemm64 POOL against fp64, independent of maxpool_bwd: x in {-1, 0, 1}, about 64 non-zero weights per
+    reduction, bias in [-3, 3].  The pooled map equals max(conv, 0) over each window and every code the first
+    maximum in row-major order (4 where the maximum is not positive); with a folded dropout of p = 0.5 (scale 2:
+    exact) the map is the reference times the CPU hash twin's mask, the codes those of the undropped map."""
+    import exact_util as xu
+    from distriflow_amd.ops import reference as ref
+
+    g = xu.gen(B + H + C + N + pad)
+    K = 9 * C
+    x = xu.ints(g, (B, H, H, C), -1, 1)
+    w = xu.sparse_ints(g, (N, K), -1, 1, xu.weight_density(K))
+    b = xu.ints(g, (N,), -3, 3)
+    assert ops.conv_pool_supported(H, H, C, 3, 3, 1, pad, N)
+    y = xu.conv_fwd_ref(x.to(dev), w.to(dev), b.to(dev), 3, 1, pad, relu=False)
+    xu.assert_exact_output(y)
+    m, am = xu.window_argmax(xu.windows(y))
+    exp, ecode = m.clamp_min(0), xu.code_relu4(m, am)
+    assert all(bool((ecode == c).any()) for c in range(5))
+    xd, wd, bd = xu.bf16(x, dev), xu.pad_w(w, dev), b.float().to(dev)
+    step = torch.tensor(5, dtype=torch.int64, device=dev)
+    keep = ref.dropout_mask(exp.numel(), 0.5, 77 ^ (5 * 0x9E3779B1)).double().view(exp.shape).to(dev)
+    assert 2 * float(exp.max()) <= xu.BF16_INT_MAX
+    for drop, want in ((None, exp), ((0.5, 77, step), 2 * exp * keep)):
+        out = torch.full(exp.shape, float("nan"), dtype=torch.bfloat16, device=dev)
+        code = torch.full(exp.shape, 255, dtype=torch.uint8, device=dev)
+        ops.conv_pool_fwd(xd, wd, bd, out, code, 3, 3, 1, pad, relu=True, drop=drop)
+        assert torch.equal(code, ecode), f"codes, drop={drop is not None}"
+        assert torch.equal(out.double(), want), f"pooled map, drop={drop is not None}"
+
+
 def test_keras_cnn_plan_has_no_dropout_launch():
     from distriflow_amd.models.layers import ConvPoolGemm, Dense, Dropout, KerasConvBlock, MaxPooling2D
     from distriflow_amd.models.zoo import build_model

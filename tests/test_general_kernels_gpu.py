@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import exact_util as xu
 from distriflow_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -82,6 +83,36 @@ def test_pool2d(H, C, pool, stride, pad, avg):
                 mx = ops._pool_ref(x.float(), geom, False)
                 gr = torch.autograd.grad(ops._pool_ref(xv, geom, False), xv, dy.float() * (mx > 0))[0]
         torch.testing.assert_close(dx.float().cpu(), gr, rtol=2e-2, atol=2e-2)
+
+
+@pytest.mark.parametrize("H,C,pool,stride,pad", [
+    (13, 8, (3, 3), (2, 2), "same"),     # overlapping windows, clipped at the border
+    (7, 3, (2, 3), (2, 1), "valid"),     # overlapping along the row only, scalar channels
+    (9, 16, (9, 9), (9, 9), "valid"),    # a global max pool
+])
+def test_pool2d_max_exact_with_ties(H, C, pool, stride, pad):
+    """Integer data (x in [-3, 1], dy in [-3, 3]: exact, most windows tied, and of 9 values at most 1 in 8 windows
+    has none positive) against the fp64 reference of tests/exact_util.py: each window sends its gradient to its
+    first maximum in row-major order, the gradients of overlapping windows sum per input pixel (at most 9 of
+    magnitude 3: exact in bf16); with in_relu a window whose maximum is not positive sends nothing."""
+    B = 3
+    g = xu.gen(H + C)
+    geom = ops.pool_geometry(B, H, H, C, pool, stride, pad)
+    OH, OW = geom[4], geom[5]
+    x, dy = xu.ints(g, (B, H, H, C), -3, 1), xu.ints(g, (B, OH, OW, C), -3, 3)
+    exp, m, _, _ = xu.pool_max_ref(x.to(dev), geom)
+    xu.assert_exact_output(exp)
+    if pool != (9, 9):
+        assert 0.05 < float((m <= 0).double().mean()) < 0.95, "in_relu would not be exercised"
+    y = torch.full((B, OH, OW, C), float("nan"), dtype=torch.bfloat16, device=dev)
+    ops.pool2d_fwd(xu.bf16(x, dev), y, geom, avg=False)
+    assert torch.equal(y.double(), exp), "forward"
+    for in_relu in (False, True):
+        edx = xu.pool_max_bwd_ref(x.to(dev), dy.to(dev), geom, in_relu)
+        xu.assert_exact_output(edx)
+        dx = torch.full((B, H, H, C), float("nan"), dtype=torch.bfloat16, device=dev)
+        ops.pool2d_bwd(xu.bf16(x, dev), xu.bf16(dy, dev), dx, geom, avg=False, in_relu=in_relu)
+        assert torch.equal(dx.double(), edx), f"backward, in_relu={in_relu}"
 
 
 # ---- csrc/layers.hip: add_act, relu_bwd, gap_fwd, gap_bwd.  One grid-stride pass of these launches is 8192

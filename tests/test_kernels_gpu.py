@@ -3,7 +3,8 @@
 Inputs are rounded to bf16 first (the kernels consume bf16), the reference computes in fp32 on the
 same rounded values; tolerances cover the bf16 rounding of outputs only.  The ``*_exact_on_integers`` tests
 compare the conv, dense and weight-gradient kernels with an fp64 reference by ``torch.equal`` instead
-(tests/exact_util.py).
+(tests/exact_util.py), and so do ``test_maxpool_exact_with_ties`` and ``test_unpool2_exact`` for the pooling
+kernels, whose tie rule (the first maximum in row-major window order) random floats never exercise.
 """
 import pytest
 import torch
@@ -30,21 +31,7 @@ def _pad_w(w2d):
 
 
 def _rowpad_w(w2d, KH, KW, C, H, W, pad):
-    """fp32 [N][KH*KW*C] -> fused conv+pool forward layout bf16 [Npad16][Kpad2]: column
-    ky*RLp + kx*Cp + c with the kernel's channel stride Cp; pair layout (N <= 8) additionally holds
-    in rows 8+n the kernel of channel n shifted right by one column (RLp = round8((KW+1)*Cp))."""
-    from distriflow_amd import ops as O
-    N = w2d.shape[0]
-    Cp, kp, pair = O.convpool_fwd_layout(H, W, C, KH, KW, pad, N)
-    RLp = _r((KW + (1 if pair else 0)) * Cp, 8)
-    out = torch.zeros(_r(N, 16), kp, dtype=torch.bfloat16, device=dev)
-    w4 = w2d.view(N, KH, KW, C).to(torch.bfloat16)
-    for ky in range(KH):
-        for kx in range(KW):
-            out[:N, ky * RLp + kx * Cp: ky * RLp + kx * Cp + C] = w4[:, ky, kx]
-            if pair:
-                out[8:8 + N, ky * RLp + (kx + 1) * Cp: ky * RLp + (kx + 1) * Cp + C] = w4[:, ky, kx]
-    return out
+    return xu.rowpad_w(w2d, KH, KW, C, H, W, pad, dev)
 
 
 def _pad_wt(w2d, N, T, Ci):
@@ -56,24 +43,7 @@ def _pad_wt(w2d, N, T, Ci):
 
 
 def _cp_wt(w2d, KH, KW, C, H, W, pad):
-    """fp32 [N][KH*KW*C] -> fused conv+pool dgrad layout: the plain [Cpad16][K2pad] layout, or the pair
-    layout [16][round32(KH*(KW+1)*N)] (row c: tap (a, b) = W[n][KH-1-a][KW-1-b][c]; row 8+c: the
-    same shifted by one column, W[n][KH-1-a][KW-b][c])."""
-    from distriflow_amd import ops as O
-    N = w2d.shape[0]
-    pair, k2p = O.convpool_dgrad_layout(H, W, C, KH, KW, pad, N)
-    if not pair:
-        return _pad_wt(w2d, N, KH * KW, C)
-    out = torch.zeros(16, k2p, dtype=torch.bfloat16, device=dev)
-    w4 = w2d.view(N, KH, KW, C).to(torch.bfloat16)
-    for a in range(KH):
-        for b in range(KW + 1):
-            col = (a * (KW + 1) + b) * N
-            if b < KW:
-                out[:C, col:col + N] = w4[:, KH - 1 - a, KW - 1 - b, :].t()
-            if b >= 1:
-                out[8:8 + C, col:col + N] = w4[:, KH - 1 - a, KW - b, :].t()
-    return out
+    return xu.cp_wt(w2d, KH, KW, C, H, W, pad, dev)
 
 
 def _close(a, b, rtol=2e-2, atol=2e-2):
@@ -365,6 +335,57 @@ def test_maxpool(B, H, W, C, P):
         # compare sums per window (robust to ties created by bf16 rounding)
         _close(dx.float().sum(), exp.sum(), 1e-2, 1e-2)
         assert ((dx.float() != 0).sum() <= (exp != 0).sum() + 8)
+
+
+@pytest.mark.parametrize("B,H,W,C,P", [
+    (2, 8, 12, 8, 2),    # 8-channel vector path, non-square
+    (2, 6, 6, 3, 2),     # scalar path
+    (2, 9, 9, 16, 3),
+    (1, 7, 5, 8, 2),     # H % P != 0: the row and column outside every window come back zero
+])
+def test_maxpool_exact_with_ties(B, H, W, C, P):
+    """x in [-2, 2] and dy in [-3, 3] (integers: every value exact, most windows tied): the forward equals the
+    fp64 reference, and dx, pre-filled with NaN, carries each window's gradient at its FIRST maximum in row-major
+    order and zero everywhere else; with relu_fused a window whose maximum is not positive passes nothing."""
+    g = xu.gen(B + H + W + C + P)
+    geom = ops.pool_geometry(B, H, W, C, (P, P), (P, P), "valid")
+    x, dy = xu.ints(g, (B, H, W, C), -2, 2), xu.ints(g, (B, H // P, W // P, C), -3, 3)
+    xd, dyd = xu.bf16(x, dev), xu.bf16(dy, dev)
+    exp = xu.pool_max_ref(x.to(dev), geom)[0]
+    xu.assert_exact_output(exp)
+    win = xu.windows(x.to(dev), P)
+    assert float(((win == exp.unsqueeze(-1)).sum(-1) > 1).double().mean()) > 0.25, "the data has too few ties"
+    if P == 2:  # the two references agree with each other
+        assert torch.equal(xu.window_argmax(win)[0], exp)
+    y = torch.full((B, H // P, W // P, C), float("nan"), device=dev, dtype=torch.bfloat16)
+    ops.maxpool_fwd(xd, y, P)
+    assert torch.equal(y.double(), exp), "forward"
+    for relu in (False, True):
+        edx = xu.pool_max_bwd_ref(x.to(dev), dy.to(dev), geom, relu)
+        xu.assert_exact_output(edx)
+        if P == 2:
+            m, am = xu.window_argmax(win)
+            code = xu.code_relu4(m, am) if relu else am.to(torch.uint8)
+            assert torch.equal(edx[:, :H // 2 * 2, :W // 2 * 2], xu.unpool_ref(dy.to(dev), code, H // 2 * 2, W // 2 * 2, "relu4"))
+        dx = torch.full((B, H, W, C), float("nan"), device=dev, dtype=torch.bfloat16)
+        ops.maxpool_bwd(xd, dyd, dx, P, relu)
+        assert torch.equal(dx.double(), edx), f"backward, relu_fused={relu}"
+
+
+@pytest.mark.parametrize("N", [8, 24])
+def test_unpool2_exact(N):
+    """Every pooled gradient at the window position its code names, nothing for code 4, zero elsewhere (dy is
+    pre-filled with NaN), with the reference's codes of a tied integer map."""
+    B, OH, OW = 3, 6, 10
+    g = xu.gen(N)
+    y, dyp = xu.ints(g, (B, OH, OW, N), -2, 2).to(dev), xu.ints(g, (B, OH // 2, OW // 2, N), -3, 3)
+    code = xu.code_relu4(*xu.window_argmax(xu.windows(y)))
+    assert all(bool((code == c).any()) for c in range(5))
+    dy = torch.full((B, OH, OW, N), float("nan"), device=dev, dtype=torch.bfloat16)
+    exp = xu.unpool_ref(dyp.to(dev), code, OH, OW, "relu4")
+    xu.assert_exact_output(exp)
+    ops.unpool2(xu.bf16(dyp, dev), code, dy)
+    assert torch.equal(dy.double(), exp)
 
 
 @pytest.mark.parametrize("B,C", [(4096, 10), (100, 5), (64, 100), (3, 1000)])

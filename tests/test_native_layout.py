@@ -307,3 +307,31 @@ def test_wgrad_plan_reads_the_diagnostic_switches():
     assert (q["family"], q["BN"], q["BM"]) == ("tr", 64, 32)
     q = _wgrad_plans_under("halo_groups=1", [call])[0]
     assert (q["family"], q["groups"], q["block"]) == ("halo", 1, 256)
+
+
+# ---------------------------------------------------------------------------- fused conv+pool dispatch keys
+@needs_ext
+def test_convpool_cases_cover_their_dispatch_keys():
+    """tests/golden/convpool_cases.json (scripts/convpool_cases.py), the shape list of the exact conv+pool tests:
+    every case is a supported geometry whose three dispatch keys, recomputed here from the layout queries, are the
+    recorded ones, and together the cases reach every key value the file's header lists as covered by the
+    enumerated space: forward (pair, channel tiles, k steps), weight gradient (channel tiles, k tiles with the
+    bias column), data gradient (pair | vec | scalar, k steps)."""
+    with open(os.path.join(os.path.dirname(GOLDEN), "convpool_cases.json")) as f:
+        j = json.load(f)
+    seen = {"fwd": set(), "wgrad": set(), "dgrad": set()}
+    for c in j["cases"]:
+        H, W, C, N, k, pad = (c[n] for n in ("H", "W", "C", "N", "k", "pad"))
+        assert ops.convpool_supported(H, W, C, k, k, pad, N), c
+        _, kpad2, pair = ops.convpool_fwd_layout(H, W, C, k, k, pad, N)
+        dpair, k2pad = ops.convpool_dgrad_layout(H, W, C, k, k, pad, N)
+        keys = {"fwd": (int(bool(pair)), -(-N // 16), kpad2 // 32), "wgrad": (-(-N // 16), -(-(k * k * C + 1) // 16)),
+                "dgrad": ("pair" if dpair else "vec" if N % 8 == 0 else "scalar", k2pad // 32)}
+        for kind, v in keys.items():
+            assert v == tuple(c[kind]), (c, kind, v)
+            seen[kind].add(v)
+    for kind, vals in j["covered"].items():
+        assert seen[kind] == {tuple(v) for v in vals}, kind
+    # both forward modes, both channel-tile counts everywhere, all three data-gradient kernels
+    assert {v[0] for v in seen["fwd"]} == {0, 1} and {v[1] for v in seen["fwd"]} == {1, 2}
+    assert {v[0] for v in seen["wgrad"]} == {1, 2} and {v[0] for v in seen["dgrad"]} == {"pair", "vec", "scalar"}
