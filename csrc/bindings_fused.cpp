@@ -335,7 +335,7 @@ void khead_wgrad_py(torch::Tensor pT, torch::Tensor h1T, torch::Tensor dz1T, tor
 // (a world > 1 P2PComm) it first sums every gradient over the ranks in-kernel (no all-reduce launch).
 void lenet_train_py(torch::Tensor x, c10::optional<torch::Tensor> idx, double scale, torch::Tensor labels,
                     std::vector<torch::Tensor> conv, std::vector<torch::Tensor> dense_w,
-                    std::vector<torch::Tensor> dense_wt, std::vector<torch::Tensor> dense_b,
+                    std::vector<torch::Tensor> dense_b,
                     std::vector<torch::Tensor> conv_grads, std::vector<torch::Tensor> dense_gw,
                     std::vector<torch::Tensor> dense_gb, std::vector<torch::Tensor> hT, std::vector<torch::Tensor> dzT,
                     torch::Tensor conv_part, torch::Tensor dense_part, torch::Tensor loss_part, torch::Tensor stats,
@@ -349,7 +349,7 @@ void lenet_train_py(torch::Tensor x, c10::optional<torch::Tensor> idx, double sc
                     const PSComm* ps, c10::optional<torch::Tensor> ps_perm, c10::optional<torch::Tensor> ps_idx,
                     double ps_lr, int64_t ps_max_stale, bool red_succ) {
   TORCH_CHECK(conv.size() == 4 && conv_grads.size() == 4, "lenet: conv = [w1, b1, w2, b2]");
-  TORCH_CHECK(dense_w.size() == 3 && dense_wt.size() == 3 && dense_b.size() == 3 && dense_gw.size() == 3 &&
+  TORCH_CHECK(dense_w.size() == 3 && dense_b.size() == 3 && dense_gw.size() == 3 &&
                   dense_gb.size() == 3 && hT.size() == 3 && dzT.size() == 3,
               "lenet: three dense layers");
   TORCH_CHECK(B > 0 && B < (1 << 30), "lenet: bad batch");
@@ -391,19 +391,16 @@ void lenet_train_py(torch::Tensor x, c10::optional<torch::Tensor> idx, double sc
   a.b1 = conv[1].data_ptr<float>();
   a.w2 = conv[2].data_ptr<float>();
   a.b2 = conv[3].data_ptr<float>();
-  const int64_t wsz[3][2] = {{128, 416}, {96, 128}, {16, 96}}, wtsz[3][2] = {{400, 128}, {128, 96}, {96, 32}};
   const int64_t NK[3][2] = {{120, 400}, {84, 120}, {10, 84}};
-  const dfa::bf16* dw[3];
-  const dfa::bf16* dwt[3];
+  const float* dw[3];
   const float* db[3];
   for (int l = 0; l < 3; ++l) {
-    need(dense_w[l], at::kBFloat16, "lenet dense w");
-    need(dense_wt[l], at::kBFloat16, "lenet dense wt");
+    // the fp32 master kernels [N][K]: the prep launch builds the dense fragments from them (the train
+    // kernel itself reads the fragment buffer only)
+    need(dense_w[l], at::kFloat, "lenet dense w");
     need(dense_b[l], at::kFloat, "lenet dense b");
-    TORCH_CHECK(dense_w[l].dim() == 2 && dense_w[l].size(0) == wsz[l][0] && dense_w[l].size(1) == wsz[l][1],
-                "lenet: dense ", l, " weights must be [", wsz[l][0], "][", wsz[l][1], "]");
-    TORCH_CHECK(dense_wt[l].dim() == 2 && dense_wt[l].size(0) == wtsz[l][0] && dense_wt[l].size(1) == wtsz[l][1],
-                "lenet: dense ", l, " dgrad weights must be [", wtsz[l][0], "][", wtsz[l][1], "]");
+    TORCH_CHECK(dense_w[l].numel() == NK[l][0] * NK[l][1], "lenet: dense ", l, " kernel must be [", NK[l][0], "][",
+                NK[l][1], "]");
     TORCH_CHECK(dense_b[l].numel() == NK[l][0], "lenet: dense bias size");
     need(dense_gw[l], at::kFloat, "lenet dense gw");
     need(dense_gb[l], at::kFloat, "lenet dense gb");
@@ -411,14 +408,15 @@ void lenet_train_py(torch::Tensor x, c10::optional<torch::Tensor> idx, double sc
                 "lenet: dense grad size");
     need(hT[l], at::kBFloat16, "lenet hT");
     need(dzT[l], at::kBFloat16, "lenet dzT");
-    TORCH_CHECK(hT[l].dim() == 2 && hT[l].size(0) == NK[l][1] && hT[l].size(1) == lds, "lenet: hT shape");
-    TORCH_CHECK(dzT[l].dim() == 2 && dzT[l].size(0) == NK[l][0] && dzT[l].size(1) == lds, "lenet: dzT shape");
-    dw[l] = reinterpret_cast<const dfa::bf16*>(dense_w[l].data_ptr());
-    dwt[l] = reinterpret_cast<const dfa::bf16*>(dense_wt[l].data_ptr());
+    // block layout (csrc/lenet_frag.h lenet_act_pos): whole 16-row tiles, the padding rows zero
+    TORCH_CHECK(hT[l].dim() == 2 && hT[l].size(0) >= (NK[l][1] + 15) / 16 * 16 && hT[l].size(1) == lds,
+                "lenet: hT must be [>= round16(K)][ldt]");
+    TORCH_CHECK(dzT[l].dim() == 2 && dzT[l].size(0) >= (NK[l][0] + 15) / 16 * 16 && dzT[l].size(1) == lds,
+                "lenet: dzT must be [>= round16(N)][ldt]");
+    dw[l] = dense_w[l].data_ptr<float>();
     db[l] = dense_b[l].data_ptr<float>();
   }
-  a.d1w = dw[0]; a.d2w = dw[1]; a.d3w = dw[2];
-  a.d1wt = dwt[0]; a.d2wt = dwt[1]; a.d3wt = dwt[2];
+  a.d1m = dw[0]; a.d2m = dw[1]; a.d3m = dw[2];
   a.d1b = db[0]; a.d2b = db[1]; a.d3b = db[2];
   const int nblk = dfa::lenet_blocks((int)B);
   need(conv_part, at::kFloat, "lenet conv_part");
@@ -688,7 +686,7 @@ void bind_fused(py::module_& m) {
   m.def("kcnn_slab_floats", [](int64_t B) { return (int64_t)dfa::kcnn_slab_floats((int)B); });
   m.def("lenet_train", &lenet_train_py, "whole-network LeNet-5 training step (fwd + CE + bwd, 2 launches)",
         py::arg("x"), py::arg("idx"), py::arg("scale"), py::arg("labels"), py::arg("conv"), py::arg("dense_w"),
-        py::arg("dense_wt"), py::arg("dense_b"), py::arg("conv_grads"), py::arg("dense_gw"), py::arg("dense_gb"),
+        py::arg("dense_b"), py::arg("conv_grads"), py::arg("dense_gw"), py::arg("dense_gb"),
         py::arg("hT"), py::arg("dzT"), py::arg("conv_part"), py::arg("dense_part"), py::arg("loss_part"),
         py::arg("stats"), py::arg("frag"), py::arg("ftab"), py::arg("pxtab"), py::arg("B"), py::arg("grad_scale"),
         py::arg("prep") = true, py::arg("snap") = py::none(),
@@ -700,6 +698,21 @@ void bind_fused(py::module_& m) {
         py::arg("ps_lr") = 0.0, py::arg("ps_max_stale") = -1, py::arg("red_succ") = true);
   m.def("lenet_blocks", [](int64_t B) { return dfa::lenet_blocks((int)B); });
   m.def("lenet_frag_bytes", []() { return (int64_t)dfa::lenet_frag_bytes(); });
+  m.def("lenet_act_map", [](int64_t rows, int64_t ldt) {
+    TORCH_CHECK(rows > 0 && ldt > 0 && ldt % 32 == 0 && rows * ldt < (1LL << 31), "lenet_act_map: bad shape");
+    auto mp = torch::empty({rows, ldt}, torch::kLong);
+    dfa::lenet_act_map((int)rows, (int)ldt, reinterpret_cast<long long*>(mp.data_ptr()));
+    return mp;
+  }, "element index of (row, batch column) in a transposed LeNet activation buffer of ldt columns (block layout)");
+  m.def("lenet_dense_frag_map", [](int64_t l) {
+    TORCH_CHECK(l >= 0 && l < 3, "lenet_dense_frag_map: layer 0 .. 2");
+    int N = 0, K = 0;
+    dfa::lenet_dense_frag_map((int)l, &N, &K, nullptr, nullptr);
+    auto fwd = torch::empty({N, K}, torch::kLong), tr = torch::empty({K, N}, torch::kLong);
+    dfa::lenet_dense_frag_map((int)l, &N, &K, reinterpret_cast<long long*>(fwd.data_ptr()),
+                              reinterpret_cast<long long*>(tr.data_ptr()));
+    return std::make_tuple(fwd, tr);
+  }, "bf16 element index in the LeNet fragment buffer of every weight of dense layer l: (forward [N][K], transposed [K][N])");
   m.def("lenet_dense_part_floats", [](int64_t B) { return (int64_t)dfa::lenet_dense_part_floats((int)B); });
   m.def("lenet_red_err_offset", []() { return (int64_t)dfa::lenet_red_err_offset(); });
 }

@@ -815,7 +815,7 @@ void sgd_multi_py(torch::Tensor descs, int64_t ndesc, int64_t total_blocks, torc
                   c10::optional<torch::Tensor> idx_stream, c10::optional<torch::Tensor> idx_cursor,
                   c10::optional<torch::Tensor> idx_dst, c10::optional<torch::Tensor> descs_host,
                   c10::optional<torch::Tensor> lenet_frag, int64_t frag_w1, int64_t frag_w2,
-                  c10::optional<torch::Tensor> lenet_snap, c10::optional<torch::Tensor> step_stats,
+                  std::vector<int64_t> frag_dense, c10::optional<torch::Tensor> lenet_snap, c10::optional<torch::Tensor> step_stats,
                   c10::optional<torch::Tensor> run_stats, uintptr_t gate, uintptr_t mirror) {
   TORCH_CHECK(descs.is_cuda() && descs.scalar_type() == at::kLong && descs.is_contiguous(), "descs must be int64 GPU");
   const dfa::ParamDesc* hd = host_descs(descs_host, descs);
@@ -841,6 +841,19 @@ void sgd_multi_py(torch::Tensor descs, int64_t ndesc, int64_t total_blocks, torc
     is.frag = lenet_frag->data_ptr();
     is.frag_w1 = frag_w1;
     is.frag_w2 = frag_w2;
+    // the three dense kernels: their tile workgroups scatter every new value into the dense fragment
+    // ranges, whose shapes are LeNet-5's (csrc/lenet_frag.h), so the descriptors must be exactly those
+    TORCH_CHECK(frag_dense.size() == 3 && hd != nullptr,
+                "lenet_frag: the three dense kernel offsets and the host descriptor table are required");
+    const int64_t NK[3][2] = {{120, 400}, {84, 120}, {10, 84}};
+    for (int l = 0; l < 3; ++l) {
+      bool found = false;
+      for (int64_t k = 0; k < ndesc; ++k)
+        if (hd[k].off == frag_dense[l])
+          found = ((hd[k].pad_ >> 28) & 1) && hd[k].N == NK[l][0] && hd[k].T == 1 && hd[k].Ci == NK[l][1];
+      TORCH_CHECK(found, "lenet_frag: dense kernel ", l, " is not a tile-mode [", NK[l][0], "][", NK[l][1], "] matrix");
+      is.frag_d[l] = frag_dense[l];
+    }
   }
   // async PS exclusive writer (PSComm.excl_gate / excl_mirror): the update gated on the admission word, the
   // new weights mirrored into the rank's shard
@@ -982,7 +995,7 @@ void bind_layers(py::module_& m) {
         py::arg("grad"), py::arg("mom"), py::arg("wbf"), py::arg("hyper"), py::arg("apply_update"),
         py::arg("idx_stream") = py::none(), py::arg("idx_cursor") = py::none(), py::arg("idx_dst") = py::none(),
         py::arg("descs_host") = py::none(), py::arg("lenet_frag") = py::none(), py::arg("frag_w1") = 0,
-        py::arg("frag_w2") = 0, py::arg("lenet_snap") = py::none(), py::arg("step_stats") = py::none(),
+        py::arg("frag_w2") = 0, py::arg("frag_dense") = std::vector<int64_t>{}, py::arg("lenet_snap") = py::none(), py::arg("step_stats") = py::none(),
         py::arg("run_stats") = py::none(), py::arg("gate") = 0, py::arg("mirror") = 0);
   m.def("adam_multi", &adam_multi_py, py::arg("descs"), py::arg("ndesc"), py::arg("total_blocks"), py::arg("master"),
         py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("wbf"), py::arg("hyper"), py::arg("state"),

@@ -225,6 +225,7 @@ struct IndexStream {  // next-batch staging folded into the optimizer launch (cs
   // fused LeNet-5 conv-weight fragments rebuilt from the updated weights (csrc/lenet_frag.h); frag null = off
   void* frag;
   long long frag_w1, frag_w2;  // offsets of the conv1 / conv2 kernels in grad (and master / momentum)
+  long long frag_d[3];         // offsets of the three dense kernels: their tile workgroups write the dense fragments
   const float* snap;           // [2][2550] pre-update weights / momentum (lenet_reduce_kernel); read
                                // instead of master, which this same launch overwrites
   // device run statistics (callbacks / metrics without extra launches): the index-stream workgroup adds
@@ -508,8 +509,8 @@ hipError_t ps_selftest_add(const PSArgs& a, float* const* words, int n, float ra
 
 
 // Whole-network LeNet-5 training step (csrc/lenet_fused.hip): conv5x5x6 'same' + pool, conv5x5x16 +
-// pool, dense 400-120-84-10, softmax-CE, full backward.  Conv weights are read from the fp32 master,
-// dense weights from the bf16 compute copies ([Npad16][Kpad32] and the dgrad layout).
+// pool, dense 400-120-84-10, softmax-CE, full backward.  Every weight matrix is read as lane-linear
+// MFMA fragments (csrc/lenet_frag.h); the biases from the fp32 master.
 constexpr int kLeNetPW1 = 0, kLeNetPB1 = 150, kLeNetPW2 = 156, kLeNetPB2 = 2556, kLeNetConvParams = 2572;
 constexpr int kLeNetConvStride = 2576;  // floats per workgroup row of the conv partial buffer
 struct LeNetArgs {
@@ -520,15 +521,15 @@ struct LeNetArgs {
   float scale;                // uint8 -> value scale
   const int* labels;          // read through idx like the images
   const float *w1, *b1, *w2, *b2;  // fp32 master: conv1 [6][25], [6]; conv2 [16][150], [16]
-  const bf16 *d1w, *d1wt, *d2w, *d2wt, *d3w, *d3wt;  // [128][416] [400][128] [96][128] [128][96] [16][96] [96][32]
+  const float *d1m, *d2m, *d3m;  // fp32 master: dense kernels [120][400], [84][120], [10][84] (the prep launch)
   const float *d1b, *d2b, *d3b;
   float* conv_part;           // [nblocks][kLeNetConvStride] per-workgroup conv gradient partials
   float* loss_part;           // [nblocks][2]
-  bf16 *h0T, *h1T, *h2T;      // [400|120|84][ldt] transposed dense inputs
-  bf16 *dz1T, *dz2T, *dz3T;   // [120|84|10][ldt] transposed dense output gradients
+  bf16 *h0T, *h1T, *h2T;      // [400|128|96][ldt] transposed dense inputs, block layout (lenet_act_pos)
+  bf16 *dz1T, *dz2T, *dz3T;   // [128|96|16][ldt] transposed dense output gradients, block layout
   float* logits;              // [B][10] (nullable)
   int prep;                   // 1: launch the fragment prep kernel first (0: the optimizer rebuilt them)
-  const void* frag;           // [37][64] x 8 bf16 conv weight fragments of this step (written by the prep launch)
+  const void* frag;           // [298][64] x 8 bf16 conv + dense weight fragments of this step (csrc/lenet_frag.h)
   const unsigned char* ftab;  // [98][2][16] conv2 dgrad gather table (lenet_tables)
   const unsigned short* pxtab;  // [832] conv2 output row -> pool1 pixel (lenet_tables)
   unsigned long long* stamps; // diagnostic phase clocks [grid][16] (lenet_set_stamps), or null
@@ -554,7 +555,7 @@ struct LeNetDense {
 };
 // Fused update of the LeNet-5 step: the reduce kernel applies the SGD update to every parameter it
 // finalises (no optimizer launch), stages the next batch's indices and scatters every updated conv
-// weight into the next step's MFMA fragments (lenet_frag_scatter).
+// and dense weight into the next step's MFMA fragments (lenet_frag_scatter, lenet_dense_frag_scatter).
 struct LeNetSgd {
   float* master;
   float* mom;          // null without momentum
@@ -712,6 +713,12 @@ int lenet_blocks(int B);
 hipError_t lenet_train(const LeNetArgs& a, LeNetRedArgs r, hipStream_t st);
 void lenet_set_stamps(void* buf);
 size_t lenet_frag_bytes();
+// dense layer l (0 .. 2): its N, K and (fwd / tr non-null) the fragment-buffer element of every weight,
+// fwd [N][K] and tr [K][N]
+void lenet_dense_frag_map(int l, int* N, int* K, long long* fwd, long long* tr);
+// out[row * ldt + col] = element index of (row, col) in a transposed activation / gradient buffer of the
+// fused LeNet-5 step (H^T, dZ^T: blocks of 16 rows x 32 batch columns, csrc/lenet_frag.h lenet_act_pos)
+void lenet_act_map(int rows, int ldt, long long* out);
 
 // Classifier evaluation metrics (csrc/metrics.hip): out = [sum of the per-example loss, correct].
 enum MetricKind {

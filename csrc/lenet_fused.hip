@@ -6,8 +6,11 @@
 // 0.174 ms per 4096-image step, ~60 us of it fixed per-launch cost and the rest VALU-bound im2col.
 // LeNet-5 is small enough that a workgroup can keep EVERYTHING of its images on chip, so here:
 //
-//   lenet_prep_kernel    the conv weights of this step as ready-made MFMA B fragments (banded conv1,
-//                        conv2 forward, pair-banded conv2 data gradient): 37 x 1 KB.  A workgroup loads the
+//   lenet_prep_kernel    every weight matrix of this step as ready-made, lane-linear MFMA B fragments
+//                        (csrc/lenet_frag.h): the conv weights (banded conv1, conv2 forward, pair-banded
+//                        conv2 data gradient: 37 x 1 KB) and the six dense matrices (forward and
+//                        transposed: 261 x 1 KB), normally kept fresh by whoever updates the weights (the
+//                        reduce launch's fused update, the optimizer launch).  A workgroup loads the
 //                        22 conv1 / conv2 forward fragments once (16-byte pieces, at most 3 per thread, in
 //                        phase 0) into LDS scratch that later phases overwrite, and its 8 waves take them
 //                        from there with one ds_read_b128 per lane and fragment; the 15 data-gradient
@@ -20,13 +23,16 @@
 //                          output columns read a copy of the image shifted by one pixel), so the
 //                          4 accumulator rows of a lane are one 2x2 pool window: the pool is in-lane
 //     conv2 5x5 + bias + ReLU + pool                  implicit GEMM, output rows in pool-window order
-//     dense 400-120-84-10 + softmax-CE + backward     MFMA, weights streamed from L2
+//     dense 400-120-84-10 + softmax-CE + backward     MFMA, weight fragments streamed from L2 (one
+//                          lane-linear 1 KB load per fragment: 8 cache-line lookups, where a row-major
+//                          matrix cost one per 16-byte piece)
 //     conv2 weight gradient                           ds_read_b64_tr_b16 transposed reads of both
 //                          operands from their natural NHWC images; bias = a column of ones
 //     conv2 data gradient                             pair-banded MFMA (two output columns per row)
 //     conv1 weight gradient                           A fragments unpooled in registers from the pool
 //                          gradient + argmax codes, B = 4 dword reads of the (shifted) input image
-//   and writes per-workgroup conv gradient partials plus transposed dense activations/gradients;
+//   and writes per-workgroup conv gradient partials plus transposed dense activations/gradients (as
+//   blocks of 16 rows x 32 batch columns in the reduce launch's operand order: lenet_act_pos);
 //   lenet_reduce_kernel  deterministic reductions: conv partials (one wave per parameter over all
 //                        workgroups), dense weight gradients over the batch (MFMA, K = batch), loss.
 #include "common.h"
@@ -196,22 +202,39 @@ __device__ __forceinline__ void pool4(float a00, float a01, float a10, float a11
 }
 
 // Weight fragments of one dense GEMM for the tiles t = w + NW tt this wave owns, loaded ahead of use so
-// that the L2 latency of layer l + 1's weights hides behind layer l (W rows of 32 * KS elements).
+// that the L2 latency of layer l + 1's weights hides behind layer l.  W: the matrix's range of the
+// fragment buffer (csrc/lenet_frag.h), [tile][k-step][64 lanes]: one lane-linear 1 KB load per fragment
+// (8 cache lines a wave; the row-major copies cost a line per lane group: 64 lookups).
 template <int KS, int NTW>
 struct DenseFrags {
   bf16x8 b[NTW][KS];
 };
 template <int KS, int NTW>
-__device__ __forceinline__ void dense_load(DenseFrags<KS, NTW>& f, const bf16* __restrict__ W, int ntiles) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+__device__ __forceinline__ void dense_load(DenseFrags<KS, NTW>& f, const bf16x8* __restrict__ W, int ntiles) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int tt = 0; tt < NTW; ++tt) {
     const int t = w + NW * tt;
     if (t < ntiles) {
-      const bf16* wrow = W + (long long)(16 * t + i) * (32 * KS) + 8 * g;
 #pragma unroll
-      for (int s = 0; s < KS; ++s) f.b[tt][s] = ld8(wrow + 32 * s);
+      for (int s = 0; s < KS; ++s) f.b[tt][s] = W[(t * KS + s) * 64 + lane];
     }
+  }
+}
+
+// Row n of a transposed activation / gradient buffer (block layout: lenet_act_pos, csrc/lenet_frag.h),
+// batch columns c0 .. c0 + 3, the first nlive of them live.  All four live: c0 is a multiple of 4 (4 or 8
+// images per workgroup), the columns are one half of a 16-byte piece, one 8-byte store -- the 16 lanes
+// of a row tile then write 256 contiguous bytes.  Otherwise element by element.
+__device__ __forceinline__ void act_store4(bf16* __restrict__ T, int ldt, int n, int c0, int nlive, const float (&v)[4]) {
+  if (nlive >= 4) {
+    bf16x4 pk;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pk[r] = f2bf(v[r]);
+    *reinterpret_cast<bf16x4*>(T + lenet_act_pos(n, c0, ldt)) = pk;
+  } else {
+    for (int r = 0; r < 4; ++r)
+      if (r < nlive) T[lenet_act_pos(n, c0 + r, ldt)] = f2bf(v[r]);
   }
 }
 
@@ -243,18 +266,7 @@ __device__ __forceinline__ void dense_fwd(const DenseFrags<KS, NTW>& f, const bf
       if (out) out[row * ldo + n] = f2bf(v[r]);
       if (out32) out32[row * 16 + (n & 15)] = v[r];
     }
-    if (hT != nullptr && n < N) {
-      bf16* dst = hT + (long long)n * ldt + r0 + 4 * g;
-      if (4 * g + 4 <= rows) {
-        bf16x4 pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pk[r] = f2bf(v[r]);
-        *reinterpret_cast<bf16x4*>(dst) = pk;
-      } else {
-        for (int r = 0; r < 4; ++r)
-          if (4 * g + r < rows) dst[r] = f2bf(v[r]);
-      }
-    }
+    if (hT != nullptr && n < N) act_store4(hT, ldt, n, r0 + 4 * g, rows - 4 * g, v);
   }
 }
 
@@ -284,18 +296,7 @@ __device__ __forceinline__ void dense_bwd(const DenseFrags<KS, NTW>& f, const bf
       if (j >= K) v[r] = 0.f;
       out[row * ldo + j] = f2bf(v[r]);
     }
-    if (gT != nullptr && j < K) {
-      bf16* dst = gT + (long long)j * ldt + r0 + 4 * g;
-      if (4 * g + 4 <= rows) {
-        bf16x4 pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pk[r] = f2bf(v[r]);
-        *reinterpret_cast<bf16x4*>(dst) = pk;
-      } else {
-        for (int r = 0; r < 4; ++r)
-          if (4 * g + r < rows) dst[r] = f2bf(v[r]);
-      }
-    }
+    if (gT != nullptr && j < K) act_store4(gT, ldt, j, r0 + 4 * g, rows - 4 * g, v);
   }
 }
 
@@ -594,7 +595,7 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
 #pragma unroll
   for (int s = 0; s < 7; ++s) bw[s] = ld8(reinterpret_cast<const bf16*>(smem + OFF_FC2) + 8 * (s * 64 + lane));
   DenseFrags<13, ccdiv(8, NW)> f1;
-  dense_load(f1, a.d1w, 8);
+  dense_load(f1, frag + FR_D1W * 64, 8);
   {
     int toff[7];
 #pragma unroll
@@ -625,27 +626,28 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
 
   // ---------------------------------------------------------------- phase C: dense head, CE, backward
   // H0^T for the dense-1 weight gradient (before H0 is overwritten by its gradient)
+  // (8 live images: r0 is a multiple of 8, the row's 8 columns are one 16-byte piece, and 16 consecutive
+  // rows 256 contiguous bytes)
   for (int k = tid; k < 400; k += NT) {
-    bf16* dst = a.h0T + (long long)k * a.ldt + r0;
     if (rows == IMG) {
       bf16x8 v;
 #pragma unroll
       for (int r = 0; r < IMG; ++r) v[r] = H0[r * LD0 + k];
-      st8(dst, v);
+      st8(a.h0T + lenet_act_pos(k, r0, a.ldt), v);
     } else {
-      for (int r = 0; r < rows; ++r) dst[r] = H0[r * LD0 + k];
+      for (int r = 0; r < rows; ++r) a.h0T[lenet_act_pos(k, r0 + r, a.ldt)] = H0[r * LD0 + k];
     }
   }
   DenseFrags<4, ccdiv(6, NW)> f2;
   DenseFrags<3, 1> f3;
-  dense_load(f2, a.d2w, 6);
-  dense_load(f3, a.d3w, 1);
+  dense_load(f2, frag + FR_D2W * 64, 6);
+  dense_load(f3, frag + FR_D3W * 64, 1);
   dense_fwd(f1, H0, LD0, ZR, DB, 120, true, H1, LD1, nullptr, a.h1T, a.ldt, r0, rows);
   __syncthreads();
   DenseFrags<1, ccdiv(6, NW)> g3;
   DenseFrags<3, ccdiv(8, NW)> g2;
-  dense_load(g3, a.d3wt, 6);
-  dense_load(g2, a.d2wt, 8);
+  dense_load(g3, frag + FR_D3WT * 64, 6);
+  dense_load(g2, frag + FR_D2WT * 64, 8);
   dense_fwd(f2, H1, LD1, ZR, DB + 120, 84, true, H2, LD2, nullptr, a.h2T, a.ldt, r0, rows);
   __syncthreads();
   dense_fwd(f3, H2, LD2, ZR, DB + 204, 10, false, nullptr, 0, LG, nullptr, a.ldt, r0, rows);
@@ -669,7 +671,7 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
     if (live && c < 10) {
       const float gv = (e * (1.f / ssum) - (c == y ? 1.f : 0.f)) * a.grad_scale;
       Z3[r * LD3 + c] = f2bf(gv);
-      a.dz3T[(long long)c * a.ldt + r0 + r] = f2bf(gv);
+      a.dz3T[lenet_act_pos(c, r0 + r, a.ldt)] = f2bf(gv);
     }
     if (c == y) LG[r * 16 + 14] = live ? -(z - mx - __logf(ssum)) : 0.f;
     if (c == 15) LG[r * 16 + 15] = (live && am == y) ? 1.f : 0.f;
@@ -689,7 +691,7 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   // otherwise push the live fragments past the 128-register budget; the loads overlap dense-3 / dense-2
   // backward
   DenseFrags<4, ccdiv(25, NW)> g1;
-  dense_load(g1, a.d1wt, 25);
+  dense_load(g1, frag + FR_D1WT * 64, 25);
   __syncthreads();
   LN_STAMP(5);
   dense_bwd(g3, Z3, LD3, ZR, 84, H2, LD2, Z2, LD2, a.dz2T, a.ldt, r0, rows);
@@ -954,11 +956,22 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   if (stamps && tid < 11) stamps[blockIdx.x * 16 + tid] = STMP[tid];
 }
 
-// Conv weights of this step as MFMA B fragments: one block (csrc/lenet_frag.h).  Only launched when
-// the optimizer does not rebuild them (the fused step's SGD launch normally does, see optim.hip).
+// Conv and dense weights of this step as MFMA B fragments (csrc/lenet_frag.h), all from the fp32 master:
+// workgroup 0 the conv fragments, the others one dense fragment lane per thread (a gather of 8 weights,
+// padding written as zero).  Only launched when the optimizer does not rebuild them (the fused step's SGD
+// launch normally does, see optim.hip).
 constexpr int PT = 1024;
+constexpr int kPrepBlocks = 1 + ccdiv(kLeNetDenseFragLanes, PT);
 __global__ void __launch_bounds__(PT) lenet_prep_kernel(const float* __restrict__ w1g, const float* __restrict__ w2g,
-                                                        bf16x8* __restrict__ frag) {
+                                                        const float* __restrict__ d1g, const float* __restrict__ d2g,
+                                                        const float* __restrict__ d3g, bf16x8* __restrict__ frag) {
+  if (blockIdx.x > 0) {
+    const int dl = (blockIdx.x - 1) * PT + threadIdx.x;
+    if (dl < kLeNetDenseFragLanes)
+      frag[kLeNetFragLanes + dl] =
+          lenet_dense_frag_lane(dl, [&](int l, int j) { return (l == 0 ? d1g : (l == 1 ? d2g : d3g))[j]; });
+    return;
+  }
   __shared__ float w[kLeNetConvW];
   for (int e = threadIdx.x; e < 150; e += PT) w[e] = w1g[e];
   for (int e = threadIdx.x; e < 2400; e += PT) w[150 + e] = w2g[e];
@@ -1080,11 +1093,16 @@ __device__ __forceinline__ void dense_job(const LeNetRedArgs& a, const RedTables
   const bf16* arow[2];
   const bf16* brow[2];
   bool a_ok[2], b_ok[2], b_one[2];
+  // operands in the block layout (lenet_act_pos): row tile 2 tn + i (2 tk + i), k-step col0 / 32 + s, one
+  // lane-linear 1 KB load each.  A tile past the buffer's last one reads that one instead (all its lanes
+  // are dropped below); the padding rows of a partial tile are zero and dropped as well.
+  const int kb = a.ldt >> 5;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int n = kDU * tn + 16 * i + (lane & 15), k = kDU * tk + 16 * i + (lane & 15);
-    arow[i] = L.dzT + (long long)min(n, L.N - 1) * a.ldt + col0 + 8 * (lane >> 4);
-    brow[i] = L.hT + (long long)min(k, L.K - 1) * a.ldt + col0 + 8 * (lane >> 4);
+    const int ta = min(2 * tn + i, (L.N + 15) / 16 - 1), tb = min(2 * tk + i, (L.K + 15) / 16 - 1);
+    arow[i] = L.dzT + (((long long)ta * kb + (col0 >> 5)) * 64 + lane) * 8;
+    brow[i] = L.hT + (((long long)tb * kb + (col0 >> 5)) * 64 + lane) * 8;
     a_ok[i] = n < L.N;
     b_ok[i] = k < L.K;
     b_one[i] = k == L.K;
@@ -1110,8 +1128,8 @@ __device__ __forceinline__ void dense_job(const LeNetRedArgs& a, const RedTables
       const int ss = min(s + q, s1 - 1);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        av[i][q] = ld8(arow[i] + 32 * ss);
-        bv[i][q] = ld8(brow[i] + 32 * ss);
+        av[i][q] = ld8(arow[i] + 512 * ss);
+        bv[i][q] = ld8(brow[i] + 512 * ss);
       }
     }
 #pragma unroll
@@ -1187,6 +1205,7 @@ __device__ __forceinline__ void red_emit(const LeNetRedArgs& a, const RedTables&
     const bf16 wb = f2bf(w);
     a.sgd.wbf[d.bf_off + (long long)n * round_up(K, 32) + kk] = wb;
     a.sgd.wbf[d.bft_off + (long long)kk * round_up(d.N, 32) + n] = wb;
+    lenet_dense_frag_scatter(a.sgd.frag, (o.di - 4) >> 1, n, kk, wb);  // the next step's dense fragments
     return;
   }
   emit_copies(d, o.i, w, a.sgd.wbf);
@@ -2131,6 +2150,24 @@ void lenet_set_stamps(void* buf) { g_lenet_stamps_host = reinterpret_cast<unsign
 
 size_t lenet_frag_bytes() { return (size_t)NFRAG * 64 * 16; }
 
+// bf16 element index in the fragment buffer of every weight of dense layer l: fwd[n * K + k] its forward
+// position, tr[k * N + n] its transposed one (tests; csrc/lenet_frag.h is the definition)
+void lenet_act_map(int rows, int ldt, long long* out) {
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < ldt; ++c) out[(long long)r * ldt + c] = lenet_act_pos(r, c, ldt);
+}
+void lenet_dense_frag_map(int l, int* N, int* K, long long* fwd, long long* tr) {
+  const LeNetDenseFrag d = lenet_dense_frag(l);
+  *N = d.N;
+  *K = d.K;
+  if (fwd == nullptr || tr == nullptr) return;
+  for (int n = 0; n < d.N; ++n)
+    for (int k = 0; k < d.K; ++k) {
+      fwd[n * d.K + k] = lenet_dense_frag_pos(d.fw, d.K, n, k);
+      tr[k * d.N + n] = lenet_dense_frag_pos(d.fwt, d.N, k, n);
+    }
+}
+
 // reduce scratch (the trainer's dense_part buffer, zero-initialised): job slabs + arrival tickets
 static int lenet_red_slots() {
   const int NK[3][2] = {{120, 400}, {84, 120}, {10, 84}};
@@ -2172,7 +2209,8 @@ hipError_t lenet_train(const LeNetArgs& a_in, LeNetRedArgs r, hipStream_t st) {
   a.ipw = lenet_ipw(a.B);
   const int nblk = (a.B + a.ipw - 1) / a.ipw;
   if (a.prep) {
-    hipLaunchKernelGGL(lenet_prep_kernel, dim3(1), dim3(PT), 0, st, a.w1, a.w2,
+    if (!a.w1 || !a.w2 || !a.d1m || !a.d2m || !a.d3m) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lenet_prep_kernel, dim3(kPrepBlocks), dim3(PT), 0, st, a.w1, a.w2, a.d1m, a.d2m, a.d3m,
                        reinterpret_cast<bf16x8*>(const_cast<void*>(a.frag)));
     DFA_HIP_CHECK(hipGetLastError());
   }
@@ -2215,6 +2253,9 @@ hipError_t lenet_train(const LeNetArgs& a_in, LeNetRedArgs r, hipStream_t st) {
       const ParamDesc& db = r.sgd.d[5 + 2 * l];
       if (!((dw.pad_ >> 28) & 1) || dw.T != 1 || dw.bf_off < 0 || dw.bft_off < 0 || db.bf_off >= 0)
         return hipErrorInvalidValue;
+      // red_emit scatters element (n, k) into the layer's fragment ranges: their shapes must be these
+      const LeNetDenseFrag df = lenet_dense_frag(l);
+      if (dw.N != df.N || dw.Ci != df.K || r.L[l].N != df.N || r.L[l].K != df.K) return hipErrorInvalidValue;
     }
   const int nslot = r.dense_tiles + r.nconv_slots;
   const int njobs = nslot * kChunks;

@@ -24,15 +24,21 @@ __device__ __forceinline__ void sgd_multi_body(const DT& descs, int ndesc,
                                                float* __restrict__ master, const float* __restrict__ grad,
                                                float* __restrict__ mom_buf, bf16* __restrict__ wbf,
                                                const float* __restrict__ hyper, int apply_update, int bid,
-                                               float* __restrict__ mirror = nullptr) {
+                                               const IndexStream& is) {
+  float* __restrict__ mirror = is.mirror;
   const int di = find_desc(descs, ndesc, bid);
   const ParamDesc d = descs[di];
+  // fused LeNet-5: the tile workgroups of the three dense kernels also write the next step's dense
+  // fragments (csrc/lenet_frag.h) from the bf16 values they emit
+  int dl = -1;
+  if (is.frag != nullptr && ((d.pad_ >> 28) & 1))
+    dl = d.off == is.frag_d[0] ? 0 : (d.off == is.frag_d[1] ? 1 : (d.off == is.frag_d[2] ? 2 : -1));
   float lr = 0.f, mom = 0.f, wd = 0.f, gs = 1.f;
   bool nesterov = false;
   if (apply_update) {
     lr = hyper[0]; mom = hyper[1]; wd = hyper[2]; gs = hyper[3]; nesterov = hyper[4] != 0.f;
   }
-  multi_tensor_body(d, wbf, bid, [&](int i) -> float {
+  auto update = [&](int i) -> float {
     float w = master[d.off + i];
     if (apply_update) {
       float v = 0.f;
@@ -42,7 +48,11 @@ __device__ __forceinline__ void sgd_multi_body(const DT& descs, int ndesc,
       if (mirror != nullptr) mirror[d.off + i] = w;
     }
     return w;
-  });
+  };
+  if (dl >= 0)
+    multi_tensor_body(d, wbf, bid, update, [&](int n, int k, bf16 wb) { lenet_dense_frag_scatter(is.frag, dl, n, k, wb); });
+  else
+    multi_tensor_body(d, wbf, bid, update);
 }
 
 // Fused LeNet-5: the conv-weight MFMA fragments of the next step, kLeNetFragBlocks extra workgroups,
@@ -84,9 +94,9 @@ __global__ void __launch_bounds__(256) sgd_multi_stream_kernel(const ParamDesc* 
     if (is.gate != nullptr && (__hip_atomic_load(is.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 7u) != 1u)
       return;
     if (INL)
-      sgd_multi_body(tab.d, ndesc, master, grad, mom_buf, wbf, hyper, apply_update, blockIdx.x, is.mirror);
+      sgd_multi_body(tab.d, ndesc, master, grad, mom_buf, wbf, hyper, apply_update, blockIdx.x, is);
     else
-      sgd_multi_body(descs, ndesc, master, grad, mom_buf, wbf, hyper, apply_update, blockIdx.x, is.mirror);
+      sgd_multi_body(descs, ndesc, master, grad, mom_buf, wbf, hyper, apply_update, blockIdx.x, is);
     return;
   }
   int fb = blockIdx.x - total_blocks;

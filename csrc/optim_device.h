@@ -91,8 +91,14 @@ __device__ __forceinline__ int find_desc(const DT& d, int n, int bid) {
 // writes that value's bf16 compute copies.
 // The optimizers differ in ``update`` only; which workgroup owns which element and where the copies go
 // is decided here, once.
-template <typename U>
-__device__ __forceinline__ void multi_tensor_body(const ParamDesc& d, bf16* __restrict__ wbf, int bid, const U& update) {
+// ``tile_emit(n, k, wb)``: a further consumer of every new bf16 value of a tile-mode matrix (the fused
+// LeNet-5 step's dense fragments).
+struct NoTileEmit {
+  __device__ __forceinline__ void operator()(int, int, bf16) const {}
+};
+template <typename U, typename E = NoTileEmit>
+__device__ __forceinline__ void multi_tensor_body(const ParamDesc& d, bf16* __restrict__ wbf, int bid, const U& update,
+                                                  const E& tile_emit = E{}) {
   const int base = (bid - d.block_start) * SGD_ELEMS_PER_BLOCK;
   const int K = d.T * d.Ci;
   // d.pad_ bit 28: tile mode for a plain [N][K] matrix with a plain dgrad copy [Ci][T*N]: the workgroup
@@ -114,6 +120,7 @@ __device__ __forceinline__ void multi_tensor_body(const ParamDesc& d, bf16* __re
         const bf16 wb = f2bf(update(n * K + k));
         wbf[d.bf_off + (long long)n * Kp + k] = wb;
         tt[cc][r0 + 8 * rr] = wb;
+        tile_emit(n, k, wb);
       }
     }
     __syncthreads();

@@ -46,11 +46,13 @@ class Net:
             specs += l.specs()
         self.store = ParamStore(specs, self.device, compute_bf16=self.is_gpu, seed=seed)
         if self.lenet_fused:
-            # the optimizer launch rebuilds the fused step's conv-weight fragments (no prep launch per step)
+            # the optimizer launch rebuilds the fused step's weight fragments, conv and dense (no prep
+            # launch per step)
             c1, c2 = self.exec_layers[0], self.exec_layers[1]
             frag = torch.zeros(ops.lenet_frag_bytes(), dtype=torch.uint8, device=self.device)
             self.store.lenet_frag = (frag, self.store.offsets[f"{c1.name}/kernel"],
-                                     self.store.offsets[f"{c2.name}/kernel"])
+                                     self.store.offsets[f"{c2.name}/kernel"],
+                                     [self.store.offsets[f"{d.name}/kernel"] for d in self.exec_layers[2:5]])
             self.store.lenet_snap = torch.zeros(2 * 2550, dtype=torch.float32, device=self.device)
             self.store.refresh_compute()
         for l in self.exec_layers:
@@ -328,14 +330,17 @@ class Net:
         if self.head_start is not None:
             ldt = (B + 31) // 32 * 32  # transposed activation / gradient buffers, zero tail columns
             if self.lenet_fused:
-                # row stride 256 B past a multiple of 8 KB: the 16 rows of one MFMA operand load land on
-                # 16 different L2 channels instead of one (csrc/lenet_fused.hip dense_unit_value)
+                # (kept from the row-major layout, whose row stride it moved off a multiple of 8 KB; the
+                # reduce launch sums round32(B) columns whatever the stride)
                 ldt += 128
             head = self.exec_layers[self.head_start:]
             z = lambda *shape: torch.zeros(shape, dtype=self.dtype, device=self.device)  # noqa: E731
-            self.head_xT = z(head[0].in_features, ldt)
-            self.head_hT = [z(l.units, ldt) for l in head[:-1]] + [None]
-            self.head_dzT = [z(l.units, ldt) for l in head]
+            # the fused LeNet-5 pair keeps these as blocks of 16 rows x 32 columns (csrc/lenet_frag.h
+            # lenet_act_pos): whole row tiles, the padding rows stay zero
+            r16 = (lambda n: (n + 15) // 16 * 16) if self.lenet_fused else (lambda n: n)
+            self.head_xT = z(r16(head[0].in_features), ldt)
+            self.head_hT = [z(r16(l.units), ldt) for l in head[:-1]] + [None]
+            self.head_dzT = [z(r16(l.units), ldt) for l in head]
             self.head_loss_part = torch.zeros(2 * ((B + 15) // 16), dtype=torch.float32, device=self.device)
             if self.khead:  # split-K slabs, published dZ1 tiles, tickets / flags / launch tag (zeroed)
                 self.khead_ws = torch.zeros(ops.khead_ws_floats(B, head[0].in_features), dtype=torch.float32,
@@ -482,9 +487,8 @@ class Net:
         cgrads = [st.gradient(f"{c1.name}/kernel"), st.gradient(f"{c1.name}/bias"),
                   st.gradient(f"{c2.name}/kernel"), st.gradient(f"{c2.name}/bias")]
         dense = (d1, d2, d3)
-        ops.lenet_train(x, labels, conv, [st.weight(f"{d.name}/kernel") for d in dense],
-                        [st.weight_t(f"{d.name}/kernel") for d in dense], [st[f"{d.name}/bias"] for d in dense],
-                        cgrads, [st.grad_matrix(f"{d.name}/kernel") for d in dense],
+        ops.lenet_train(x, labels, conv, [st[f"{d.name}/kernel"] for d in dense],
+                        [st[f"{d.name}/bias"] for d in dense], cgrads, [st.grad_matrix(f"{d.name}/kernel") for d in dense],
                         [st.gradient(f"{d.name}/bias") for d in dense], [self.head_xT] + self.head_hT[:2],
                         self.head_dzT, self.lenet_conv_part, self.lenet_dense_part, self.lenet_loss_part, self.stats,
                         self._loss_scale(B), frag=st.lenet_frag[0] if st.lenet_frag is not None else None,

@@ -228,9 +228,10 @@ class ParamStore:
         if any(frozen):
             raise NotImplementedError("non-trainable matrix parameters are not supported yet")
 
-    # fused LeNet-5 (csrc/lenet_fused.hip): (frag buffer, conv1 kernel offset, conv2 kernel offset).  The
-    # optimizer launch rebuilds the conv-weight MFMA fragments of the next step from the pre-update
-    # snapshot ``lenet_snap`` the step's reduce kernel took.  ``lenet_state``: "fresh" = fragments match
+    # fused LeNet-5 (csrc/lenet_fused.hip): (frag buffer, conv1 kernel offset, conv2 kernel offset, the
+    # three dense kernel offsets).  The optimizer launch rebuilds the MFMA fragments of the next step: the
+    # conv ones from the pre-update snapshot ``lenet_snap`` the step's reduce kernel took, the dense ones in
+    # the workgroups that update the dense kernels.  ``lenet_state``: "fresh" = fragments match
     # the master; "snap" = also a snapshot of the current master / momentum exists (a fused step ran);
     # "stale" = the master changed without a rebuild (the next fused step launches its prep kernel).
     lenet_frag = None
@@ -243,9 +244,9 @@ class ParamStore:
         if update and self.lenet_state != "snap":
             self.lenet_state = "stale"  # gradient not from a fused step: no snapshot to rebuild from
             return {}
-        buf, o1, o2 = self.lenet_frag
+        buf, o1, o2, od = self.lenet_frag
         self.lenet_state = "fresh"
-        kw = {"lenet_frag": buf, "frag_w1": int(o1), "frag_w2": int(o2)}
+        kw = {"lenet_frag": buf, "frag_w1": int(o1), "frag_w2": int(o2), "frag_dense": [int(o) for o in od]}
         if update:
             kw["lenet_snap"] = self.lenet_snap
         return kw
@@ -254,7 +255,7 @@ class ParamStore:
         """Momentum views of the two conv kernels (for the fused step's snapshot); [] without momentum."""
         if self.momentum is None or self.lenet_frag is None:
             return []
-        _, o1, o2 = self.lenet_frag
+        _, o1, o2, _ = self.lenet_frag
         return [self.momentum[o1: o1 + 150], self.momentum[o2: o2 + 2400]]
 
     def refresh_compute(self):

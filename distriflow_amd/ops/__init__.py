@@ -896,7 +896,7 @@ def lenet_tables(device):
     image's 104-row block (outside the 10x10 map: swz(100) = 96, a zero padding row);
     ``pxtab`` [832] i16 — padded conv2 output row (image * 104 + window * 4 + position) -> pool1 pixel
     index (padding rows 100..103 of an image: its pixel 0, read against a zero gradient);
-    ``frag`` — scratch for the per-step conv weight fragments (written by the kernel's prep launch)."""
+    ``frag`` — scratch for the per-step conv and dense weight fragments (written by the kernel's prep launch)."""
     key = str(device)
     if key not in _LENET_TABLES:
         import numpy as np
@@ -933,11 +933,13 @@ def lenet_dense_part_floats(B: int) -> int:
     return int(_C().lenet_dense_part_floats(int(B)))
 
 
-def lenet_train(x, labels, conv, dense_w, dense_wt, dense_b, conv_grads, dense_gw, dense_gb, hT, dzT, conv_part,
+def lenet_train(x, labels, conv, dense_w, dense_b, conv_grads, dense_gw, dense_gb, hT, dzT, conv_part,
                 dense_part, loss_part, stats, grad_scale, frag=None, prep=True, snap=None, conv_mom=(), sgd=None):
     """Whole-network LeNet-5 training step on GPU (csrc/lenet_fused.hip, 2 launches): fills every
     gradient and ``stats`` = [loss sum, correct].  ``x``: bf16 batch [B,28,28,1] or a :class:`GatherRef`
-    over a uint8 dataset; ``labels``: int32 [B] or a :class:`LabelRef` through the same indices."""
+    over a uint8 dataset; ``labels``: int32 [B] or a :class:`LabelRef` through the same indices.
+    ``conv`` / ``dense_w`` / ``dense_b``: views of the fp32 master (the kernel reads every weight matrix
+    from the fragment buffer; the prep launch builds it from these)."""
     if isinstance(x, GatherRef):
         src, idx, scale = x.data, x.idx, x.scale
     else:
@@ -951,9 +953,10 @@ def lenet_train(x, labels, conv, dense_w, dense_wt, dense_b, conv_grads, dense_g
     B = x.shape[0]
     ftab, pxtab, scratch = lenet_tables(stats.device)
     # ``frag``: the fragment buffer the optimizer rebuilds (ParamStore.lenet_frag), refreshed by the prep
-    # launch only when ``prep``; None = prep into scratch.  ``snap`` [2][2550]: the reduce kernel stores the
-    # conv kernels' weights and momentum (``conv_mom``) there for the optimizer's rebuild.
-    _C().lenet_train(src, idx, float(scale), lab, list(conv), list(dense_w), list(dense_wt), list(dense_b),
+    # launch only when ``prep``; None = prep into scratch.  It holds the conv and the dense fragments.
+    # ``snap`` [2][2550]: the reduce kernel stores the conv kernels' weights and momentum (``conv_mom``)
+    # there for the optimizer's rebuild.
+    _C().lenet_train(src, idx, float(scale), lab, list(conv), list(dense_w), list(dense_b),
                      list(conv_grads), list(dense_gw), list(dense_gb), list(hT), list(dzT), conv_part, dense_part,
                      loss_part, stats, scratch if frag is None else frag, ftab, pxtab, int(B), float(grad_scale),
                      prep=bool(prep) or frag is None, snap=snap, conv_mom=list(conv_mom),
