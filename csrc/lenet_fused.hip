@@ -27,7 +27,8 @@
 //                          lane-linear 1 KB load per fragment: 8 cache-line lookups, where a row-major
 //                          matrix cost one per 16-byte piece)
 //     conv2 weight gradient                           ds_read_b64_tr_b16 transposed reads of both
-//                          operands from their natural NHWC images; bias = a column of ones
+//                          operands from their natural NHWC images; bias = a column of ones; the
+//                          waves split it as 2 K-halves x 4 column groups (one fp32 add through LDS)
 //     conv2 data gradient                             pair-banded MFMA (two output columns per row)
 //     conv1 weight gradient                           A fragments unpooled in registers from the pool
 //                          gradient + argmax codes, B = 4 dword reads of the (shifted) input image
@@ -45,6 +46,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 namespace dfa {
@@ -422,7 +424,7 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   // per-image loop trip counts (tiles of 16 / 32 rows over rows-of-image blocks of 56, 104, 98, 14)
   const int nA = TRIM ? 2 * ((7 * rows + 1) / 2) : 56;        // conv1: 3.5 M-tiles per image, 2 halves each
   const int nB = TRIM ? (13 * rows + 1) / 2 : NM / 16;        // conv2: 6.5 M-tiles per image
-  const int nE = TRIM ? ((13 * rows + 3) / 4 + 1) / 2 * 2 : NM / 32;  // conv2 wgrad: 3.25 steps, paired
+  const int nE = TRIM ? (13 * rows + 3) / 4 : NM / 32;        // conv2 wgrad: 3.25 K-steps of 32 rows per image
   const int nF = TRIM ? (49 * rows + 7) / 8 : 49;             // conv2 dgrad: 6.125 M-tiles per image
   const int nG = TRIM ? 14 * rows : IMG * 14;                 // conv1 wgrad: 14 pool-window rows per image
   const bf16x8* __restrict__ frag = reinterpret_cast<const bf16x8*>(a.frag);
@@ -668,10 +670,13 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
     const int am = __builtin_ctzll((hit >> (16 * (r & 3))) | 0x10000ull);
     const float e = c < 10 ? __expf(z - mx) : 0.f;
     const float ssum = row16_sum(e);
-    if (live && c < 10) {
-      const float gv = (e * (1.f / ssum) - (c == y ? 1.f : 0.f)) * a.grad_scale;
+    if (c < 10) {
+      // an image past the batch takes a zero gradient: its Z3 row still holds what build_shift1 left
+      // there (pixels of image 5, non-zero when 6 or 7 images are live), which would otherwise flow
+      // back through the dense layers into the conv gradients
+      const float gv = live ? (e * (1.f / ssum) - (c == y ? 1.f : 0.f)) * a.grad_scale : 0.f;
       Z3[r * LD3 + c] = f2bf(gv);
-      a.dz3T[lenet_act_pos(c, r0 + r, a.ldt)] = f2bf(gv);
+      if (live) a.dz3T[lenet_act_pos(c, r0 + r, a.ldt)] = f2bf(gv);
     }
     if (c == y) LG[r * 16 + 14] = live ? -(z - mx - __logf(ssum)) : 0.f;
     if (c == 15) LG[r * 16 + 15] = (live && am == y) ? 1.f : 0.f;
@@ -739,24 +744,27 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   LN_STAMP(7);
 
   // ---------------------------------------------------------------- phase E: conv2 weight gradient
-  // dW2[n][(tap, c)] = sum_m dC2[m][n] im2col(P1)[m][(tap, c)]: both operands by transposed reads;
-  // wave w owns the 16-column tiles T = w + NW k (taps 2T, 2T + 1); tap 25 is the bias column of ones.
+  // dW2[n][(tap, c)] = sum_m dC2[m][n] im2col(P1)[m][(tap, c)]: both operands by transposed reads.  The 8
+  // waves are 2 K-halves x 4 column groups: wave w runs the 32-row steps of half h = w >> 2 (steps
+  // [0, ceil(nE / 2)) and [ceil(nE / 2), nE): every row in exactly one half) over the 16-column tiles
+  // T = cg + 4 k < 13 of group cg = w & 3 (taps 2T, 2T + 1, tap 25 unused): 4 tiles in group 0, 3 in the
+  // others, no dummy tile.  A step's dC2 operand is read by 4 waves and each im2col tile by 2 (all 8
+  // waves read all of dC2, and 16 tile slots were run for 13 tiles, while every wave ran over the whole
+  // K); the two halves meet in one fp32 add through LDS at the end.
   bf16x8 bd[15];  // conv2 data-gradient fragments for phase F, in flight during this phase
 #pragma unroll
   for (int s = 0; s < 15; ++s) bd[s] = frag[(FR_DG + s) * 64 + lane];
   {
     const int q = (lane & 15) >> 2, p = lane & 3;
-    constexpr int KT = ccdiv(13, NW);  // column tiles per wave (13 tiles: taps 0..25, tap 25 unused)
-    int toff[KT];  // element offset of the lane's tap (taps >= 25: tap 0, its column is dropped)
+    const int h = w >> 2, cg = w & 3;
+    constexpr int KTM = ccdiv(13, NW / 2);  // column tiles of the widest group
+    static_assert(NW == 8 && KTM == 4, "phase E: 2 K-halves x 4 column groups of 4, 3, 3, 3 tiles");
+    const int nlo = (nE + 1) >> 1;
+    const int sb = h ? nlo : 0, se = h ? nE : nlo;  // this wave's steps
+    const int ntile = cg == 0 ? KTM : KTM - 1;
+    f32x4 acc[KTM];
 #pragma unroll
-    for (int k = 0; k < KT; ++k) {
-      const int tap = 2 * (w + NW * k) + (p >> 1);
-      toff[k] = tap < 25 ? ((tap / 5) * 14 + (tap - 5 * (tap / 5))) * 8 + 4 * (p & 1) : 4 * (p & 1);
-    }
-    const int ntile = (13 - w + NW - 1) / NW;
-    f32x4 acc[KT];
-#pragma unroll
-    for (int k = 0; k < KT; ++k) acc[k] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < KTM; ++k) acc[k] = {0.f, 0.f, 0.f, 0.f};
     // the GEMM's M runs over the padded rows (26 steps of 32; the zero rows add nothing).  Step s + 1's
     // dC2 rows and pixel indices are read during step s: the P1 reads of a step depend on its
     // pixel-index reads, a second LDS round trip that was exposed once per step.
@@ -766,60 +774,90 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
       const int b = 4 * s + g, sx = (b - 13 * ((b * 79) >> 10)) & 7;
       return cat8(tr_read(DC2 + (mA ^ sx) * 16 + 4 * p), tr_read(DC2 + ((mA + 4) ^ sx) * 16 + 4 * p));
     };
-    auto step = [&](const bf16x8& av, unsigned px0, unsigned px1) {
-      const bf16* pb0 = P1 + 8 * px0;
-      const bf16* pb1 = P1 + 8 * px1;
-      // every wave runs KT tiles (a wave with fewer real ones computes a tile it drops): all reads of the
-      // step are in flight before its first MFMA
-      bf16x4 t0[KT], t1[KT];
+    const unsigned short* pxl = PX + 8 * g + q;
+    // the step loop for a wave with KT tiles (one copy per tile count: a wave with 3 tiles issues 3
+    // tiles' reads and MFMAs)
+    auto run = [&](auto ktc) {
+      constexpr int KT = decltype(ktc)::value;
+      int toff[KT];  // element offset of the lane's tap (tap 25: tap 0, its column is dropped)
 #pragma unroll
       for (int k = 0; k < KT; ++k) {
-        t0[k] = tr_read(pb0 + toff[k]);
-        t1[k] = tr_read(pb1 + toff[k]);
+        const int tap = 2 * (cg + NW / 2 * k) + (p >> 1);
+        toff[k] = tap < 25 ? ((tap / 5) * 14 + (tap - 5 * (tap / 5))) * 8 + 4 * (p & 1) : 4 * (p & 1);
       }
+      auto step = [&](const bf16x8& av, unsigned px0, unsigned px1) {
+        const bf16* pb0 = P1 + 8 * px0;
+        const bf16* pb1 = P1 + 8 * px1;
+        // all reads of the step are in flight before its first MFMA
+        bf16x4 t0[KT], t1[KT];
 #pragma unroll
-      for (int k = 0; k < KT; ++k) acc[k] = mfma16x16x32(av, cat8(t0[k], t1[k]), acc[k]);
-    };
-    // two register sets, steps 2j (set a) and 2j + 1 (set b): each step's reads were issued one step
-    // earlier (no register rotation, which waited for the prefetched data)
-    static_assert(NM / 32 % 2 == 0, "phase E pairs its steps");
-    const unsigned short* pxl = PX + 8 * g + q;
-    bf16x8 ava = ldAv(0);
-    unsigned pxa0 = pxl[0], pxa1 = pxl[4];
+        for (int k = 0; k < KT; ++k) {
+          t0[k] = tr_read(pb0 + toff[k]);
+          t1[k] = tr_read(pb1 + toff[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < KT; ++k) acc[k] = mfma16x16x32(av, cat8(t0[k], t1[k]), acc[k]);
+      };
+      // two register sets, steps sb + 2j (set a) and sb + 2j + 1 (set b): each step's reads were issued
+      // one step earlier (no register rotation, which waited for the prefetched data).  A half with an
+      // odd count (13 of the 26 steps at 8 images) ends with one step from set a, which the last pair
+      // has prefetched.
+      bf16x8 ava = ldAv(sb);
+      unsigned pxa0 = pxl[32 * sb], pxa1 = pxl[32 * sb + 4];
+      int s = sb;
 #pragma unroll 1
-    for (int s = 0; s < nE; s += 2) {
-      // (scheduling barriers keep the prefetches where they are: the scheduler otherwise hoists every LDS
-      // read to the top of the loop body and waits for all of them there)
-      const bf16x8 avb = ldAv(s + 1);
-      const unsigned pxb0 = pxl[32 * (s + 1)], pxb1 = pxl[32 * (s + 1) + 4];
-      __builtin_amdgcn_sched_barrier(0);
-      step(ava, pxa0, pxa1);
-      __builtin_amdgcn_sched_barrier(0);
-      const int sn = s + 2 < nE ? s + 2 : s;  // the last pair re-reads its own rows (unused)
-      ava = ldAv(sn);
-      pxa0 = pxl[32 * sn];
-      pxa1 = pxl[32 * sn + 4];
-      __builtin_amdgcn_sched_barrier(0);
-      step(avb, pxb0, pxb1);
-      __builtin_amdgcn_sched_barrier(0);
+      for (; s + 1 < se; s += 2) {
+        // (scheduling barriers keep the prefetches where they are: the scheduler otherwise hoists every
+        // LDS read to the top of the loop body and waits for all of them there)
+        const bf16x8 avb = ldAv(s + 1);
+        const unsigned pxb0 = pxl[32 * (s + 1)], pxb1 = pxl[32 * (s + 1) + 4];
+        __builtin_amdgcn_sched_barrier(0);
+        step(ava, pxa0, pxa1);
+        __builtin_amdgcn_sched_barrier(0);
+        const int sn = s + 2 < se ? s + 2 : s;  // the last pair of an even count re-reads its own rows (unused)
+        ava = ldAv(sn);
+        pxa0 = pxl[32 * sn];
+        pxa1 = pxl[32 * sn + 4];
+        __builtin_amdgcn_sched_barrier(0);
+        step(avb, pxb0, pxb1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (s < se) step(ava, pxa0, pxa1);
+    };
+    if (cg == 0) run(std::integral_constant<int, KTM>{});
+    else run(std::integral_constant<int, KTM - 1>{});
+    // cross-half sum, lower + upper: P1 is dead from here until phase F writes dP1 into it, so the upper
+    // half's accumulators go through its first 13 KB (fp32, [tile][lane][4]: lane-linear 16-byte pieces)
+    static_assert(13 * 64 * 16 <= IMG * 196 * 16, "the upper half's 13 accumulator tiles fit in P1");
+    f32x4* ES = reinterpret_cast<f32x4*>(smem + OFF_P1);
+    __syncthreads();  // every wave has finished reading P1
+    if (h) {
+#pragma unroll
+      for (int k = 0; k < KTM; ++k)
+        if (k < ntile) ES[(cg + NW / 2 * k) * 64 + lane] = acc[k];
     }
+    __syncthreads();
     // D[row = output channel 4g + r][col i = (tap 2T + (i >> 3), channel i & 7)]; the bias gradient is
     // column (tap 0, channel 6), P1's ones
+    if (!h) {
 #pragma unroll
-    for (int k = 0; k < KT; ++k) {
-      if (k < ntile) {
-        const int T = w + NW * k;
-        const int tap = 2 * T + (i >> 3), c = i & 7;
+      for (int k = 0; k < KTM; ++k) {
+        if (k < ntile) {
+          const int T = cg + NW / 2 * k;
+          const f32x4 up = ES[T * 64 + lane];
+          const int tap = 2 * T + (i >> 3), c = i & 7;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int n = 4 * g + r;
-          if (tap < 25 && c < 6) part[(long long)(kLeNetPW2 + n * 150 + tap * 6 + c)] = acc[k][r];
-          else if (tap == 0 && c == 6) part[(long long)(kLeNetPB2 + n)] = acc[k][r];
+          for (int r = 0; r < 4; ++r) {
+            const int n = 4 * g + r;
+            const float v = acc[k][r] + up[r];
+            if (tap < 25 && c < 6) part[(long long)(kLeNetPW2 + n * 150 + tap * 6 + c)] = v;
+            else if (tap == 0 && c == 6) part[(long long)(kLeNetPB2 + n)] = v;
+          }
         }
       }
     }
   }
-  __syncthreads();  // phase E finished reading P1: it now receives dP1
+  __syncthreads();  // the cross-half sums are read: P1 now receives dP1
   LN_STAMP(8);
 
   // ---------------------------------------------------------------- phase F: conv2 data gradient

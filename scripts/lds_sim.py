@@ -6,6 +6,8 @@ workgroup's loop iterations and prices them with the gfx950 banking rules (MI355
 an instruction's lanes are serviced in fixed lane groups, one LDS cycle per group when conflict-free;
 each extra distinct dword address on a bank within a group costs one more cycle.  Prints, per phase,
 LDS-array cycles and the conflict share -- the same ratio as SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE.
+Phase E is replayed twice: as 8 waves x 26 steps over 16 tile slots (the kernel before the split) and as the
+2 K-halves x 4 column groups it runs now.
 Usage: python3 scripts/lds_sim.py
 """
 from collections import defaultdict
@@ -125,33 +127,57 @@ def phase_b(ph):
                 ph.add("b128", addr)
 
 
-def phase_e(ph, ph2=None):
-    """A (dC2) reads into ph, the im2col B (P1) reads into ph2 (default: ph too)."""
-    PX = pxtab()
-    KT = (13 + NW - 1) // NW
+def e_waves(split):
+    """Phase E's work per wave: (first step, end step, column tiles).  Parent: every wave runs all 26 steps
+    over KT = 2 tile slots T = w + 8 k (16 slots for 13 tiles: a slot past tile 12 reads tap 0 and is
+    dropped).  Split: 2 K-halves x 4 column groups, tiles T = cg + 4 k < 13, no dummy slot."""
+    nE = NM // 32
     for w in range(NW):
-        ntile = (13 - w + NW - 1) // NW
-        for s in range(NM // 32):
-            # A: two transposed reads of dC2
+        if split:
+            h, cg = w >> 2, w & 3
+            nlo = (nE + 1) >> 1
+            yield (nlo if h else 0), (nE if h else nlo), [T for T in range(cg, 13, NW // 2)]
+        else:
+            yield 0, nE, [w + NW * k for k in range((13 + NW - 1) // NW)]
+
+
+def phase_e(ph, ph2=None, ph3=None, split=True):
+    """A (dC2) reads into ph, the im2col B (P1) reads into ph2, the u16 pixel-index reads and (split) the
+    cross-half exchange through P1 into ph3 (default: ph for all)."""
+    PX = pxtab()
+    ph2 = ph2 if ph2 is not None else ph
+    ph3 = ph3 if ph3 is not None else ph
+    for w, (s0, s1, tiles) in enumerate(e_waves(split)):
+        for s in range(s0, s1):
+            # A: two transposed reads of dC2 (ldAv: the swizzle term comes from the 8-row block)
             for half in range(2):
                 addr = []
                 for lane, i, g in lanes():
                     q, p = (lane & 15) >> 2, lane & 3
                     mA = 32 * s + 8 * g + q + 4 * half
+                    b = 4 * s + g
+                    sx = (b - 13 * ((b * 79) >> 10)) & 7
                     img, t = divmod(mA, DC2_RS)
-                    addr.append(OFF_DC2 + 2 * ((img * DC2_RS + dc2_swz(t)) * 16 + 4 * p))
+                    assert (mA ^ sx) == img * DC2_RS + dc2_swz(t)
+                    addr.append(OFF_DC2 + 2 * ((mA ^ sx) * 16 + 4 * p))
                 ph.add("tr", addr)
-            for k in range(KT):  # every wave runs KT tiles (taps >= 25 read tap 0's pixel, dropped)
+            # the step's two pixel indices (PX + 8 g + q, + 4)
+            for half in range(2):
+                ph3.add("b16", [OFF_PX + 2 * (32 * s + 8 * g + ((lane & 15) >> 2) + 4 * half) for lane, i, g in lanes()])
+            for T in tiles:
                 for half in range(2):
                     addr = []
                     for lane, i, g in lanes():
                         q, p = (lane & 15) >> 2, lane & 3
                         mA = 32 * s + 8 * g + q + 4 * half
-                        tap = 2 * (w + NW * k) + (p >> 1)
+                        tap = 2 * T + (p >> 1)
                         tp = tap if tap < 25 else 0
                         toff = ((tp // 5) * 14 + tp % 5) * 8 + 4 * (p & 1)
                         addr.append(OFF_P1 + 2 * (int(PX[mA]) * 8 + toff))
-                    (ph2 if ph2 is not None else ph).add("tr", addr)
+                    ph2.add("tr", addr)
+        if split:  # upper half writes, lower half reads [tile][lane] 16-byte pieces at the start of P1
+            for T in tiles:
+                ph3.add("b128", [OFF_P1 + (T * 64 + lane) * 16 for lane in range(64)])
 
 
 def ftab():
@@ -189,51 +215,59 @@ def phase_f(ph):
 
 
 def phase_g(ph):
+    kxs1 = (OFF_XS1 - OFF_XS) // 2
     for w in range(NW):
         for rp in range(w, IMG * 14, NW):
             img, py = divmod(rp, 14)
-            # pool values: 4 b16 reads per lane
+            p0 = (img * 14 + py) * 14
+            # pool codes of the lane's 4 windows: two 8-byte reads
+            for h in range(2):
+                ph.add("b64", [OFF_C1 + 4 * (p0 + 4 * g + 2 * h) for lane, i, g in lanes()])
+            # pool gradients: 4 u16 reads per lane, every lane (rows (c, dy): i < 12; the rest re-read c = 5)
             for wd in range(4):
                 addr = []
                 for lane, i, g in lanes():
-                    ca = i if i < 6 else 5
-                    p0 = (img * 14 + py) * 14 + 4 * g
-                    ok = 4 * g + wd < 14 and i < 6
-                    addr.append(OFF_P1 + 2 * ((p0 + wd) * 8 + ca) if ok else None)
+                    ca = i if i < 6 else (i - 6 if i < 12 else 5)
+                    addr.append(OFF_P1 + 2 * ((p0 + 4 * g + wd) * 8 + ca))
                 ph.add("b16", addr)
-            for dy in range(2):
-                y = 2 * py + dy
-                for T in range(2):
-                    for h in range(2):  # two ds_read2_b32 (dwords 0, 1 and 2, 3) from a dword-aligned start
-                        addr = []
-                        for lane, i, g in lanes():
-                            tap = 16 * T + i
-                            if tap < 25:
-                                ky, kx = divmod(tap, 5)
-                                base = (OFF_XS1 if kx & 1 else OFF_XS) + 2 * (img * 1024 + y * 32 + ky * 32 + 8 * g)
-                                addr.append(base + 4 * (kx >> 1) + 8 * h)
-                            else:
-                                addr.append((KO if tap == 25 else KZ) + 8 * h)
-                        ph.add("b64", addr)
+            # B: extended tap e = 16 T + i (30 taps ky' 0 .. 5, kx 0 .. 4; 30 = ones, 31 = zeros): two
+            # ds_read2_b32 (dwords 0, 1 and 2, 3) from a dword-aligned start
+            rowb = OFF_XS + 2 * (img * 1024 + 2 * py * 32)
+            for T in range(2):
+                for h in range(2):
+                    addr = []
+                    for lane, i, g in lanes():
+                        e = 16 * T + i
+                        if e < 30:
+                            ky, kx = divmod(e, 5)
+                            addr.append(rowb + 2 * ((kxs1 if kx & 1 else 0) + ky * 32 + 8 * g + 2 * (kx >> 1)) + 8 * h)
+                        else:
+                            addr.append((KO if e == 30 else KZ) + 8 * h)
+                    ph.add("b64", addr)
 
 
 def main():
     tot = conf = 0
     for name, fn in [("A conv1 (A reads)", phase_a), ("B conv2 (A reads)", phase_b),
-                     ("E conv2 wgrad (tr reads)", phase_e), ("F conv2 dgrad (A reads)", phase_f),
+                     ("E conv2 wgrad, 8 x 26 steps", lambda *p: phase_e(*p, split=False)),
+                     ("E conv2 wgrad, 2 x 4 split", phase_e), ("F conv2 dgrad (A reads)", phase_f),
                      ("G conv1 wgrad", phase_g)]:
         ph = Phase(name)
-        if fn is phase_e:
-            ph_b = Phase("  of which im2col (P1) reads")
-            fn(ph, ph_b)
-            ph.cyc += ph_b.cyc
-            ph.ideal += ph_b.ideal
-            ph.n += ph_b.n
+        if name.startswith("E "):
+            ph_a, ph_b, ph_x = Phase("  dC2 (tr reads)"), Phase("  im2col P1 (tr reads)"), Phase("  indices, exchange")
+            fn(ph_a, ph_b, ph_x)
+            for q in (ph_a, ph_b, ph_x):
+                ph.cyc += q.cyc
+                ph.ideal += q.ideal
+                ph.n += q.n
         else:
             fn(ph)
         c, k = ph.report()
-        if fn is phase_e:
-            ph_b.report()
+        if name.startswith("E "):
+            for q in (ph_a, ph_b, ph_x):
+                q.report()
+        if "8 x 26" in name:  # the kernel as it was: shown for comparison, not part of the total
+            continue
         tot += c
         conf += k
     print(f"{'modelled total':<28} {'':13} LDS cycles {tot:7d}  conflict {conf:7d} ({100.0 * conf / tot:5.1f} %)")
