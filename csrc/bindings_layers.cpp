@@ -363,6 +363,55 @@ void sigmoid_ce_py(torch::Tensor logits, torch::Tensor labels, c10::optional<tor
             "sigmoid_ce");
 }
 
+// a [rows][C] matrix of leading dimension ld: a contiguous tensor, or a column slice [:, :C] of a wider
+// contiguous buffer (row stride ld); its rows must lie inside the tensor's storage
+static void need_rows(const torch::Tensor& t, at::ScalarType dt, const char* name, int64_t rows, int64_t C, int64_t ld) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
+  TORCH_CHECK(t.scalar_type() == dt, name, " has dtype ", t.scalar_type(), ", expected ", dt);
+  int64_t avail = t.numel();
+  if (!t.is_contiguous()) {
+    TORCH_CHECK(t.dim() == 2 && t.size(1) == C && t.stride(1) == 1 && t.stride(0) == ld, name,
+                " must be contiguous or a column slice [:, :C] with row stride ld");
+    avail = (int64_t)(t.storage().nbytes() / t.element_size()) - t.storage_offset();
+  }
+  TORCH_CHECK(rows >= 1 && avail >= (rows - 1) * ld + C, name, " too small");
+}
+
+void loss_grad_py(torch::Tensor logits, c10::optional<torch::Tensor> labels, c10::optional<torch::Tensor> targets,
+                  c10::optional<torch::Tensor> idx, c10::optional<torch::Tensor> dlogits,
+                  c10::optional<torch::Tensor> stats, int64_t B, int64_t C, int64_t ldl, int64_t ldt, int64_t ldg,
+                  int64_t kind, int64_t out_act, double grad_scale) {
+  const int64_t lim = 1ll << 31;
+  TORCH_CHECK(B > 0 && B < lim, "loss_grad: B must be in [1, 2^31)");
+  TORCH_CHECK(C > 0 && C < lim, "loss_grad: C must be in [1, 2^31)");
+  TORCH_CHECK(ldl >= C && ldl < lim, "loss_grad: ldl must be in [C, 2^31)");
+  TORCH_CHECK(ldt >= C && ldt < lim, "loss_grad: ldt must be in [C, 2^31)");
+  TORCH_CHECK(ldg >= C && ldg < lim, "loss_grad: ldg must be in [C, 2^31)");
+  TORCH_CHECK(kind >= 0 && kind <= dfa::kMetricCategoricalCE, "loss_grad: unknown loss kind ", kind);
+  TORCH_CHECK(out_act >= 0 && out_act <= 2, "loss_grad: out_act is 0 (linear), 1 (softmax) or 2 (sigmoid)");
+  TORCH_CHECK(has(labels) != has(targets), "loss_grad: exactly one of labels and targets");
+  need_rows(logits, at::kFloat, "logits", B, C, ldl);
+  const long long* ip = opt_ptr<const long long>(idx, at::kLong, "idx", B, "idx needs B entries");
+  int64_t nrows;  // rows of the label / target table: all of them through idx, the first B without
+  if (has(labels)) {
+    need(*labels, at::kInt, "labels");
+    nrows = labels->numel();
+  } else {
+    nrows = targets->dim() == 2 ? targets->size(0) : targets->numel() / ldt;
+    need_rows(*targets, at::kFloat, "targets", nrows, C, ldt);
+  }
+  TORCH_CHECK(nrows >= (ip ? 1 : B), "loss_grad: labels / targets need B rows");
+  dfa::bf16* dl = nullptr;
+  if (has(dlogits)) {
+    need_rows(*dlogits, at::kBFloat16, "dlogits", B, C, ldg);
+    dl = reinterpret_cast<dfa::bf16*>(dlogits->data_ptr());
+  }
+  float* sp = opt_ptr<float>(stats, at::kFloat, "stats", 2, "stats needs 2 floats");
+  check_hip(dfa::loss_grad(logits.data_ptr<float>(), cptr<int>(labels), cptr<float>(targets), ip, nrows, dl, sp, B, C,
+                           ldl, ldt, ldg, kind, out_act, (float)grad_scale, cur_stream()),
+            "loss_grad");
+}
+
 static dfa::Pool2DGeom pool_geom(const std::vector<int64_t>& g) {
   TORCH_CHECK(g.size() == 12, "pool2d: geom = [B, H, W, C, OH, OW, ph, pw, sh, sw, pt, pl]");
   dfa::Pool2DGeom p{};
@@ -977,6 +1026,8 @@ void bind_layers(py::module_& m) {
   m.def("act_fwd", &act_fwd_py, "standalone activation y = act(x) (csrc/act.hip)");
   m.def("act_bwd", &act_bwd_py, "dx = dy * act'(x) [* relu'(x)]");
   m.def("sigmoid_ce", &sigmoid_ce_py, "sigmoid cross-entropy on logits vs one-hot labels (+ dlogits)");
+  m.def("loss_grad", &loss_grad_py,
+        "any lossesMap loss on act(logits) vs int labels or dense targets, optionally through idx (+ dlogits, stats)");
   m.def("pool2d_fwd", &pool2d_fwd_py, "general 2-D max / average pooling, any window / stride / padding");
   m.def("pool2d_bwd", &pool2d_bwd_py, "backward of pool2d_fwd (input-centric, no atomics)");
   m.def("dwconv_fwd", &dwconv_fwd_py, "depthwise conv forward, fp32 kernel [KH][KW][C*M] (csrc/dwconv.hip)");

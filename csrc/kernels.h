@@ -727,6 +727,13 @@ enum MetricKind {
 };
 hipError_t classifier_metrics(const float* z, const int* labels, int B, int C, int kind, int softmax, float* out,
                               hipStream_t st);
+// Fused training loss of any MetricKind (csrc/loss.hip) on fp32 outputs z [B][ldl], out_act as above:
+// dlogits[b][c] = grad_scale * dL_b/dz_bc (bf16, ld ldg), stats += [sum_b L_b, correct]; both nullable.
+// Exactly one of labels (int, one-hot) / targets (fp32 [.][ldt]) is given, a table of nrows rows; row b reads
+// table row idx[b] (clamped) when idx is given, else row b.
+hipError_t loss_grad(const float* z, const int* labels, const float* targets, const long long* idx, long long nrows,
+                     bf16* dlogits, float* stats, int B, int C, int ldl, int ldt, int ldg, int kind, int out_act,
+                     float grad_scale, hipStream_t st);
 
 // Generic Keras layers (csrc/act.hip): standalone activations, sigmoid-CE loss, general pooling.
 enum ActKind {

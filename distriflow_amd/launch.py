@@ -74,6 +74,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--beta2", type=float, default=0.999)
     p.add_argument("--eps", type=float, default=1e-7)
     p.add_argument("--weight-decay", type=float, default=0.0, help="L2 for sgd / adam, decoupled for adamw")
+    p.add_argument("--loss", default=None, metavar="{NAME,model}",
+                   help="train this lossesMap entry (meanSquaredError, huberLoss, ...) against the one-hot labels "
+                        "instead of the cross-entropy of the model's output; model = the loss the model.json's "
+                        "training_config names")
     p.add_argument("--graph", default=None, choices=["full", "split", "none"])
     p.add_argument("--save-dir", default=None, help="checkpoint directory: weights and optimizer state per version")
     p.add_argument("--resume", action="store_true")
@@ -300,6 +304,27 @@ def sync_optimizer(args, net) -> dict:
     return kw
 
 
+def sync_loss(args) -> str | None:
+    """Net's ``loss=`` from ``sync --loss``: a lossesMap name, or ``model`` = the loss of the model's Keras
+    ``training_config`` (models/keras.py loss_from_keras).  None without the flag: the default path."""
+    loss = getattr(args, "loss", None)
+    if loss == "model":
+        from .models.keras import loss_from_keras
+        from .models.zoo import keras_cnn_topology
+
+        topo = keras_cnn_topology() if args.model == "keras_cnn" else None
+        loss = loss_from_keras(topo) if topo else None
+        if loss is None:
+            raise SystemExit(f"--loss model: model {args.model!r} carries no Keras training_config")
+    if loss is not None:
+        from .losses import LOSSES
+        from .ops import METRIC_KINDS
+
+        if loss not in LOSSES or loss not in METRIC_KINDS:
+            raise SystemExit(f"--loss {loss}: not a trainable lossesMap entry; choose from {sorted(METRIC_KINDS)}")
+    return loss
+
+
 def save_sync_checkpoint(store, net, epoch: int, step: int) -> str:
     """One checkpoint version of a ``sync`` job: the weights (tf.js LayersModel), the optimizer state beside
     them (checkpoint/optim_state.py) and the resume record naming the optimizer and its hyper-parameters."""
@@ -356,7 +381,9 @@ def run_sync(args) -> dict:
     rank, world, dev = env.rank, env.world_size, env.device
     log = _logger(args, f"Distributed Worker {rank}")
     faults = Faults(args, rank)
-    net = build_model(args.model, device=dev, seed=args.seed)
+    net = build_model(args.model, device=dev, seed=args.seed, loss=sync_loss(args))
+    if net.loss is not None:
+        log.log(f"training loss {net.loss} on the {net.final_act} output")
     x, y = _load_data(args, dev)
     n = x.shape[0]
     B = args.batch

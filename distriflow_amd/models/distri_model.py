@@ -34,7 +34,7 @@ from .. import ops
 from ..checkpoint import VersionedStore, load_flat, load_layers_model_weights, save_flat, save_layers_model
 from ..config import compile_args
 from ..losses import accuracy, get_loss
-from .net import Net
+from .net import _CE_LOSSES, Net, normalise_loss
 from .params import OPTIMIZERS
 
 
@@ -171,19 +171,21 @@ class DistriModel(ABC):
 ModelSource = Union[Net, str, Callable[[], Net]]
 
 
-def fetch_model(src: ModelSource, device=None) -> Net:
+def fetch_model(src: ModelSource, device=None, loss: Optional[str] = None) -> Net:
     """Reference ``fetchModel`` (utils.ts:236-244): a Net, a callable returning one, a zoo name, or a
-    tf.js model.json path (topology + weights)."""
+    tf.js model.json path (topology + weights).  ``loss``: the lossesMap name the Net is to train (Net's
+    ``loss=``); a Net passed in, or returned by a callable, must already carry it."""
     from .zoo import MODELS, build_model
 
-    if isinstance(src, Net):
-        return src
-    if callable(src):
-        return src()
+    if isinstance(src, Net) or callable(src):
+        net = src if isinstance(src, Net) else src()
+        if loss is not None and net.loss != normalise_loss(loss, net.final_act):
+            raise ValueError(f"the Net trains loss={net.loss!r}; build it with loss={loss!r}")
+        return net
     if isinstance(src, str):
         dev = device or ("cuda" if torch.cuda.is_available() else "cpu")
         if src in MODELS:
-            return build_model(src, device=dev)
+            return build_model(src, device=dev, loss=loss)
         path = src[len("file://"):] if src.startswith("file://") else src
         if os.path.isdir(path):
             path = os.path.join(path, "model.json")
@@ -193,7 +195,7 @@ def fetch_model(src: ModelSource, device=None) -> Net:
 
             topo = load_topology(path)
             layers, shape = layers_from_keras(topo)
-            net = Net(layers, shape, device=dev, name=os.path.basename(os.path.dirname(path)) or "model")
+            net = Net(layers, shape, device=dev, name=os.path.basename(os.path.dirname(path)) or "model", loss=loss)
             net.topology = topo
             try:
                 load_layers_model_weights(net, path, strict=True)
@@ -204,7 +206,6 @@ def fetch_model(src: ModelSource, device=None) -> Net:
     raise TypeError(f"cannot fetch a model from {type(src).__name__}")
 
 
-_CE_LOSSES = {"softmaxCrossEntropy", "categorical_crossentropy", "categoricalCrossentropy"}
 _WARNED_LOSSES: set = set()
 
 
@@ -212,7 +213,10 @@ class EngineModel(DistriModel):
     """The MI355X engine behind the DistriModel contract (reference DistributedTfModel)."""
 
     def __init__(self, model: ModelSource, compile_config: Optional[dict] = None, device=None,
-                 strict_loss: bool = False, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-7):
+                 strict_loss: bool = False, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-7,
+                 train_compile_loss: bool = False):
+        """``train_compile_loss``: minimise the compile loss itself (any lossesMap entry, csrc/loss.hip)
+        instead of the cross-entropy of the model's output; a 2-D floating ``y`` is then a dense target."""
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         self._src = model
@@ -228,6 +232,9 @@ class EngineModel(DistriModel):
         self.betas = (float(betas[0]), float(betas[1]))
         self.eps = float(eps)
         self._strict_loss = strict_loss
+        self.train_compile_loss = bool(train_compile_loss)
+        if self.train_compile_loss and self.net is not None:
+            fetch_model(self.net, loss=self.compile["loss"])  # the Net must already train that loss
         # checked now when the output is known (or cannot matter); a sigmoidCrossEntropy compile loss on a
         # not-yet-fetched model is checked once fetch_initial() knows whether the model ends in sigmoid
         if self.net is not None or self.compile["loss"] != "sigmoidCrossEntropy":
@@ -238,6 +245,8 @@ class EngineModel(DistriModel):
         compile loss (default meanSquaredError) only feeds evaluate().  The engine trains the cross-entropy
         that matches the model's output (softmax CE, or sigmoid CE for a model ending in sigmoid) and says
         so once when the compile loss differs, instead of silently training another loss."""
+        if self.train_compile_loss:
+            return  # the compile loss is the one minimised
         loss = self.compile["loss"]
         trained = "sigmoidCrossEntropy" if getattr(self.net, "final_act", "") == "sigmoid" else "softmax cross-entropy"
         ok = loss == "sigmoidCrossEntropy" if trained == "sigmoidCrossEntropy" else loss in _CE_LOSSES
@@ -253,7 +262,8 @@ class EngineModel(DistriModel):
 
     def fetch_initial(self):
         if self.net is None:
-            self.net = fetch_model(self._src, self._device)
+            self.net = fetch_model(self._src, self._device,
+                                   loss=self.compile["loss"] if self.train_compile_loss else None)
             if self.compile["loss"] == "sigmoidCrossEntropy":
                 self._check_loss()
         self._sync_hyper()
@@ -286,6 +296,8 @@ class EngineModel(DistriModel):
                 xx = xx.unsqueeze(0)
             xx = xx.reshape((xx.shape[0],) + tuple(net.input_shape))
         y = y.to(net.device)
+        if self.train_compile_loss and net.loss is not None and y.dim() == 2 and y.is_floating_point():
+            return xx, y.to(torch.float32)  # dense targets of the compile loss, as they stand
         if y.dim() > 1:  # one-hot labels (reference convention) -> class indices
             y = y.argmax(dim=1)
         return xx, y.to(torch.int32)
@@ -333,13 +345,16 @@ class EngineModel(DistriModel):
             z = net._forward_eval(xx.to(net.dtype) if not isinstance(xx, ops.GatherRef) else xx)
             if not hasattr(self, "_metric_buf") or self._metric_buf.device != z.device:
                 self._metric_buf = torch.zeros(2, dtype=torch.float32, device=z.device)
-            st = ops.classifier_metrics(z, yy, loss, net.final_act, self._metric_buf).tolist()
+            if yy.is_floating_point():  # dense targets (train_compile_loss): the training loss kernel, stats only
+                st = ops.loss_grad(z, yy, loss, net.final_act, None, self._metric_buf.zero_()).tolist()
+            else:
+                st = ops.classifier_metrics(z, yy, loss, net.final_act, self._metric_buf).tolist()
             out = [st[0] / max(n, 1)]
             if "accuracy" in self.compile["metrics"] or "acc" in self.compile["metrics"]:
                 out.append(st[1] / max(n, 1))
             return out
         probs = net.predict(xx)
-        labels = torch.nn.functional.one_hot(yy.long(), net.num_classes).float()
+        labels = yy if yy.is_floating_point() else torch.nn.functional.one_hot(yy.long(), net.num_classes).float()
         out = [float(self.loss_fn(labels, probs).mean())]
         if "accuracy" in self.compile["metrics"] or "acc" in self.compile["metrics"]:
             out.append(float(accuracy(yy, probs).mean()))

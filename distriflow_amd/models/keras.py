@@ -255,6 +255,29 @@ def optimizer_from_keras(topology: dict) -> dict | None:
     return {"name": "sgd", "lr": float(lr), "betas": None, "eps": None, "momentum": float(cfg.get("momentum", 0.0))}
 
 
+_KERAS_LOSSES = {"mean_squared_error": "meanSquaredError", "mse": "meanSquaredError",
+                 "mean_absolute_error": "absoluteDifference", "mae": "absoluteDifference",
+                 "hinge": "hingeLoss", "huber": "huberLoss", "huber_loss": "huberLoss",
+                 "binary_crossentropy": "logLoss", "categorical_crossentropy": "categorical_crossentropy"}
+
+
+def loss_from_keras(topology: dict) -> str | None:
+    """The ``lossesMap`` name of the loss a Keras / tf.js ``modelTopology`` was compiled with, from
+    ``training_config.loss``, or None when the topology names none.  ``binary_crossentropy`` maps to
+    ``logLoss`` and ``categorical_crossentropy`` to itself: Keras clips the probabilities to
+    [eps, 1 - eps] where the tf.js losses add eps inside the logarithm, so the two differ by O(1e-7).
+    Any other loss name, and a per-output dict or list of losses, raises instead of training something else."""
+    tc = (topology or {}).get("training_config") or {}
+    loss = tc.get("loss")
+    if loss is None:
+        return None
+    if isinstance(loss, (dict, list, tuple)):
+        raise NotImplementedError(f"per-output losses {loss!r} (one loss name is supported)")
+    if loss not in _KERAS_LOSSES:
+        raise NotImplementedError(f"Keras loss {loss!r} (supported: {sorted(_KERAS_LOSSES)})")
+    return _KERAS_LOSSES[loss]
+
+
 def keras_config_from_layers(layers: list[Layer], input_shape: tuple, name: str = "sequential") -> dict:
     """Inverse of :func:`layers_from_keras` (Keras 2.x Sequential JSON, as tf.js writes it)."""
     out = []

@@ -29,11 +29,37 @@ class Workspace:
     bn: torch.Tensor      # fp32 BN partial sums
 
 
+# the lossesMap names of the cross-entropy a linear / softmax output trains by default
+_CE_LOSSES = {"softmaxCrossEntropy", "categorical_crossentropy", "categoricalCrossentropy"}
+
+
+def normalise_loss(loss: Optional[str], final_act: str) -> Optional[str]:
+    """The training loss a Net keeps for a requested ``lossesMap`` name: None when (loss, output activation)
+    names what the default path already trains -- a cross-entropy of ``_CE_LOSSES`` on a linear or softmax
+    output, sigmoidCrossEntropy on a sigmoid output -- so the fused plans are kept; else the name (the general
+    loss path, csrc/loss.hip).  An unknown name raises KeyError, as ``losses.get_loss`` does."""
+    if loss is None:
+        return None
+    from ..losses import get_loss
+
+    get_loss(loss)
+    if loss not in ops.METRIC_KINDS:
+        raise KeyError(f"loss {loss!r} is not trainable by the engine; available: {sorted(ops.METRIC_KINDS)}")
+    if loss in _CE_LOSSES and final_act in ("linear", "softmax"):
+        return None
+    if loss == "sigmoidCrossEntropy" and final_act == "sigmoid":
+        return None
+    return loss
+
+
 class Net:
     def __init__(self, layers: list[Layer], input_shape: tuple, num_classes: Optional[int] = None,
                  device="cuda", name: str = "model", seed: int = 0, compute_dtype: Optional[torch.dtype] = None,
-                 fuse: bool = True):
+                 fuse: bool = True, loss: Optional[str] = None):
         self.name = name
+        # the requested lossesMap training loss; _plan() normalises it once the output activation is known
+        # (None: the cross-entropy of the model's output, every fused plan available)
+        self.loss = loss
         self.device = torch.device(device)
         self.input_shape = tuple(input_shape)
         self.layers_all = list(layers)
@@ -165,6 +191,7 @@ class Net:
                 l.dx_bn_sinks = [prev]
         self.exec_layers = execd
         self.output_shape = shape
+        self.loss = normalise_loss(self.loss, self.final_act)
         self.head_start = self._plan_head(execd) if self.fuse else None
         self.khead = self._plan_khead(execd) if self.fuse else False
         if self.khead:
@@ -177,7 +204,7 @@ class Net:
         two launches (csrc/lenet_fused.hip).  ``DISTRIFLOW_DIAG=lenet_fused=0`` keeps the per-layer kernels."""
         import os
 
-        if not self.is_gpu or not diag_on("lenet_fused") or not ops.lenet_supported():
+        if not self.is_gpu or not diag_on("lenet_fused") or not ops.lenet_supported() or self.loss is not None:
             return False
         if self.final_act == "sigmoid":  # the fused kernel trains softmax cross-entropy
             return False
@@ -199,7 +226,7 @@ class Net:
         """Index of the first layer of the trailing Dense chain trained by the fused head kernels
         (csrc/mlphead.hip), or None.  Conditions: <= 4 Dense layers, ReLU on all but the logits layer,
         <= 16 classes, hidden widths <= 256, input width a multiple of 8 and <= 1024."""
-        if not self.is_gpu or not ops.head_supported() or self.final_act == "sigmoid":
+        if not self.is_gpu or not ops.head_supported() or self.final_act == "sigmoid" or self.loss is not None:
             return None
         j0 = len(execd)
         while j0 > 0 and isinstance(execd[j0 - 1], Dense) and len(execd) - j0 < 4:
@@ -223,7 +250,8 @@ class Net:
         head's forward, loss and both data gradients then run as ONE split-K launch (csrc/khead.hip) and
         its weight gradients as the fused head weight-gradient launch.  ``DISTRIFLOW_DIAG=khead_fused=0``
         keeps the per-layer path."""
-        if not self.is_gpu or not diag_on("khead_fused") or self.final_act == "sigmoid" or len(execd) < 3:
+        if (not self.is_gpu or not diag_on("khead_fused") or self.final_act == "sigmoid" or len(execd) < 3
+                or self.loss is not None):
             return False
         d1, d2 = execd[-2], execd[-1]
         if not (isinstance(d1, Dense) and isinstance(d2, Dense)):
@@ -405,19 +433,38 @@ class Net:
 
     def loss_and_grad(self, logits, labels, grad_scale: Optional[float] = None):
         """The training loss on the logits: softmax cross-entropy (a final softmax or linear output) or,
-        for a model that ends in sigmoid, sigmoid cross-entropy against the one-hot labels."""
+        for a model that ends in sigmoid, sigmoid cross-entropy against the one-hot labels.  A Net built
+        with ``loss=`` (the general loss path) trains that lossesMap entry on its output instead, against int
+        labels, dense fp32 targets [B, C], or an :class:`ops.LabelRef` / :class:`ops.TargetRef` read through
+        its index vector."""
         B = logits.shape[0]
         self.stats.zero_()
         gs = self._loss_scale(B) if grad_scale is None else grad_scale
-        if self.final_act == "sigmoid":
+        if self.loss is not None:
+            target, idx = self._loss_target(labels)
+            ops.loss_grad(logits, target, self.loss, self.final_act, self.dlogits, self.stats, gs, idx=idx)
+        elif self.final_act == "sigmoid":
             ops.sigmoid_ce(logits, labels, self.dlogits, self.stats, gs)
         else:
             ops.softmax_ce(logits, labels, self.dlogits, self.stats, gs)
         return self.stats
 
+    def _loss_target(self, labels):
+        """(target, idx) of ops.loss_grad from what a general-loss step was given."""
+        if isinstance(labels, ops.TargetRef):
+            return labels.targets, labels.idx
+        if isinstance(labels, ops.LabelRef):
+            return labels.labels, labels.idx
+        if labels.is_floating_point():
+            if labels.dim() != 2 or labels.shape[1] != self.num_classes:
+                raise ValueError(f"dense targets must be [B, {self.num_classes}], got {tuple(labels.shape)}")
+            return (labels if labels.dtype == torch.float32 else labels.float()), None
+        return (labels if labels.dtype == torch.int32 else labels.to(torch.int32)), None
+
     def compute_gradients(self, x, labels, grad_ready=None):
-        """fwd + fused softmax-CE + bwd; returns the device stats tensor [loss_sum, correct].
-        ``labels``: int tensor [B], or an :class:`ops.LabelRef` (dataset labels + batch indices)."""
+        """fwd + fused loss + bwd; returns the device stats tensor [loss_sum, correct].
+        ``labels``: int tensor [B], or an :class:`ops.LabelRef` (dataset labels + batch indices); on the
+        general loss path also dense fp32 targets [B, C] or an :class:`ops.TargetRef`."""
         if not isinstance(x, ops.GatherRef) and x.dtype != self.dtype:
             x = x.to(self.dtype)
         if self.has_dropout and isinstance(self.exec_layers[0], KerasConvBlock):
@@ -437,10 +484,14 @@ class Net:
             return self._compute_gradients_lenet(x, labels, grad_ready)
         if self.head_start is not None:
             return self._compute_gradients_head(x, labels, grad_ready)
-        if isinstance(labels, ops.LabelRef):
-            labels = labels.materialise(self.y_buf)
-        if labels.dtype != torch.int32:
-            labels = labels.to(torch.int32)
+        if self.loss is None:
+            if isinstance(labels, ops.TargetRef) or (isinstance(labels, torch.Tensor) and labels.dim() == 2
+                                                     and labels.is_floating_point()):
+                raise ValueError("dense targets need a Net built with loss= (the general loss path)")
+            if isinstance(labels, ops.LabelRef):
+                labels = labels.materialise(self.y_buf)
+            if labels.dtype != torch.int32:
+                labels = labels.to(torch.int32)
         logits = self.forward(x, training=True)
         stats = self.loss_and_grad(logits, labels)
         self.backward(self.dlogits, grad_ready)
@@ -665,16 +716,20 @@ class Net:
 
     @torch.no_grad()
     def evaluate(self, x, labels, batch_size: int = 4096):
-        """-> (mean loss, accuracy) over the given examples (inference mode, chunked)."""
+        """-> (mean loss, accuracy) over the given examples (inference mode, chunked).  The loss is the
+        training loss: with ``loss=`` that lossesMap entry, ``labels`` int classes or dense [N, C] targets."""
         n = x.shape[0]
         loss = 0.0
         correct = 0.0
         for s in range(0, n, batch_size):
             xb = x[s: s + batch_size].to(self.device, self.dtype)
-            yb = labels[s: s + batch_size].to(self.device, torch.int32)
+            dense = self.loss is not None and labels.is_floating_point()
+            yb = labels[s: s + batch_size].to(self.device, torch.float32 if dense else torch.int32)
             logits = self._forward_eval(xb)
             st = torch.zeros(2, dtype=torch.float32, device=self.device)
-            if self.final_act == "sigmoid":
+            if self.loss is not None:
+                ops.loss_grad(logits, yb.contiguous(), self.loss, self.final_act, None, st, 1.0)
+            elif self.final_act == "sigmoid":
                 ops.sigmoid_ce(logits, yb, None, st, 1.0)
             else:
                 ops.softmax_ce(logits, yb, None, st, 1.0)

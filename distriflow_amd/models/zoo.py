@@ -74,8 +74,9 @@ MODELS = {
 }
 
 
-def build_model(name: str, device="cuda", seed: int = 0) -> Net:
+def build_model(name: str, device="cuda", seed: int = 0, loss=None) -> Net:
+    """``loss``: a lossesMap name to train instead of the output's cross-entropy (Net's ``loss=``)."""
     if name not in MODELS:
         raise KeyError(f"unknown model {name!r}; choose from {sorted(MODELS)}")
     layers, in_shape = MODELS[name]()
-    return Net(layers, in_shape, device=device, name=name, seed=seed)
+    return Net(layers, in_shape, device=device, name=name, seed=seed, loss=loss)

@@ -794,6 +794,15 @@ class LabelRef:
         return gather_labels(self.labels, self.idx, out)
 
 
+class TargetRef:
+    """Dense fp32 targets of a batch that has not been gathered: ``targets[idx]`` ([N, C] table, int64
+    batch indices).  :func:`loss_grad` reads through the index vector, so no gather launch exists."""
+
+    def __init__(self, targets, idx):
+        self.targets, self.idx = targets, idx
+        self.shape = (idx.shape[0], targets.shape[1])
+
+
 def head_supported() -> bool:
     m = native.get(build_if_missing=False)
     return m is not None and hasattr(m, "head_train")
@@ -849,6 +858,95 @@ def khead_wgrad(pT, h1T, dz1T, dz2T, gw1, gb1, gw2, gb2, B, K, C, loss_part, sta
 METRIC_KINDS = {"meanSquaredError": 0, "mse": 0, "absoluteDifference": 1, "hingeLoss": 2, "huberLoss": 3,
                 "logLoss": 4, "sigmoidCrossEntropy": 5, "softmaxCrossEntropy": 6, "categorical_crossentropy": 7,
                 "categoricalCrossentropy": 7}
+
+
+def _out_act_code(out_act) -> int:
+    """0 linear, 1 softmax, 2 sigmoid, from the code itself, an activation name, or a final_softmax bool."""
+    if out_act in ("linear", None):
+        return 0
+    if out_act in ("softmax", "sigmoid"):
+        return 1 if out_act == "softmax" else 2
+    if isinstance(out_act, (bool, int)) and 0 <= int(out_act) <= 2:
+        return int(out_act)
+    raise ValueError(f"unknown output activation {out_act!r}")
+
+
+def _ld(t, C):
+    """Leading dimension of a [rows][C] matrix: a contiguous tensor or a column slice of a wider buffer."""
+    return int(t.stride(0)) if t.dim() == 2 and t.shape[0] > 1 and not t.is_contiguous() else int(t.shape[-1])
+
+
+def _loss_terms(kind: int, p, t):
+    """Per-element loss terms and dL/dp of METRIC_KINDS ``kind`` on outputs ``p`` vs targets ``t`` (the
+    closed forms of csrc/loss.hip; rows sum to the per-example loss)."""
+    C = p.shape[1]
+    d = p - t
+    if kind == 0:
+        return d * d / C, 2 * d / C
+    if kind == 1:
+        return d.abs() / C, torch.sign(d) / C
+    if kind == 2:
+        s = 2 * t - 1
+        m = 1 - s * p
+        return m.clamp_min(0) / C, torch.where(m > 0, -s, torch.zeros_like(s)) / C
+    if kind == 3:
+        a = d.abs()
+        return torch.where(a <= 1, 0.5 * d * d, a - 0.5) / C, torch.where(a <= 1, d, torch.sign(d)) / C
+    if kind == 4:
+        eps = 1e-7
+        return (-(t * torch.log(p + eps) + (1 - t) * torch.log(1 - p + eps)) / C,
+                (-t / (p + eps) + (1 - t) / (1 - p + eps)) / C)
+    if kind == 5:
+        return (p.clamp_min(0) - p * t + torch.log1p(torch.exp(-p.abs()))) / C, (torch.sigmoid(p) - t) / C
+    if kind == 6:
+        return -t * torch.log_softmax(p, dim=1), torch.softmax(p, dim=1) * t.sum(1, keepdim=True) - t
+    eps = 1e-7
+    inside = (p >= eps) & (p <= 1)
+    return -t * torch.log(p.clamp(eps, 1.0)), torch.where(inside, -t / p, torch.zeros_like(p))
+
+
+def loss_grad(logits, target, loss: str, out_act, dlogits=None, stats=None, grad_scale=1.0, idx=None):
+    """Any ``lossesMap`` loss (a key of METRIC_KINDS) on ``act(logits)``, fp32 ``logits`` [B][C], in one launch
+    (csrc/loss.hip): dlogits = grad_scale * dL/dlogits (bf16 on the GPU, rows of ``dlogits.shape[-1]`` elements);
+    stats += [sum of the per-example loss, #correct].  ``target``: an int tensor [.] of classes (one-hot, clamped
+    to the row) or a float tensor [., C] of dense targets; row b reads ``target[idx[b]]`` when ``idx`` (int64 [B])
+    is given.  ``out_act``: "linear" | "softmax" | "sigmoid" (or 0 / 1 / 2).  Correct: argmax logits == the
+    class, or == argmax of the dense target (first maximum).  ``logits`` / ``target`` / ``dlogits`` may be column
+    slices ``buf[:, :C]`` of wider buffers.  The CPU path is the same closed forms in fp32 torch."""
+    kind = METRIC_KINDS[loss]
+    act = _out_act_code(out_act)
+    B, C = logits.shape
+    dense = target.is_floating_point()
+    if dense and (target.dim() != 2 or target.shape[1] != C):
+        raise ValueError(f"dense targets must be [., {C}], got {tuple(target.shape)}")
+    if idx is None and target.shape[0] < B:
+        raise ValueError(f"{target.shape[0]} target rows for {B} rows of logits")
+    if logits.is_cuda:
+        if dense:
+            lab, tgt = None, (target if target.dtype == torch.float32 else target.float())
+        else:
+            lab, tgt = (target if target.dtype == torch.int32 else target.to(torch.int32)), None
+        _C().loss_grad(logits, lab, tgt, idx, dlogits, stats, B, C, _ld(logits, C), _ld(tgt, C) if dense else C,
+                       _ld(dlogits, C) if dlogits is not None else C, kind, act, float(grad_scale))
+        return stats
+    z = logits.float()
+    tt = target if idx is None else target.index_select(0, idx.long().clamp(0, target.shape[0] - 1))
+    tt = tt[:B]
+    if dense:
+        t = tt.float()
+        ref_class = t.argmax(1)
+    else:
+        ref_class = tt.long().view(-1).clamp(0, C - 1)
+        t = torch.nn.functional.one_hot(ref_class, C).float()
+    p = torch.softmax(z, dim=1) if act == 1 else (torch.sigmoid(z) if act == 2 else z)
+    terms, g = _loss_terms(kind, p, t)
+    if dlogits is not None:
+        dz = p * (g - (g * p).sum(1, keepdim=True)) if act == 1 else (g * p * (1 - p) if act == 2 else g)
+        dlogits[:, :C].copy_((dz * grad_scale).to(dlogits.dtype))
+    if stats is not None:
+        stats[0] += terms.sum()
+        stats[1] += (z.argmax(1) == ref_class).float().sum()
+    return stats
 
 
 def classifier_metrics(z, labels, loss: str, softmax, out):

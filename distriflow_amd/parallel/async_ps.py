@@ -46,7 +46,7 @@ import torch.distributed as dist
 
 from .. import native
 from ..diagnostics import diag, on as diag_on
-from .data_parallel import DataParallelTrainer, require_sgd, shared_gpu_exch_blocks
+from .data_parallel import DataParallelTrainer, require_default_loss, require_sgd, shared_gpu_exch_blocks
 
 
 class AsyncPSTrainer(DataParallelTrainer):
@@ -62,6 +62,7 @@ class AsyncPSTrainer(DataParallelTrainer):
         :meth:`attach`, parallel/elastic.py): uncached buffers and no exclusive-writer shortcuts even at one
         rank."""
         require_sgd(optimizer, type(self).__name__, "the master is updated by the parameter-server kernels")
+        require_default_loss(net, type(self).__name__)
         if not net.is_gpu:
             raise RuntimeError("AsyncPSTrainer is the GPU path; use AsynchronousSGDServer/Client on CPU")
         super().__init__(net, lr=lr, group=group, overlap=False, graph="full" if graph == "split" else graph,
@@ -215,6 +216,7 @@ class AsyncPSTrainer(DataParallelTrainer):
         m = rec["meta"]
         if int(m["n"]) != net.store.total:
             raise ValueError(f"attach: the server's master has {m['n']} elements, this model {net.store.total}")
+        require_default_loss(net, cls.__name__)
         self = cls.__new__(cls)
         DataParallelTrainer.__init__(self, net, lr=0.001 if lr is None else lr, group=None, overlap=False,
                                      graph="full" if graph == "split" else graph, broadcast_init=False,

@@ -37,6 +37,13 @@ def require_sgd(optimizer: str, who: str, why: str):
         raise ValueError(f"{who} supports optimizer='sgd' only ({why}); got {optimizer!r}")
 
 
+def require_default_loss(net, who: str):
+    """The device parameter-server engines train classification with the model's cross-entropy only."""
+    if getattr(net, "loss", None) is not None:
+        raise NotImplementedError(f"{who} trains the model's cross-entropy on class labels only; this net was "
+                                  f"built with loss={net.loss!r} (the general loss path)")
+
+
 class DataParallelTrainer:
     def __init__(self, net, lr: float = 0.001, momentum: float = 0.0, weight_decay: float = 0.0,
                  group=None, bucket_mb: Optional[float] = None, overlap: bool = True, graph: str = "full",
@@ -100,6 +107,7 @@ class DataParallelTrainer:
         self._graph_B = None
         self._index_stream = None
         self.preprocess_callbacks: list = []
+        self.dense_targets = False  # bind_dataset was given a float [N, C] target table
         self.steps = 0
         # device run statistics [loss sum, correct, updates, -]: accumulated inside the step's own last
         # launch (no extra launch), read back asynchronously per replay when callbacks are registered
@@ -405,7 +413,8 @@ class DataParallelTrainer:
         self.net.store.set_hyper(lr, self.momentum, self.weight_decay, grad_scale=self._grad_scale())
 
     def train_step(self, x: torch.Tensor, y: torch.Tensor):
-        """Eager step on an explicit batch; returns device stats [loss_sum, correct]."""
+        """Eager step on an explicit batch; returns device stats [loss_sum, correct].  ``y``: int labels, or
+        dense fp32 targets [B, C] when the net was built with ``loss=`` (the general loss path)."""
         self.steps += 1
         return self._step_body(x, y)
 
@@ -413,7 +422,18 @@ class DataParallelTrainer:
     def bind_dataset(self, data: torch.Tensor, labels: torch.Tensor, batch_size: int, scale: float = 1.0):
         """Attach an HBM-resident dataset (uint8/bf16 [N, ...], int32 labels); steps then take index batches.
         ``batch_size``: rows per step per rank; with ``min_updates_per_version`` it is the MICROBATCH size
-        and a step takes ``micro_per_rank[rank]`` microbatches (their rows concatenated)."""
+        and a step takes ``micro_per_rank[rank]`` microbatches (their rows concatenated).  A net built with
+        ``loss=`` (the general loss path) also takes a float [N, C] target table as ``labels``: the loss
+        kernel reads its rows through the step's index vector (no gather launch)."""
+        self.dense_targets = labels.is_floating_point()
+        if self.dense_targets:
+            if getattr(self.net, "loss", None) is None:
+                raise ValueError("a float target table needs a net built with loss= (the general loss path)")
+            if labels.dim() != 2 or labels.shape[1] != self.net.num_classes:
+                raise ValueError(f"the target table must be [N, {self.net.num_classes}], got {tuple(labels.shape)}")
+            if self.preprocess_callbacks:
+                raise NotImplementedError("preprocess callbacks with a dense target table")
+            labels = labels.to(torch.float32).contiguous()
         self.data, self.labels, self.scale = data, labels, scale
         self.micro_B = batch_size
         if self.min_updates is not None:
@@ -446,6 +466,8 @@ class DataParallelTrainer:
         1-element int64 tensor) and ``Batch.epoch`` is -1 (epochs are a host-side notion here).  The
         callback must be made of device tensor ops with fixed shapes: it is captured into the step's
         hipGraph and replayed with it.  It may return new tensors or modify ``x`` / ``y`` in place."""
+        if self.dense_targets:
+            raise NotImplementedError("preprocess callbacks with a dense target table")
         self.preprocess_callbacks.append(cb)
         self._graph = None  # the captured step must include it
         self._multi, self._multi_u = None, 0
@@ -474,6 +496,13 @@ class DataParallelTrainer:
     def _gather(self):
         if self.preprocess_callbacks:
             self._gather_preprocessed()
+            return
+        if getattr(self.net, "loss", None) is not None:
+            # the loss kernel reads labels / dense targets through the index vector: no gather launch
+            ref = ops.TargetRef if self.dense_targets else ops.LabelRef
+            self.yb = ref(self.labels, self.idx)
+            if not isinstance(self.xb, ops.GatherRef):
+                ops.gather_batch(self.data, None, self.idx, self.xb, None, self.scale)
             return
         if isinstance(self.xb, ops.GatherRef):
             if self.net.head_start is not None:

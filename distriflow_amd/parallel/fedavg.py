@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import torch
 
-from .data_parallel import DataParallelTrainer, require_sgd
+from .data_parallel import DataParallelTrainer, require_default_loss, require_sgd
 
 
 class FedAvgTrainer(DataParallelTrainer):
@@ -29,6 +29,7 @@ class FedAvgTrainer(DataParallelTrainer):
     def __init__(self, net, lr: float = 0.05, local_steps: int = 20, group=None, graph: str = "full",
                  allreduce: str = "auto", optimizer: str = "sgd"):
         require_sgd(optimizer, "FedAvgTrainer", "whether optimizer state survives the weight averaging is undecided")
+        require_default_loss(net, "FedAvgTrainer")
         super().__init__(net, lr=lr, group=group, overlap=False, graph=graph, allreduce=allreduce)
         self.local_steps = int(local_steps)
         self.rounds = 0
