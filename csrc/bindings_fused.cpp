@@ -33,51 +33,55 @@ CPIn cp_input(const torch::Tensor& x, const c10::optional<torch::Tensor>& idx, i
   return r;
 }
 
+// the prologue of the three launches: the plan of the geometry (fetched once), the batch, the pooled elements
+struct CPCall {
+  const dfa::CPPlan& p;
+  int64_t B, pn;
+};
+
+CPCall cp_call(const std::vector<int64_t>& geom) {
+  TORCH_CHECK(geom.size() == 8, "geom = [B,H,W,C,KH,KW,pad,N]");
+  const dfa::CPPlan& p = dfa::convpool_plan(geom[1], geom[2], geom[3], geom[4], geom[5], geom[6], geom[7]);
+  TORCH_CHECK(p.ok, "convpool: unsupported geometry");
+  return {p, geom[0], geom[0] * p.g.PH * p.g.PW * p.g.N};
+}
+
 void convpool_fwd_py(torch::Tensor x, c10::optional<torch::Tensor> idx, double scale, torch::Tensor w,
                      c10::optional<torch::Tensor> bias, torch::Tensor p, c10::optional<torch::Tensor> code,
                      std::vector<int64_t> geom) {
-  TORCH_CHECK(geom.size() == 8, "geom = [B,H,W,C,KH,KW,pad,N]");
-  const int B = geom[0], H = geom[1], W = geom[2], C = geom[3], KH = geom[4], KW = geom[5], pad = geom[6], N = geom[7];
-  TORCH_CHECK(dfa::convpool_supported(H, W, C, KH, KW, pad, N), "convpool: unsupported geometry");
-  CPIn in = cp_input(x, idx, B, (int64_t)H * W * C);
+  const CPCall c = cp_call(geom);
+  const dfa::CPGeom& g = c.p.g;
+  CPIn in = cp_input(x, idx, c.B, (int64_t)g.H * g.W * g.C);
   need(w, at::kBFloat16, "w");
-  // row-segment layout [Npad16][Kpad2] (ParamSpec.row_pad / row_cp, convpool_fwd_layout)
-  int Cp = 0, Kpad2 = 0, pair = 0;
-  dfa::convpool_fwd_layout(H, W, C, KH, KW, pad, N, &Cp, &Kpad2, &pair);
-  TORCH_CHECK(w.numel() >= (int64_t)((N + 15) / 16 * 16) * Kpad2 && w.size(-1) == Kpad2,
-              "w must be the row-segment layout [Npad16][", Kpad2, "] (channel stride ", Cp, ")");
-  const int OH = H + 2 * pad - KH + 1, OW = W + 2 * pad - KW + 1;
-  const int64_t pn = (int64_t)B * (OH / 2) * (OW / 2) * N;
+  // row-segment layout [Npad16][Kpad2] (ParamSpec.row_pad / row_cp)
+  TORCH_CHECK(w.numel() >= (int64_t)((g.N + 15) / 16 * 16) * g.wKpad2 && w.size(-1) == g.wKpad2,
+              "w must be the row-segment layout [Npad16][", g.wKpad2, "] (channel stride ", g.Cp, ")");
   need(p, at::kBFloat16, "p");
-  TORCH_CHECK(p.numel() >= pn, "p too small");
-  uint8_t* cp = opt_ptr<uint8_t>(code, at::kByte, "code", pn, "code too small");
-  const float* bp = opt_ptr<const float>(bias, at::kFloat, "bias", N, "bias too small");
-  check_hip(dfa::convpool_fwd(in.x, in.u8, in.idx, in.nrows, (float)scale, B, H, W, C, KH, KW, pad, N,
-                              (const dfa::bf16*)w.data_ptr(), bp, (dfa::bf16*)p.data_ptr(), cp,
-                              cur_stream()),
+  TORCH_CHECK(p.numel() >= c.pn, "p too small");
+  uint8_t* cp = opt_ptr<uint8_t>(code, at::kByte, "code", c.pn, "code too small");
+  const float* bp = opt_ptr<const float>(bias, at::kFloat, "bias", g.N, "bias too small");
+  check_hip(dfa::convpool_fwd(c.p, c.B, in.x, in.u8, in.idx, in.nrows, (float)scale, (const dfa::bf16*)w.data_ptr(), bp,
+                              (dfa::bf16*)p.data_ptr(), cp, cur_stream()),
             "convpool_fwd");
 }
 
 int64_t convpool_wgrad_py(torch::Tensor x, c10::optional<torch::Tensor> idx, double scale, torch::Tensor dp,
                           torch::Tensor code, torch::Tensor gw, c10::optional<torch::Tensor> gb, torch::Tensor ws,
                           std::vector<int64_t> geom, bool defer) {
-  TORCH_CHECK(geom.size() == 8, "geom = [B,H,W,C,KH,KW,pad,N]");
-  const int B = geom[0], H = geom[1], W = geom[2], C = geom[3], KH = geom[4], KW = geom[5], pad = geom[6], N = geom[7];
-  TORCH_CHECK(dfa::convpool_supported(H, W, C, KH, KW, pad, N), "convpool: unsupported geometry");
-  CPIn in = cp_input(x, idx, B, (int64_t)H * W * C);
-  const int OH = H + 2 * pad - KH + 1, OW = W + 2 * pad - KW + 1;
-  const int64_t pn = (int64_t)B * (OH / 2) * (OW / 2) * N;
+  const CPCall c = cp_call(geom);
+  const dfa::CPGeom& g = c.p.g;
+  CPIn in = cp_input(x, idx, c.B, (int64_t)g.H * g.W * g.C);
   need(dp, at::kBFloat16, "dp");
   need(code, at::kByte, "code");
-  TORCH_CHECK(dp.numel() >= pn && code.numel() >= pn, "dp/code too small");
+  TORCH_CHECK(dp.numel() >= c.pn && code.numel() >= c.pn, "dp/code too small");
   need(gw, at::kFloat, "gw");
-  TORCH_CHECK(gw.numel() >= (int64_t)N * KH * KW * C, "gw too small");
-  float* gbp = opt_ptr<float>(gb, at::kFloat, "gb", N, "gb too small");
+  TORCH_CHECK(gw.numel() >= (int64_t)g.N * g.K, "gw too small");
+  float* gbp = opt_ptr<float>(gb, at::kFloat, "gb", g.N, "gb too small");
   need(ws, at::kFloat, "workspace");
   int slabs = 0;
-  check_hip(dfa::convpool_wgrad(in.x, in.u8, in.idx, in.nrows, (float)scale, B, H, W, C, KH, KW, pad, N,
-                                (const dfa::bf16*)dp.data_ptr(), code.data_ptr<uint8_t>(), gw.data_ptr<float>(), gbp,
-                                ws.data_ptr<float>(), (size_t)ws.numel(), cur_stream(), defer ? &slabs : nullptr),
+  check_hip(dfa::convpool_wgrad(c.p, c.B, in.x, in.u8, in.idx, in.nrows, (float)scale, (const dfa::bf16*)dp.data_ptr(),
+                                code.data_ptr<uint8_t>(), gw.data_ptr<float>(), gbp, ws.data_ptr<float>(),
+                                (size_t)ws.numel(), cur_stream(), defer ? &slabs : nullptr),
             "convpool_wgrad");
   return slabs;  // > 0: the slab reduction was deferred (run it with slab_reduce_multi)
 }
@@ -115,26 +119,51 @@ void slab_reduce_multi_py(std::vector<py::tuple> segs) {
 
 void convpool_dgrad_py(torch::Tensor dp, torch::Tensor code, torch::Tensor wt, torch::Tensor dx,
                        std::vector<int64_t> geom) {
-  TORCH_CHECK(geom.size() == 8, "geom = [B,H,W,C,KH,KW,pad,N]");
-  const int B = geom[0], H = geom[1], W = geom[2], C = geom[3], KH = geom[4], KW = geom[5], pad = geom[6], N = geom[7];
-  TORCH_CHECK(dfa::convpool_supported(H, W, C, KH, KW, pad, N), "convpool: unsupported geometry");
-  const int OH = H + 2 * pad - KH + 1, OW = W + 2 * pad - KW + 1;
-  const int64_t pn = (int64_t)B * (OH / 2) * (OW / 2) * N;
+  const CPCall c = cp_call(geom);
+  const dfa::CPGeom& g = c.p.g;
+  const dfa::CPDgrad& d = c.p.d;
   need(dp, at::kBFloat16, "dp");
   need(code, at::kByte, "code");
-  TORCH_CHECK(dp.numel() >= pn && code.numel() >= pn, "dp/code too small");
+  TORCH_CHECK(dp.numel() >= c.pn && code.numel() >= c.pn, "dp/code too small");
   need(wt, at::kBFloat16, "wt");
-  int pair = 0, K2pad = 0;
-  dfa::convpool_dgrad_layout(H, W, C, KH, KW, pad, N, &pair, &K2pad);
-  const int rows = pair ? 16 : (C + 15) / 16 * 16;
-  TORCH_CHECK(wt.size(-1) == K2pad && wt.numel() >= (int64_t)rows * K2pad, "wt must be the dgrad layout [", rows,
-              "][", K2pad, "] (pair ", pair, ")");
+  const int rows = d.pair ? 16 : (g.C + 15) / 16 * 16;
+  TORCH_CHECK(wt.size(-1) == d.K2pad && wt.numel() >= (int64_t)rows * d.K2pad, "wt must be the dgrad layout [", rows,
+              "][", d.K2pad, "] (pair ", d.pair, ")");
   need(dx, at::kBFloat16, "dx");
-  TORCH_CHECK(dx.numel() >= (int64_t)B * H * W * C, "dx too small");
-  check_hip(dfa::convpool_dgrad((const dfa::bf16*)dp.data_ptr(), code.data_ptr<uint8_t>(),
-                                (const dfa::bf16*)wt.data_ptr(), (dfa::bf16*)dx.data_ptr(), B, H, W, C, KH, KW, pad,
-                                N, cur_stream()),
+  TORCH_CHECK(dx.numel() >= (int64_t)c.B * g.H * g.W * g.C, "dx too small");
+  check_hip(dfa::convpool_dgrad(c.p, c.B, (const dfa::bf16*)dp.data_ptr(), code.data_ptr<uint8_t>(),
+                                (const dfa::bf16*)wt.data_ptr(), (dfa::bf16*)dx.data_ptr(), cur_stream()),
             "convpool_dgrad");
+}
+
+// The plan of a geometry as a dict (no GPU needed).  B > 0 adds the launch sizes for that batch and a weight-
+// gradient workspace of ws_floats (these ask the device for the kernels' occupancy; nothing is launched; the
+// data gradient is sized for aligned dp / code).
+py::dict convpool_plan_py(int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW, int64_t pad, int64_t N, int64_t B,
+                          int64_t ws_floats) {
+  using namespace pybind11::literals;
+  const dfa::CPPlan& p = dfa::convpool_plan(H, W, C, KH, KW, pad, N);
+  py::dict r("ok"_a = p.ok, "Cp"_a = p.g.Cp, "Kpad2"_a = p.g.wKpad2, "pair"_a = p.g.pair, "dgrad_pair"_a = p.d.pair,
+             "K2pad"_a = p.d.K2pad);
+  if (!p.ok) return r;
+  auto launch = [&](const char* name, py::tuple key, int inst, const int* have, auto size) {
+    py::list l;
+    for (; *have; ++have) l.append(*have);
+    py::dict d("key"_a = key, "instance"_a = inst, "instantiated"_a = l);
+    if (B > 0) {
+      const dfa::CPSizing z = size();
+      d["imgs"] = z.imgs, d["grid"] = z.grid, d["lds"] = z.lds;
+    }
+    r[name] = d;
+  };
+  static const char* const kKind[] = {"pair", "vec", "scalar"};
+  launch("fwd", py::make_tuple(p.g.pair, p.fwd_NT, p.fwd_nk), p.fwd_NK, p.fwd_list,
+         [&] { return dfa::convpool_size_fwd(p, (int)B); });
+  launch("wgrad", py::make_tuple(p.wg_NT, p.wg_KT), p.wg_KTMAX, p.wg_list,
+         [&] { return dfa::convpool_size_wgrad(p, (int)B, (size_t)ws_floats); });
+  launch("dgrad", py::make_tuple(kKind[p.dg_kind], p.dg_nk), p.dg_NKMAX, p.dg_list,
+         [&] { return dfa::convpool_size_dgrad(p, (int)B); });
+  return r;
 }
 
 // a dense head's labels: read through idx (a dataset of any length) or row by row (at least B)
@@ -614,10 +643,6 @@ void kcnn_bwd_py(torch::Tensor x, c10::optional<torch::Tensor> idx, double scale
             "kcnn_bwd");
 }
 
-bool convpool_supported_py(int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW, int64_t pad, int64_t N) {
-  return dfa::convpool_supported(H, W, C, KH, KW, pad, N);
-}
-
 }  // namespace
 
 void bind_fused(py::module_& m) {
@@ -640,17 +665,9 @@ void bind_fused(py::module_& m) {
       dfa::lenet_set_stamps(nullptr);
     }
   }, "profiling aid: per-block phase stamps of the convpool kernels");
-  m.def("convpool_fwd_layout", [](int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW, int64_t pad, int64_t N) {
-    int Cp = 0, Kpad2 = 0, pair = 0;
-    dfa::convpool_fwd_layout(H, W, C, KH, KW, pad, N, &Cp, &Kpad2, &pair);
-    return std::make_tuple(Cp, Kpad2, pair);
-  }, "forward weight layout of the fused conv+pool kernel: (channel stride Cp, row length Kpad2, pair)");
-  m.def("convpool_dgrad_layout", [](int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW, int64_t pad, int64_t N) {
-    int pair = 0, K2pad = 0;
-    dfa::convpool_dgrad_layout(H, W, C, KH, KW, pad, N, &pair, &K2pad);
-    return std::make_tuple(pair, K2pad);
-  }, "data-gradient weight layout of the fused conv+pool kernel: (pair, row length K2pad)");
-  m.def("convpool_supported", &convpool_supported_py);
+  m.def("convpool_plan", &convpool_plan_py, "the launch plan of a fused conv+pool geometry", py::arg("H"), py::arg("W"),
+        py::arg("C"), py::arg("KH"), py::arg("KW"), py::arg("pad"), py::arg("N"), py::arg("B") = 0,
+        py::arg("ws_floats") = 0);
   m.def("head_train", &head_train_py, "fused dense head: forward + softmax-CE + backward (2 launches)",
         py::arg("w"), py::arg("wt"), py::arg("b"), py::arg("gw"), py::arg("gb"), py::arg("hT"), py::arg("dzT"),
         py::arg("K"), py::arg("N"), py::arg("x"), py::arg("x_relu"), py::arg("xT"), py::arg("dx"), py::arg("logits"),

@@ -70,6 +70,17 @@ inline FastDiv make_fastdiv(unsigned d) {
 
 __device__ __forceinline__ unsigned fdiv(unsigned n, FastDiv f) { return (__umulhi(n, f.mul) + n) >> f.shr; }
 
+// Compute units of the current device (256 when it cannot be asked), for persistent-grid sizing
+inline int num_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+  }
+  return n;
+}
+
 // Bijective XCD-aware remap of a 1-D block id: consecutive logical tiles land on the same XCD
 // (blocks b and b+8 share an XCD under round-robin dispatch) so neighbouring tiles share L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {

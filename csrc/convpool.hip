@@ -26,6 +26,8 @@
 // point at a real LDS element instead of being masked (the matching weight rows are zero padding
 // and activations are finite, so they contribute exactly 0), weights / offsets / bias live in
 // registers for the whole workgroup.
+// Host side: convpool_plan (kernels.h CPPlan) decides everything about a geometry once (support, the kernel
+// argument structs, the instantiation of each launch, the sizing inputs); the launchers only read it.
 #include <cstdlib>
 
 #include "common.h"
@@ -38,20 +40,6 @@
 #include <numeric>
 
 namespace dfa {
-
-struct CPGeom {
-  int B, H, W, C, KH, KW, pad, N, OH, OW, PH, PW, K, Kpad;
-  int Hp, Wp, img_elems;  // padded input image in LDS
-  int imgs;               // images per workgroup
-  // forward row-segment layout: k = ky*RLp + (kx*C + c); every 8-slot k group is 8 CONSECUTIVE
-  // elements of one padded image row, read with one 16-byte LDS load from one of S shifted copies
-  int Cp;                  // LDS channel stride of the forward image (>= C, zero-filled channels)
-  int RLp, chunks, Kpad2;  // RLp = round8(KW*Cp), chunks = RLp/8, Kpad2 = round32(KH*RLp)
-  int G, S, RowP, ystr, xs_img;  // G = gcd(C,8): copy ci is shifted by ci*G elements, S = 8/G copies
-  int pair;                       // forward pair mode (N <= 8): cols 8-15 = pixel x+1 via shifted weights
-  int wRLp, wKpad2;               // GLOBAL weight layout (row-segment, KW columns): round8(KW*Cp), row length
-  unsigned long long* stamps;     // profiling aid: per-block s_memtime stamps [grid][32] (nullptr = off)
-};
 
 static unsigned long long* g_cp_stamps = nullptr;
 void convpool_set_stamps(void* buf) { g_cp_stamps = reinterpret_cast<unsigned long long*>(buf); }
@@ -440,14 +428,7 @@ __global__ void __launch_bounds__(256) convpool_fwd_kernel(CPGeom g, int vec, co
 //       [C][Hq][KW][RowQ], copy s = row shifted left by s, so column k = (ky, kx, c) of pixels
 //       ox0..ox0+7 is copy kx of row oy+ky at ox0 (ox0 a multiple of 8).
 // A chunk = (4/G) output rows x 8G columns (one row / 8 columns per 16-lane group).
-struct CPWg {
-  int G, R;                          // lane-group split: chunk = R = 4/G rows x 8G cols
-  int OHc, OWc, cpr, cpc, cpi;       // chunk-aligned output extent, chunk rows/cols, chunks per image
-  int Hq, RowQ, ystr, cstr, xs_img;  // X image [C][Hq][KW][RowQ] (+pads)
-  int DWc, dcs, dc_img;              // dConv image [N+1][OHc][DWc] (+pad; plane N stays zero), dc_img = (N+1)*dcs
-  int build_per_img;                 // shifted-copy build tasks per image
-};
-
+// The layout is CPWg (kernels.h), filled by make_wg below.
 template <int KT>
 struct WgU {
   static constexpr int value = KT <= 2 ? 4 : (KT <= 5 ? 2 : 1);
@@ -772,20 +753,11 @@ __global__ void __launch_bounds__(256) convpool_wgrad_kernel(CPGeom g, CPWg q, i
 
 // ------------------------------------------------------------------------------------------------
 // Data gradient through the pool: dx[b][iy][ix][c] = sum_{ky,kx,n} dConv[iy+pad-ky][ix+pad-kx][n] W[n][ky][kx][c]
-struct CPDgrad {
-  int Hq, Wq, q_elems, P;  // padded dConv image in LDS, P = KH-1-pad
-  int K2, K2pad;           // K2 = KH*KW*N  (pair: KH*(KW+1)*N)
-  int Nq;                  // LDS pixel stride (>= N): 16-byte reads of 8 consecutive pixels hit distinct banks
-  int pair;                // C <= 8, W even: MFMA rows = pixel pairs, columns 8-15 = pixel x+1 (shifted weights)
-};
-
 // dgrad weight layouts (emitted by the optimizer, csrc/optim.hip):
 //  plain: [Cpad16][round32(KH*KW*N)],   element (c, (ky*KW+kx)*N + n) = W[n][ky][kx][c]
 //  pair:  [16][round32(KH*(KW+1)*N)],  patch tap (a, b) = (row, col) of the flipped kernel window:
 //         row c   : col (a*(KW+1) + b)*N + n = W[n][KH-1-a][KW-1-b][c]    (b < KW)
 //         row 8+c : col (a*(KW+1) + b)*N + n = W[n][KH-1-a][KW-b][c]      (b >= 1)
-static CPGeom make_geom(int B, int H, int W, int C, int KH, int KW, int pad, int N);
-
 static CPDgrad make_dgrad(const CPGeom& g) {
   CPDgrad d{};
   d.P = g.KH - 1 - g.pad;
@@ -799,13 +771,6 @@ static CPDgrad make_dgrad(const CPGeom& g) {
   d.K2 = g.KH * (g.KW + d.pair) * g.N;
   d.K2pad = round_up(d.K2, 32);
   return d;
-}
-
-void convpool_dgrad_layout(int H, int W, int C, int KH, int KW, int pad, int N, int* pair, int* K2pad) {
-  CPGeom g = make_geom(1, H, W, C, KH, KW, pad, N);
-  const CPDgrad d = make_dgrad(g);
-  *pair = d.pair;
-  *K2pad = d.K2pad;
 }
 
 template <int NT, int NKMAX, bool VEC, int CHM, bool PAIR>
@@ -1264,13 +1229,7 @@ static void set_fwd_pair_layout(CPGeom& g) {
   g.xs_img = g.Hp * g.ystr;
 }
 
-static const FwdLayout& choose_fwd_layout(const CPGeom& g0, bool pair) {
-  static std::mutex mu;
-  static std::map<std::array<int, 7>, FwdLayout> cache;
-  const std::array<int, 7> key{g0.H, g0.W, g0.C, g0.KH, g0.KW, g0.pad, pair ? 1 : 0};
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
+static FwdLayout choose_fwd_layout(const CPGeom& g0, bool pair) {
   FwdLayout best{g0.C, 0, 0};
   double best_score = 1e30;
   for (int Cp : {g0.C, round_up(g0.C, 2), round_up(g0.C, 4), round_up(g0.C, 8)}) {
@@ -1291,13 +1250,12 @@ static const FwdLayout& choose_fwd_layout(const CPGeom& g0, bool pair) {
         }
       }
   }
-  return cache.emplace(key, best).first->second;
+  return best;
 }
 
-static CPGeom make_geom(int B, int H, int W, int C, int KH, int KW, int pad, int N) {
+static CPGeom make_geom(int H, int W, int C, int KH, int KW, int pad, int N) {
   CPGeom g{};
-  g.stamps = g_cp_stamps;
-  g.B = B; g.H = H; g.W = W; g.C = C; g.KH = KH; g.KW = KW; g.pad = pad; g.N = N;
+  g.H = H; g.W = W; g.C = C; g.KH = KH; g.KW = KW; g.pad = pad; g.N = N;
   g.OH = H + 2 * pad - KH + 1;
   g.OW = W + 2 * pad - KW + 1;
   g.PH = g.OH / 2;
@@ -1309,160 +1267,12 @@ static CPGeom make_geom(int B, int H, int W, int C, int KH, int KW, int pad, int
   g.img_elems = round_up(g.Hp * g.Wp * C + 8, 8);  // +8: slack for the finite "padding column" reads
   set_fwd_layout(g, C, 0, 0);
   const bool pair = N <= 8 && g.OW >= 2;
-  const FwdLayout& L = choose_fwd_layout(g, pair);
+  const FwdLayout L = choose_fwd_layout(g, pair);
   set_fwd_layout(g, L.Cp, L.RowP, L.ypad);
   if (pair) set_fwd_pair_layout(g);
   g.wRLp = g.RLp;  // the compute copy is emitted by the optimizer in exactly the kernel's layout
   g.wKpad2 = g.Kpad2;
   return g;
-}
-
-static const size_t kLdsBudget = 64 * 1024;  // keeps >= 2 workgroups per CU (160 KiB LDS)
-constexpr int kStageChunks = 4;              // register-staged 4-element chunks per thread and group
-
-void convpool_fwd_layout(int H, int W, int C, int KH, int KW, int pad, int N, int* Cp, int* Kpad2, int* pair) {
-  CPGeom g = make_geom(1, H, W, C, KH, KW, pad, N);
-  *Cp = g.Cp;
-  *Kpad2 = g.wKpad2;
-  *pair = g.pair;
-}
-
-bool convpool_supported(int H, int W, int C, int KH, int KW, int pad, int N) {
-  CPGeom g = make_geom(1, H, W, C, KH, KW, pad, N);
-  if (g.OH <= 0 || g.OW <= 0 || (g.OH & 1) || (g.OW & 1)) return false;
-  if ((g.PH * g.PW * N) % 4 != 0) return false;  // 4-element pooled-gradient chunks (wgrad scatter plan)
-  if (g.PH * g.PW * N > kStageChunks * 1024) return false;  // one image's pooled gradient fits the plan
-  if (C > 16 || N > 32 || KH > 7 || KW > 7) return false;
-  if (g.Kpad2 / 32 > 16 || g.wKpad2 / 32 > 16) return false;  // fwd weight fragments in registers
-  if ((g.K + 16) / 16 > 13) return false;                 // wgrad accumulators (incl. bias column)
-  if (KH != KW) return false;  // dConv padding P = KH-1-pad is shared by both axes
-  {
-    const CPDgrad d = make_dgrad(g);
-    if (d.K2pad / 32 > (d.pair ? 18 : 16)) return false;  // dgrad weight fragments in registers
-  }
-  const int P = KH - 1 - pad;
-  if (P < 0) return false;
-  const int Nq = N % 8 == 0 ? ((N / 8) % 2 == 1 ? N : N + 8) : N;
-  const size_t q_elems = (size_t)(g.OH + 2 * P) * (g.OW + 2 * P) * Nq;
-  if ((size_t)g.img_elems * 2 > kLdsBudget / 2 || q_elems * 2 > kLdsBudget / 2) return false;
-  if ((size_t)g.xs_img * 2 > kLdsBudget / 2) return false;
-  return true;
-}
-
-static int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
-// Persistent grid: `wg_per_cu` workgroups per CU, each looping over groups of `imgs` images; the
-// per-workgroup setup (tables, weights in registers) is paid once per workgroup, not per group.
-// Persistent-grid sizing from the kernel's real occupancy: blocks/CU allowed by its registers picks
-// the LDS budget per block (-> images per group), then the grid is exactly the resident block count
-// at that LDS size, so every block starts in the first (and only) dispatch round.
-static int blocks_per_cu(const void* kern, size_t lds) {
-  static std::mutex mu;
-  static std::map<std::pair<const void*, size_t>, int> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  auto key = std::make_pair(kern, lds);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
-  cache[key] = nb;
-  return nb;
-}
-
-struct Sizing {
-  int imgs, grid;
-  size_t lds;
-};
-
-// Tuning overrides (measurement only, csrc/diag.h): cp_wpc caps workgroups per CU, cp_minimgs raises
-// the images per group (fewer, longer-lived workgroups amortise the per-workgroup setup).
-
-static Sizing size_persistent(const void* kern, int B, size_t fixed, size_t per_img, size_t min_lds, int cap) {
-  static const int wpc_cap = max(1, diag_int("cp_wpc", 8));
-  static const int min_imgs = max(1, diag_int("cp_minimgs", 1));
-  const int wpc = min(wpc_cap, blocks_per_cu(kern, 0));
-  const size_t budget = (160 * 1024) / wpc;
-  int fit = (int)max((size_t)1, (budget > fixed ? budget - fixed : 0) / per_img);
-  fit = max(1, min(fit, min(cap, 32)));
-  Sizing z{};
-  z.imgs = min(fit, max(min_imgs, cdiv(B, num_cus() * wpc)));
-  z.lds = max(fixed + (size_t)z.imgs * per_img, min_lds);
-  const int nb = blocks_per_cu(kern, z.lds);
-  z.grid = min(num_cus() * nb, cdiv(B, z.imgs));
-  return z;
-}
-
-template <int NT, int NK, bool PAIR = false>
-static hipError_t launch_cp_fwd(CPGeom g, bool vec, const void* x, int x_u8, const long long* idx, long long nrows,
-                                float scale, const bf16* w, const float* bias, bf16* p, uint8_t* code,
-                                hipStream_t st) {
-  auto kern = convpool_fwd_kernel<NT, NK, kStageChunks, PAIR>;
-  const int tpi = cdiv(g.PH * g.PW, PAIR ? 8 : 4);
-  const Sizing z = size_persistent(reinterpret_cast<const void*>(kern), g.B, 32,
-                                   (size_t)tpi * (16 * 4 + 8) + (size_t)g.xs_img * 2, 0,
-                                   kStageChunks * 256 * 4 / (g.H * g.W * g.C));
-  g.imgs = z.imgs;
-  hipLaunchKernelGGL(kern, dim3(z.grid), dim3(256), z.lds, st, g, (int)vec, x, x_u8, idx, nrows, scale, w, bias, p,
-                     code);
-  return hipGetLastError();
-}
-
-// 4-element vector staging applies when image rows are whole 4-element chunks and the source is aligned
-static bool stage_vec_ok(const CPGeom& g, const void* x, int x_u8) {
-  return (g.W * g.C) % 4 == 0 && g.H * g.W * g.C <= kStageChunks * 1024 && (g.Cp == g.C || g.C >= 2) &&
-         (reinterpret_cast<uintptr_t>(x) % (x_u8 ? 4 : 8)) == 0;
-}
-
-hipError_t convpool_fwd(const void* x, int x_u8, const long long* idx, long long nrows, float scale, int B, int H,
-                        int W, int C, int KH, int KW, int pad, int N, const bf16* w, const float* bias, bf16* p,
-                        uint8_t* code, hipStream_t st) {
-  if (!convpool_supported(H, W, C, KH, KW, pad, N)) return hipErrorInvalidValue;
-  CPGeom g = make_geom(B, H, W, C, KH, KW, pad, N);
-  const bool vec = stage_vec_ok(g, x, x_u8);
-  const int nk = g.Kpad2 / 32;
-  const int nt = cdiv(N, 16);
-#define CP_FWD(NT_, NK_) return launch_cp_fwd<NT_, NK_>(g, vec, x, x_u8, idx, nrows, scale, w, bias, p, code, st)
-#define CP_FWDP(NK_) return launch_cp_fwd<1, NK_, true>(g, vec, x, x_u8, idx, nrows, scale, w, bias, p, code, st)
-  if (g.pair) {
-    if (nk <= 1) CP_FWDP(1);
-    if (nk <= 2) CP_FWDP(2);
-    if (nk <= 3) CP_FWDP(3);
-    if (nk <= 4) CP_FWDP(4);
-    if (nk <= 5) CP_FWDP(5);
-    if (nk <= 7) CP_FWDP(7);
-    if (nk <= 10) CP_FWDP(10);
-    CP_FWDP(16);
-  }
-  if (nt == 1) {
-    if (nk <= 1) CP_FWD(1, 1);
-    if (nk <= 2) CP_FWD(1, 2);
-    if (nk <= 3) CP_FWD(1, 3);
-    if (nk <= 4) CP_FWD(1, 4);
-    if (nk <= 5) CP_FWD(1, 5);
-    if (nk <= 6) CP_FWD(1, 6);
-    if (nk <= 7) CP_FWD(1, 7);
-    if (nk <= 8) CP_FWD(1, 8);
-    if (nk <= 10) CP_FWD(1, 10);
-    if (nk <= 13) CP_FWD(1, 13);
-    CP_FWD(1, 16);
-  }
-  if (nk <= 2) CP_FWD(2, 2);
-  if (nk <= 4) CP_FWD(2, 4);
-  if (nk <= 5) CP_FWD(2, 5);
-  if (nk <= 7) CP_FWD(2, 7);
-  if (nk <= 8) CP_FWD(2, 8);
-  if (nk <= 13) CP_FWD(2, 13);
-  CP_FWD(2, 16);
-#undef CP_FWD
-#undef CP_FWDP
 }
 
 static CPWg make_wg(const CPGeom& g) {
@@ -1498,103 +1308,216 @@ static CPWg make_wg(const CPGeom& g) {
   return q;
 }
 
-template <int NT, int KTMAX>
-static hipError_t launch_cp_wgrad(CPGeom g, bool vec, const void* x, int x_u8, const long long* idx, long long nrows,
-                                  float scale, const bf16* dp, const uint8_t* code, float* gw, float* gb,
-                                  float* workspace, size_t ws_floats, hipStream_t st, int* deferred) {
-  auto kern = convpool_wgrad_kernel<NT, KTMAX, kStageChunks>;
-  const CPWg q = make_wg(g);
-  const int Kt = g.K + 1;
-  const int KT = cdiv(Kt, 16);
-  const int wn = g.PH * g.PW * g.N;
-  const size_t red_bytes = (size_t)4 * NT * 16 * KT * 16 * 4;
-  // caps: register staging plans (image chunks, 2x pooled chunks per thread)
-  int cap = min(kStageChunks * 256 * 4 / (g.H * g.W * g.C), kStageChunks * 256 * 4 / wn);
-  cap = min(cap, 65535 / q.dc_img);  // scatter offsets are packed as 16 bits
-  Sizing z = size_persistent(reinterpret_cast<const void*>(kern), g.B, 64,
-                             (size_t)q.cpi * 8 + ((size_t)q.xs_img + q.dc_img) * 2 + 16, red_bytes, max(cap, 1));
-  while ((size_t)z.grid * g.N * Kt > ws_floats && z.grid > 1) z.grid /= 2;
-  if ((size_t)z.grid * g.N * Kt > ws_floats || z.lds > 160 * 1024) return hipErrorInvalidValue;
-  g.imgs = z.imgs;
-  hipLaunchKernelGGL(kern, dim3(z.grid), dim3(256), z.lds, st, g, q, (int)vec, x, x_u8, idx, nrows, scale, dp, code,
-                     workspace);
+static const size_t kLdsBudget = 64 * 1024;      // keeps >= 2 workgroups per CU (160 KiB LDS)
+constexpr int kStageChunks = 4;                   // register-staged 4-element chunks per thread and group
+constexpr int kStageElems = kStageChunks * 1024;  // elements a workgroup's staging plan holds per group
+constexpr size_t kTileTabBytes = 16 * 4 + 8;      // LDS table bytes per 16-row MFMA tile (fwd / dgrad)
+
+// The instantiated step counts of each ladder (0 ends a list).  A launch takes the smallest one >= its own
+// count; the kernel pickers below switch over the same lists, so these are the instantiations, once.
+#define CP_FWD_PAIR_NK(X) X(1) X(2) X(3) X(4) X(5) X(7) X(10) X(16)
+#define CP_FWD_NT1_NK(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(10) X(13) X(16)
+#define CP_FWD_NT2_NK(X) X(2) X(4) X(5) X(7) X(8) X(13) X(16)
+#define CP_WG_NT1_KT(X) X(2) X(4) X(10) X(13)
+#define CP_WG_NT2_KT(X) X(2) X(4) X(13)
+#define CP_DG_PAIR_NK(X) X(4) X(8) X(12) X(15) X(18)
+#define CP_DG_VEC_NK(X) X(2) X(4) X(5) X(8) X(10) X(13) X(16)
+#define CP_DG_SCALAR_NK(X) X(4) X(8) X(16)
+#define CP_ITEM(n) n,
+constexpr int kFwdPairNK[] = {CP_FWD_PAIR_NK(CP_ITEM) 0}, kFwdNT1NK[] = {CP_FWD_NT1_NK(CP_ITEM) 0},
+              kFwdNT2NK[] = {CP_FWD_NT2_NK(CP_ITEM) 0}, kWgNT1KT[] = {CP_WG_NT1_KT(CP_ITEM) 0},
+              kWgNT2KT[] = {CP_WG_NT2_KT(CP_ITEM) 0}, kDgPairNK[] = {CP_DG_PAIR_NK(CP_ITEM) 0},
+              kDgVecNK[] = {CP_DG_VEC_NK(CP_ITEM) 0}, kDgScalarNK[] = {CP_DG_SCALAR_NK(CP_ITEM) 0};
+#undef CP_ITEM
+
+static int pick_instance(const int* have, int want) {
+  while (*have && *have < want) ++have;
+  return *have;
+}
+
+static CPPlan make_plan(int H, int W, int C, int KH, int KW, int pad, int N) {
+  CPPlan p{};
+  const CPGeom& g = p.g = make_geom(H, W, C, KH, KW, pad, N);
+  const CPDgrad& d = p.d = make_dgrad(g);
+  const int wn = g.PH * g.PW * N;  // one image's pooled gradient
+  p.fwd_NT = p.wg_NT = cdiv(N, 16);
+  p.fwd_nk = g.Kpad2 / 32;
+  p.wg_KT = cdiv(g.K + 1, 16);  // with the bias column
+  p.dg_kind = d.pair ? CP_DGRAD_PAIR : (N % 8 == 0 ? CP_DGRAD_VEC : CP_DGRAD_SCALAR);
+  p.dg_nk = d.K2pad / 32;
+  p.ok = H >= 1 && W >= 1 && C >= 1 && N >= 1 && g.OH > 0 && g.OW > 0 && !(g.OH & 1) && !(g.OW & 1) &&
+         wn % 4 == 0 &&         // 4-element pooled-gradient chunks (wgrad / dgrad scatter plan)
+         wn <= kStageElems &&   // one image's pooled gradient fits the plan
+         C <= 16 && N <= 32 && KH <= 7 && KW <= 7 &&
+         p.fwd_nk <= 16 &&                    // fwd weight fragments in registers
+         p.wg_KT <= 13 &&                     // wgrad accumulators
+         KH == KW && d.P >= 0 &&              // dConv padding P = KH-1-pad is shared by both axes
+         p.dg_nk <= (d.pair ? 18 : 16) &&     // dgrad weight fragments in registers
+         (size_t)g.img_elems * 2 <= kLdsBudget / 2 && (size_t)d.Hq * d.Wq * d.Nq * 2 <= kLdsBudget / 2 &&
+         (size_t)g.xs_img * 2 <= kLdsBudget / 2;
+  if (!p.ok) return p;
+  const CPWg& q = p.q = make_wg(g);
+  // 4-element vector staging applies when image rows are whole 4-element chunks (and the source is aligned)
+  p.stage_vec = (W * C) % 4 == 0 && H * W * C <= kStageElems && (g.Cp == C || C >= 2);
+  p.fwd_list = g.pair ? kFwdPairNK : (p.fwd_NT == 1 ? kFwdNT1NK : kFwdNT2NK);
+  p.wg_list = p.wg_NT == 1 ? kWgNT1KT : kWgNT2KT;
+  p.dg_list = d.pair ? kDgPairNK : (p.dg_kind == CP_DGRAD_VEC ? kDgVecNK : kDgScalarNK);
+  p.fwd_NK = pick_instance(p.fwd_list, p.fwd_nk);
+  p.wg_KTMAX = pick_instance(p.wg_list, p.wg_KT);
+  p.dg_NKMAX = pick_instance(p.dg_list, p.dg_nk);
+  // caps: the register staging plans (image chunks, pooled chunks per thread)
+  const int img_cap = kStageElems / (H * W * C), pool_cap = kStageElems / wn;
+  p.fwd = CPLaunch{32, cdiv(g.PH * g.PW, g.pair ? 8 : 4) * kTileTabBytes + (size_t)g.xs_img * 2, 0, img_cap};
+  p.wgrad = CPLaunch{64, (size_t)q.cpi * 8 + ((size_t)q.xs_img + q.dc_img) * 2 + 16,
+                     (size_t)4 * p.wg_NT * 16 * p.wg_KT * 16 * 4,  // the reduction buffer
+                     max(min(min(img_cap, pool_cap), 65535 / q.dc_img), 1)};  // scatter offsets are 16 bits
+  p.dgrad = CPLaunch{(size_t)d.K2pad * 4 + 32,
+                     cdiv(d.pair ? H * W / 2 : H * W, 16) * kTileTabBytes + (size_t)d.q_elems * 2, 0, pool_cap};
+  return p;
+}
+
+const CPPlan& convpool_plan(int H, int W, int C, int KH, int KW, int pad, int N) {
+  static std::mutex mu;
+  static std::map<std::array<int, 7>, CPPlan> cache;
+  const std::array<int, 7> key{H, W, C, KH, KW, pad, N};
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(key);
+  if (it == cache.end()) it = cache.emplace(key, make_plan(H, W, C, KH, KW, pad, N)).first;
+  return it->second;
+}
+
+// The kernel of a plan: one switch per launch over its instantiation lists.
+using FwdKern = decltype(&convpool_fwd_kernel<1, 1, kStageChunks, false>);
+using WgKern = decltype(&convpool_wgrad_kernel<1, 2, kStageChunks>);
+using DgKern = decltype(&convpool_dgrad_kernel<1, 4, true, kStageChunks, false>);
+
+#define CP_FWD_P(NK) case NK: return convpool_fwd_kernel<1, NK, kStageChunks, true>;
+#define CP_FWD_1(NK) case 32 + NK: return convpool_fwd_kernel<1, NK, kStageChunks, false>;
+#define CP_FWD_2(NK) case 64 + NK: return convpool_fwd_kernel<2, NK, kStageChunks, false>;
+static FwdKern fwd_kernel(const CPPlan& p) {
+  switch ((p.g.pair ? 0 : p.fwd_NT) * 32 + p.fwd_NK) { CP_FWD_PAIR_NK(CP_FWD_P) CP_FWD_NT1_NK(CP_FWD_1) CP_FWD_NT2_NK(CP_FWD_2) }
+  return nullptr;
+}
+
+#define CP_WG_1(KT) case 32 + KT: return convpool_wgrad_kernel<1, KT, kStageChunks>;
+#define CP_WG_2(KT) case 64 + KT: return convpool_wgrad_kernel<2, KT, kStageChunks>;
+static WgKern wgrad_kernel(const CPPlan& p) {
+  switch (p.wg_NT * 32 + p.wg_KTMAX) { CP_WG_NT1_KT(CP_WG_1) CP_WG_NT2_KT(CP_WG_2) }
+  return nullptr;
+}
+
+// staged: dp and code are read through the 4-element scatter plan (CHM = 0: element by element)
+#define CP_DG(KIND, NK, VEC, PAIR) \
+  case KIND * 32 + NK: return staged ? convpool_dgrad_kernel<1, NK, VEC, kStageChunks, PAIR> : convpool_dgrad_kernel<1, NK, VEC, 0, PAIR>;
+#define CP_DG_P(NK) CP_DG(CP_DGRAD_PAIR, NK, true, true)
+#define CP_DG_V(NK) CP_DG(CP_DGRAD_VEC, NK, true, false)
+#define CP_DG_S(NK) CP_DG(CP_DGRAD_SCALAR, NK, false, false)
+static DgKern dgrad_kernel(const CPPlan& p, bool staged) {
+  switch (p.dg_kind * 32 + p.dg_NKMAX) { CP_DG_PAIR_NK(CP_DG_P) CP_DG_VEC_NK(CP_DG_V) CP_DG_SCALAR_NK(CP_DG_S) }
+  return nullptr;
+}
+
+// Persistent grid: `wg_per_cu` workgroups per CU, each looping over groups of `imgs` images; the
+// per-workgroup setup (tables, weights in registers) is paid once per workgroup, not per group.
+// Persistent-grid sizing from the kernel's real occupancy: blocks/CU allowed by its registers picks
+// the LDS budget per block (-> images per group), then the grid is exactly the resident block count
+// at that LDS size, so every block starts in the first (and only) dispatch round.
+static int blocks_per_cu(const void* kern, size_t lds) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, size_t>, int> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  auto key = std::make_pair(kern, lds);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
+  cache[key] = nb;
+  return nb;
+}
+
+// Tuning overrides (measurement only, csrc/diag.h): cp_wpc caps workgroups per CU, cp_minimgs raises
+// the images per group (fewer, longer-lived workgroups amortise the per-workgroup setup).
+
+static CPSizing size_persistent(const void* kern, int B, size_t fixed, size_t per_img, size_t min_lds, int cap) {
+  static const int wpc_cap = max(1, diag_int("cp_wpc", 8));
+  static const int min_imgs = max(1, diag_int("cp_minimgs", 1));
+  const int wpc = min(wpc_cap, blocks_per_cu(kern, 0));
+  const size_t budget = (160 * 1024) / wpc;
+  int fit = (int)max((size_t)1, (budget > fixed ? budget - fixed : 0) / per_img);
+  fit = max(1, min(fit, min(cap, 32)));
+  CPSizing z{};
+  z.imgs = min(fit, max(min_imgs, cdiv(B, num_cus() * wpc)));
+  z.lds = max(fixed + (size_t)z.imgs * per_img, min_lds);
+  const int nb = blocks_per_cu(kern, z.lds);
+  z.grid = min(num_cus() * nb, cdiv(B, z.imgs));
+  return z;
+}
+
+CPSizing convpool_size_fwd(const CPPlan& p, int B) {
+  const CPLaunch& l = p.fwd;
+  return size_persistent(reinterpret_cast<const void*>(fwd_kernel(p)), B, l.fixed, l.per_img, l.min_lds, l.cap);
+}
+
+CPSizing convpool_size_wgrad(const CPPlan& p, int B, size_t ws_floats) {
+  const CPLaunch& l = p.wgrad;
+  CPSizing z = size_persistent(reinterpret_cast<const void*>(wgrad_kernel(p)), B, l.fixed, l.per_img, l.min_lds, l.cap);
+  const size_t slab = (size_t)p.g.N * (p.g.K + 1);  // one per workgroup
+  while (z.grid * slab > ws_floats && z.grid > 1) z.grid /= 2;
+  if (z.grid * slab > ws_floats || z.lds > 160 * 1024) z.grid = 0;
+  return z;
+}
+
+CPSizing convpool_size_dgrad(const CPPlan& p, int B, bool staged) {
+  const CPLaunch& l = p.dgrad;
+  return size_persistent(reinterpret_cast<const void*>(dgrad_kernel(p, staged)), B, l.fixed, l.per_img, l.min_lds,
+                         staged ? l.cap : 32);
+}
+
+static CPGeom launch_geom(CPGeom g, int B, int imgs) {  // the plan's geometry for one launch
+  g.B = B, g.imgs = imgs, g.stamps = g_cp_stamps;
+  return g;
+}
+
+static int stage_vec(const CPPlan& p, const void* x, int x_u8) {
+  return p.stage_vec && reinterpret_cast<uintptr_t>(x) % (x_u8 ? 4 : 8) == 0;
+}
+
+// pooled gradient / codes as 4-element chunks
+static bool pooled_aligned(const bf16* dp, const uint8_t* code) {
+  return reinterpret_cast<uintptr_t>(dp) % 8 == 0 && reinterpret_cast<uintptr_t>(code) % 4 == 0;
+}
+
+hipError_t convpool_fwd(const CPPlan& p, int B, const void* x, int x_u8, const long long* idx, long long nrows,
+                        float scale, const bf16* w, const float* bias, bf16* out, uint8_t* code, hipStream_t st) {
+  const CPSizing z = convpool_size_fwd(p, B);
+  hipLaunchKernelGGL(fwd_kernel(p), dim3(z.grid), dim3(256), z.lds, st, launch_geom(p.g, B, z.imgs), stage_vec(p, x, x_u8),
+                     x, x_u8, idx, nrows, scale, w, bias, out, code);
+  return hipGetLastError();
+}
+
+hipError_t convpool_wgrad(const CPPlan& p, int B, const void* x, int x_u8, const long long* idx, long long nrows,
+                          float scale, const bf16* dp, const uint8_t* code, float* gw, float* gb, float* workspace,
+                          size_t ws_floats, hipStream_t st, int* deferred) {
+  if (!pooled_aligned(dp, code)) return hipErrorInvalidValue;
+  const CPSizing z = convpool_size_wgrad(p, B, ws_floats);
+  if (z.grid == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(wgrad_kernel(p), dim3(z.grid), dim3(256), z.lds, st, launch_geom(p.g, B, z.imgs), p.q,
+                     stage_vec(p, x, x_u8), x, x_u8, idx, nrows, scale, dp, code, workspace);
   DFA_HIP_CHECK(hipGetLastError());
   if (deferred) {  // the caller batches this slab reduction with others (slab_reduce_multi)
     *deferred = z.grid;
     return hipSuccess;
   }
-  return slab_reduce(workspace, gw, gb, g.N, g.K, Kt, z.grid, 1.f, st);
+  return slab_reduce(workspace, gw, gb, p.g.N, p.g.K, p.g.K + 1, z.grid, 1.f, st);
 }
 
-hipError_t convpool_wgrad(const void* x, int x_u8, const long long* idx, long long nrows, float scale, int B, int H,
-                          int W, int C, int KH, int KW, int pad, int N, const bf16* dp, const uint8_t* code,
-                          float* gw, float* gb, float* workspace, size_t ws_floats, hipStream_t st, int* deferred) {
-  if (!convpool_supported(H, W, C, KH, KW, pad, N)) return hipErrorInvalidValue;
-  CPGeom g = make_geom(B, H, W, C, KH, KW, pad, N);
-  const int KT = cdiv(g.K + 1, 16);
-  const int NT = cdiv(N, 16);
-  const int npool = g.PH * g.PW;
-  if (reinterpret_cast<uintptr_t>(dp) % 8 != 0 || reinterpret_cast<uintptr_t>(code) % 4 != 0)
-    return hipErrorInvalidValue;  // pooled gradient / codes are read as 4-element chunks
-  (void)npool;
-  const bool vec = stage_vec_ok(g, x, x_u8);
-#define CP_WG(NT_, KT_) \
-  return launch_cp_wgrad<NT_, KT_>(g, vec, x, x_u8, idx, nrows, scale, dp, code, gw, gb, workspace, ws_floats, st, deferred)
-  if (NT == 1) {
-    if (KT <= 2) CP_WG(1, 2);
-    if (KT <= 4) CP_WG(1, 4);
-    if (KT <= 10) CP_WG(1, 10);
-    CP_WG(1, 13);
-  }
-  if (KT <= 2) CP_WG(2, 2);
-  if (KT <= 4) CP_WG(2, 4);
-  CP_WG(2, 13);
-#undef CP_WG
-}
-
-template <int NT, int NKMAX, bool VEC, bool PAIR = false>
-static hipError_t launch_cp_dgrad(CPGeom g, const CPDgrad& d, bool plan, const bf16* dp, const uint8_t* code,
-                                  const bf16* wt, bf16* dx, hipStream_t st) {
-  auto kern = plan ? convpool_dgrad_kernel<NT, NKMAX, VEC, kStageChunks, PAIR>
-                   : convpool_dgrad_kernel<NT, NKMAX, VEC, 0, PAIR>;
-  const int tpi = cdiv(PAIR ? g.H * g.W / 2 : g.H * g.W, 16);
-  const int wn = g.PH * g.PW * g.N;
-  const Sizing z = size_persistent(reinterpret_cast<const void*>(kern), g.B, (size_t)d.K2pad * 4 + 32,
-                                   (size_t)tpi * 72 + (size_t)d.q_elems * 2, 0, plan ? kStageChunks * 256 * 4 / wn : 32);
-  g.imgs = z.imgs;
-  hipLaunchKernelGGL(kern, dim3(z.grid), dim3(256), z.lds, st, g, d, dp, code, wt, dx);
+hipError_t convpool_dgrad(const CPPlan& p, int B, const bf16* dp, const uint8_t* code, const bf16* wt, bf16* dx,
+                          hipStream_t st) {
+  const bool staged = pooled_aligned(dp, code);
+  const CPSizing z = convpool_size_dgrad(p, B, staged);
+  hipLaunchKernelGGL(dgrad_kernel(p, staged), dim3(z.grid), dim3(256), z.lds, st, launch_geom(p.g, B, z.imgs), p.d, dp,
+                     code, wt, dx);
   return hipGetLastError();
-}
-
-hipError_t convpool_dgrad(const bf16* dp, const uint8_t* code, const bf16* wt, bf16* dx, int B, int H, int W, int C,
-                          int KH, int KW, int pad, int N, hipStream_t st) {
-  if (!convpool_supported(H, W, C, KH, KW, pad, N)) return hipErrorInvalidValue;
-  CPGeom g = make_geom(B, H, W, C, KH, KW, pad, N);
-  const CPDgrad d = make_dgrad(g);
-  const int wn = g.PH * g.PW * N;
-  const bool plan = wn % 4 == 0 && wn <= kStageChunks * 1024 && reinterpret_cast<uintptr_t>(dp) % 8 == 0 &&
-                    reinterpret_cast<uintptr_t>(code) % 4 == 0;
-  const int nk = d.K2pad / 32;
-  if (cdiv(C, 16) != 1) return hipErrorInvalidValue;
-  if (d.pair) {
-    if (nk <= 4) return launch_cp_dgrad<1, 4, true, true>(g, d, plan, dp, code, wt, dx, st);
-    if (nk <= 8) return launch_cp_dgrad<1, 8, true, true>(g, d, plan, dp, code, wt, dx, st);
-    if (nk <= 12) return launch_cp_dgrad<1, 12, true, true>(g, d, plan, dp, code, wt, dx, st);
-    if (nk <= 15) return launch_cp_dgrad<1, 15, true, true>(g, d, plan, dp, code, wt, dx, st);
-    return launch_cp_dgrad<1, 18, true, true>(g, d, plan, dp, code, wt, dx, st);
-  }
-  if (N % 8 == 0) {
-    if (nk <= 2) return launch_cp_dgrad<1, 2, true>(g, d, plan, dp, code, wt, dx, st);
-    if (nk <= 4) return launch_cp_dgrad<1, 4, true>(g, d, plan, dp, code, wt, dx, st);
-    if (nk <= 5) return launch_cp_dgrad<1, 5, true>(g, d, plan, dp, code, wt, dx, st);
-    if (nk <= 8) return launch_cp_dgrad<1, 8, true>(g, d, plan, dp, code, wt, dx, st);
-    if (nk <= 10) return launch_cp_dgrad<1, 10, true>(g, d, plan, dp, code, wt, dx, st);
-    if (nk <= 13) return launch_cp_dgrad<1, 13, true>(g, d, plan, dp, code, wt, dx, st);
-    return launch_cp_dgrad<1, 16, true>(g, d, plan, dp, code, wt, dx, st);
-  }
-  if (nk <= 4) return launch_cp_dgrad<1, 4, false>(g, d, plan, dp, code, wt, dx, st);
-  if (nk <= 8) return launch_cp_dgrad<1, 8, false>(g, d, plan, dp, code, wt, dx, st);
-  return launch_cp_dgrad<1, 16, false>(g, d, plan, dp, code, wt, dx, st);
 }
 
 }  // namespace dfa

@@ -345,20 +345,74 @@ size_t head_train_lds(const HeadArgs& a);
 hipError_t head_train(HeadArgs a, int phases, hipStream_t st);  // phases: 1 fwd/CE/bwd-data, 2 wgrad
 
 void convpool_set_stamps(void* buf);  // [grid][32] uint64 s_memtime stamps, nullptr = off
-// forward weight layout: [Npad16][Kpad2], column ky*RLp + kx*Cp + c (zero for c >= C) with
-// RLp = round8(KW*Cp); pair layout (N <= 8): RLp = round8((KW+1)*Cp) and rows 8+n = row n shifted by Cp
-void convpool_fwd_layout(int H, int W, int C, int KH, int KW, int pad, int N, int* Cp, int* Kpad2, int* pair);
 void head_set_stamps(void* buf);
-void convpool_dgrad_layout(int H, int W, int C, int KH, int KW, int pad, int N, int* pair, int* K2pad);
-bool convpool_supported(int H, int W, int C, int KH, int KW, int pad, int N);
-hipError_t convpool_fwd(const void* x, int x_u8, const long long* idx, long long nrows, float scale, int B, int H,
-                        int W, int C, int KH, int KW, int pad, int N, const bf16* w, const float* bias, bf16* p,
-                        uint8_t* code, hipStream_t st);
-hipError_t convpool_wgrad(const void* x, int x_u8, const long long* idx, long long nrows, float scale, int B, int H,
-                          int W, int C, int KH, int KW, int pad, int N, const bf16* dp, const uint8_t* code,
-                          float* gw, float* gb, float* workspace, size_t ws_floats, hipStream_t st, int* deferred = nullptr);
-hipError_t convpool_dgrad(const bf16* dp, const uint8_t* code, const bf16* wt, bf16* dx, int B, int H, int W, int C,
-                          int KH, int KW, int pad, int N, hipStream_t st);
+// The kernel arguments of the conv+pool launches, by value (csrc/convpool.hip: forward, weight and data gradient)
+struct CPGeom {
+  int B, H, W, C, KH, KW, pad, N, OH, OW, PH, PW, K, Kpad;
+  int Hp, Wp, img_elems;  // padded input image in LDS
+  int imgs;               // images per workgroup
+  // forward row-segment layout: k = ky*RLp + (kx*C + c); every 8-slot k group is 8 CONSECUTIVE
+  // elements of one padded image row, read with one 16-byte LDS load from one of S shifted copies
+  int Cp;                  // LDS channel stride of the forward image (>= C, zero-filled channels)
+  int RLp, chunks, Kpad2;  // RLp = round8(KW*Cp), chunks = RLp/8, Kpad2 = round32(KH*RLp)
+  int G, S, RowP, ystr, xs_img;  // G = gcd(C,8): copy ci is shifted by ci*G elements, S = 8/G copies
+  int pair;                       // forward pair mode (N <= 8): cols 8-15 = pixel x+1 via shifted weights
+  int wRLp, wKpad2;               // GLOBAL weight layout (row-segment, KW columns): round8(KW*Cp), row length
+  unsigned long long* stamps;     // profiling aid: per-block s_memtime stamps [grid][32] (nullptr = off)
+};
+struct CPWg {
+  int G, R;                          // lane-group split: chunk = R = 4/G rows x 8G cols
+  int OHc, OWc, cpr, cpc, cpi;       // chunk-aligned output extent, chunk rows/cols, chunks per image
+  int Hq, RowQ, ystr, cstr, xs_img;  // X image [C][Hq][KW][RowQ] (+pads)
+  int DWc, dcs, dc_img;              // dConv image [N+1][OHc][DWc] (+pad; plane N stays zero), dc_img = (N+1)*dcs
+  int build_per_img;                 // shifted-copy build tasks per image
+};
+struct CPDgrad {
+  int Hq, Wq, q_elems, P;  // padded dConv image in LDS, P = KH-1-pad
+  int K2, K2pad;           // K2 = KH*KW*N  (pair: KH*(KW+1)*N)
+  int Nq;                  // LDS pixel stride (>= N): 16-byte reads of 8 consecutive pixels hit distinct banks
+  int pair;                // C <= 8, W even: MFMA rows = pixel pairs, columns 8-15 = pixel x+1 (shifted weights)
+};
+
+// The one decision of a fused conv+pool geometry (csrc/convpool.hip convpool_plan): whether the kernels take it,
+// the three argument structs, and per launch the dispatch key, the template instantiation picked for it and
+// the inputs of the persistent-grid sizing.  The launchers switch on it and the bindings read it; the batch
+// enters only at launch (g.B, g.imgs and the sizing, which asks the device for the kernel's occupancy).
+enum CPDgradKind { CP_DGRAD_PAIR, CP_DGRAD_VEC, CP_DGRAD_SCALAR };
+struct CPLaunch {  // LDS bytes per workgroup, per image and at least (wgrad: its reduction buffer); images per group at most
+  size_t fixed, per_img, min_lds;
+  int cap;
+};
+struct CPSizing {  // images per group, workgroups (0: the workspace holds no slab, or the LDS does not fit), LDS bytes
+  int imgs, grid;
+  size_t lds;
+};
+// forward weight layout: [Npad16][g.Kpad2], column ky*RLp + kx*Cp + c (zero for c >= C) with
+// RLp = round8(KW*Cp); pair layout (N <= 8): RLp = round8((KW+1)*Cp) and rows 8+n = row n shifted by Cp
+struct CPPlan {
+  bool ok;                         // the kernels take the geometry; the launch fields are planned only then
+  CPGeom g;                        // B, imgs and stamps are set per launch
+  CPWg q;
+  CPDgrad d;
+  bool stage_vec;                 // images stage as 4-element vectors (if the source pointer is aligned too)
+  int fwd_NT, fwd_nk, fwd_NK;      // forward: channel tiles, k steps, instantiated k steps (pair: g.pair)
+  int wg_NT, wg_KT, wg_KTMAX;      // weight gradient: channel tiles, k tiles with the bias column, instantiated
+  int dg_kind, dg_nk, dg_NKMAX;    // data gradient: CPDgradKind, k steps, instantiated
+  const int *fwd_list, *wg_list, *dg_list;  // the instantiated counts each was picked from (0 ends a list)
+  CPLaunch fwd, wgrad, dgrad;      // dgrad.cap: with the scatter plan (aligned dp / code); 32 without
+};
+const CPPlan& convpool_plan(int H, int W, int C, int KH, int KW, int pad, int N);  // cached; needs no GPU
+// launch sizes for a batch (these ask the device; ``staged``: dp and code are 4-element aligned) and the launchers (p.ok)
+CPSizing convpool_size_fwd(const CPPlan& p, int B);
+CPSizing convpool_size_wgrad(const CPPlan& p, int B, size_t ws_floats);
+CPSizing convpool_size_dgrad(const CPPlan& p, int B, bool staged = true);
+hipError_t convpool_fwd(const CPPlan& p, int B, const void* x, int x_u8, const long long* idx, long long nrows,
+                        float scale, const bf16* w, const float* bias, bf16* out, uint8_t* code, hipStream_t st);
+hipError_t convpool_wgrad(const CPPlan& p, int B, const void* x, int x_u8, const long long* idx, long long nrows,
+                          float scale, const bf16* dp, const uint8_t* code, float* gw, float* gb, float* workspace,
+                          size_t ws_floats, hipStream_t st, int* deferred = nullptr);
+hipError_t convpool_dgrad(const CPPlan& p, int B, const bf16* dp, const uint8_t* code, const bf16* wt, bf16* dx,
+                          hipStream_t st);
 hipError_t slab_reduce(const float* partial, float* gw, float* gb, int N, int K, int Kt, int S, float scale,
                        hipStream_t st);
 constexpr int kMaxSlabSegs = 8;

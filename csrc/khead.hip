@@ -715,23 +715,13 @@ bool khead_supported(int K, int C) {
          khead_lds(K) <= 64 * 1024;
 }
 
-static int khead_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 hipError_t khead_train(KHeadArgs a, hipStream_t st) {
   if (!khead_supported(a.K, a.C) || a.B <= 0 || a.ldt < round_up(a.B, KR) || a.ldw1 < a.K) return hipErrorInvalidValue;
   a.ntiles = cdiv(a.B, KR);
   if (a.ldt < a.ntiles * KR) return hipErrorInvalidValue;
   // persistent grid: every workgroup resident (one per CU at most), a multiple of 8 so the 8 jobs of a row
   // tile are always in flight together
-  const int cap = (g_khead_cap > 0 ? std::min(khead_cus(), g_khead_cap) : khead_cus()) / KCH * KCH;
+  const int cap = (g_khead_cap > 0 ? std::min(num_cus(), g_khead_cap) : num_cus()) / KCH * KCH;
   a.G = min(a.ntiles * KCH, cap);
   if (a.G < KCH) return hipErrorInvalidValue;
   a.stamps = g_khead_stamps;

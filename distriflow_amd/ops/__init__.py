@@ -1067,21 +1067,25 @@ def lenet_red_error(dense_part) -> int:
     return int(dense_part[o:o + 1].view(torch.int32)[0].item())
 
 
+def convpool_plan(H, W, C, KH, KW, pad, N, B=0, ws_floats=0) -> dict:
+    """csrc/kernels.h CPPlan as a dict: ``ok``, the weight layouts, and per launch (``fwd``, ``wgrad``, ``dgrad``)
+    the dispatch ``key``, the ``instance`` picked from the ``instantiated`` list and, with ``B`` on a GPU machine,
+    ``imgs`` per group, ``grid`` and ``lds`` bytes (nothing is launched)."""
+    return _C().convpool_plan(H, W, C, KH, KW, pad, N, B=B, ws_floats=ws_floats)
+
+
 def convpool_supported(H, W, C, KH, KW, pad, N) -> bool:
-    m = native.get(build_if_missing=False)
-    if m is None:
-        return False
-    return bool(m.convpool_supported(H, W, C, KH, KW, pad, N))
+    return native.get(build_if_missing=False) is not None and convpool_plan(H, W, C, KH, KW, pad, N)["ok"]
 
 
 def convpool_fwd_layout(H, W, C, KH, KW, pad, N):
     """(channel stride Cp, row length Kpad2, pair) of the fused conv+pool forward weight layout."""
-    return tuple(_C().convpool_fwd_layout(H, W, C, KH, KW, pad, N))
+    return tuple(convpool_plan(H, W, C, KH, KW, pad, N)[k] for k in ("Cp", "Kpad2", "pair"))
 
 
 def convpool_dgrad_layout(H, W, C, KH, KW, pad, N):
     """(pair, row length K2pad) of the fused conv+pool data-gradient weight layout."""
-    return tuple(_C().convpool_dgrad_layout(H, W, C, KH, KW, pad, N))
+    return tuple(convpool_plan(H, W, C, KH, KW, pad, N)[k] for k in ("dgrad_pair", "K2pad"))
 
 
 def _cp_in(x):

@@ -2,18 +2,17 @@
 
     python scripts/convpool_cases.py
 
-csrc/convpool.hip picks one of about 50 template instantiations per launch from three ladders.  What decides
-is exposed by the bindings without a GPU (``convpool_supported``, ``convpool_fwd_layout``,
-``convpool_dgrad_layout``), so the list is generated, not guessed: over a bounded space of geometries the
-script computes three keys per supported geometry,
+csrc/convpool.hip picks one of about 50 template instantiations per launch from three lists.  What decides
+is the plan of the geometry, which the bindings give without a GPU (``ops.convpool_plan``), so the list is
+generated, not guessed: over a bounded space of geometries the script reads three keys per supported geometry,
 
     fwd    (pair, cdiv(N, 16), Kpad2 / 32)            forward: pair / plain, channel tiles, k steps
     wgrad  (cdiv(N, 16), cdiv(K + 1, 16))             weight gradient: channel tiles, k tiles (bias column)
     dgrad  (pair | vec (N % 8 == 0) | scalar, K2pad / 32)
 
 and greedily picks geometries until every distinct key VALUE is covered (most uncovered keys first, the
-cheapest among equals).  Covering values rather than instantiations means the test does not copy the
-``if (nk <= ...)`` ladders, and it runs instantiations partly filled as well as full.  No GPU needed; the
+cheapest among equals).  Covering values rather than instantiations means the test does not depend on the
+instantiation lists, and it runs instantiations partly filled as well as full.  No GPU needed; the
 extension must be built (as for scripts/conv_plan_fixture.py).
 """
 from __future__ import annotations
@@ -34,19 +33,11 @@ NS = (1, 4, 6, 8, 12, 16, 20, 32)
 BATCH = 3   # odd, more than one workgroup
 
 
-def cdiv(a, b):
-    return -(-a // b)
-
-
 def keys_of(H, W, C, N, k, pad):
     """The three dispatch keys of one geometry, as JSON-friendly lists."""
     from distriflow_amd import ops
-    _, kpad2, pair = ops.convpool_fwd_layout(H, W, C, k, k, pad, N)
-    dpair, k2pad = ops.convpool_dgrad_layout(H, W, C, k, k, pad, N)
-    kind = "pair" if dpair else ("vec" if N % 8 == 0 else "scalar")
-    return {"fwd": [int(bool(pair)), cdiv(N, 16), kpad2 // 32],
-            "wgrad": [cdiv(N, 16), cdiv(k * k * C + 1, 16)],
-            "dgrad": [kind, k2pad // 32]}
+    p = ops.convpool_plan(H, W, C, k, k, pad, N)
+    return {kind: p[kind]["key"] for kind in ("fwd", "wgrad", "dgrad")}
 
 
 def space():

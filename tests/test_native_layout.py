@@ -313,8 +313,8 @@ def test_wgrad_plan_reads_the_diagnostic_switches():
 @needs_ext
 def test_convpool_cases_cover_their_dispatch_keys():
     """tests/golden/convpool_cases.json (scripts/convpool_cases.py), the shape list of the exact conv+pool tests:
-    every case is a supported geometry whose three dispatch keys, recomputed here from the layout queries, are the
-    recorded ones, and together the cases reach every key value the file's header lists as covered by the
+    every case is a supported geometry whose three dispatch keys, read from its plan, are the recorded ones (and
+    each launch's instantiation is one of the instantiated list and holds the key's step count), and together the cases reach every key value the file's header lists as covered by the
     enumerated space: forward (pair, channel tiles, k steps), weight gradient (channel tiles, k tiles with the
     bias column), data gradient (pair | vec | scalar, k steps)."""
     with open(os.path.join(os.path.dirname(GOLDEN), "convpool_cases.json")) as f:
@@ -322,16 +322,67 @@ def test_convpool_cases_cover_their_dispatch_keys():
     seen = {"fwd": set(), "wgrad": set(), "dgrad": set()}
     for c in j["cases"]:
         H, W, C, N, k, pad = (c[n] for n in ("H", "W", "C", "N", "k", "pad"))
-        assert ops.convpool_supported(H, W, C, k, k, pad, N), c
-        _, kpad2, pair = ops.convpool_fwd_layout(H, W, C, k, k, pad, N)
-        dpair, k2pad = ops.convpool_dgrad_layout(H, W, C, k, k, pad, N)
-        keys = {"fwd": (int(bool(pair)), -(-N // 16), kpad2 // 32), "wgrad": (-(-N // 16), -(-(k * k * C + 1) // 16)),
-                "dgrad": ("pair" if dpair else "vec" if N % 8 == 0 else "scalar", k2pad // 32)}
-        for kind, v in keys.items():
+        p = ops.convpool_plan(H, W, C, k, k, pad, N)
+        assert p["ok"] and ops.convpool_supported(H, W, C, k, k, pad, N), c
+        for kind in seen:
+            v = tuple(p[kind]["key"])
             assert v == tuple(c[kind]), (c, kind, v)
+            assert p[kind]["instance"] in p[kind]["instantiated"] and p[kind]["instance"] >= v[-1], (c, kind, p[kind])
             seen[kind].add(v)
     for kind, vals in j["covered"].items():
         assert seen[kind] == {tuple(v) for v in vals}, kind
     # both forward modes, both channel-tile counts everywhere, all three data-gradient kernels
     assert {v[0] for v in seen["fwd"]} == {0, 1} and {v[1] for v in seen["fwd"]} == {1, 2}
     assert {v[0] for v in seen["wgrad"]} == {1, 2} and {v[0] for v in seen["dgrad"]} == {"pair", "vec", "scalar"}
+
+
+# ---------------------------------------------------------------------------- fused conv+pool launch plan
+def _convpool_plan_entries():
+    with open(os.path.join(os.path.dirname(GOLDEN), "convpool_plan.json")) as f:
+        return json.load(f)["entries"]
+
+
+def _targs(kernel, name):
+    """The template arguments of 'name<a,b,...>' (ints, booleans)."""
+    head, _, targs = kernel.partition("<")
+    assert head == name, kernel
+    return [{"true": True, "false": False}.get(v) if v in ("true", "false") else int(v) for v in targs.rstrip(">").split(",")]
+
+
+@needs_ext
+def test_convpool_plan_names_recorded_kernels():
+    """For every entry of tests/golden/convpool_plan.json (scripts/convpool_plan_fixture.py: the cases of
+    convpool_cases.json, LeNet-5's two conv blocks at B in {3, 64, 4096}, the small-workspace weight gradient)
+    the plan names, for all three launches, the kernel instantiation that the commit before the planner launched
+    on the GPU: convpool_fwd_kernel<NT, NK, 4, PAIR>, convpool_wgrad_kernel<NT, KTMAX, 4> and
+    convpool_dgrad_kernel<1, NKMAX, VEC, 4, PAIR> (4: the staged variants, which aligned operands take)."""
+    entries = _convpool_plan_entries()
+    assert len(entries) == 32
+    seen = set()
+    for e in entries:
+        p = ops.convpool_plan(e["H"], e["W"], e["C"], e["k"], e["k"], e["pad"], e["N"])
+        assert p["ok"], e["name"]
+        f, w, d = p["fwd"], p["wgrad"], p["dgrad"]
+        assert _targs(e["launch"]["fwd"][0], "convpool_fwd_kernel") == [f["key"][1], f["instance"], 4, bool(f["key"][0])], e["name"]
+        assert _targs(e["launch"]["wgrad"][0], "convpool_wgrad_kernel") == [w["key"][0], w["instance"], 4], e["name"]
+        kind = d["key"][0]
+        assert _targs(e["launch"]["dgrad"][0], "convpool_dgrad_kernel") == \
+            [1, d["instance"], kind != "scalar", 4, kind == "pair"], e["name"]
+        assert (kind == "pair") == bool(p["dgrad_pair"]) and bool(f["key"][0]) == bool(p["pair"]), e["name"]
+        seen |= {e["launch"][k][0] for k in ("fwd", "wgrad", "dgrad")}
+    assert len(seen) == 35   # of the 48 staged instantiations: what the list keeps reaching
+
+
+@pytest.mark.gpu
+def test_convpool_plan_sizes_recorded_launches():
+    """Nothing is launched: for every entry of the same list, ops.convpool_plan with the entry's batch and
+    weight-gradient workspace gives the workgroups, dynamic LDS bytes and images per group that the commit before
+    the planner launched with (recorded on 256 CUs with no DISTRIFLOW_DIAG switch set; cp_wpc and cp_minimgs
+    change the sizing), the small workspace halving the weight gradient's grid to two slabs."""
+    for e in _convpool_plan_entries():
+        p = ops.convpool_plan(e["H"], e["W"], e["C"], e["k"], e["k"], e["pad"], e["N"], B=e["B"], ws_floats=e["ws"])
+        for kind in ("fwd", "wgrad", "dgrad"):
+            _, grid, block, lds, imgs = e["launch"][kind]
+            assert (p[kind]["grid"], p[kind]["lds"], p[kind]["imgs"], block) == (grid, lds, imgs, 256), (e["name"], kind)
+        if e["name"] == "small_workspace":
+            assert p["wgrad"]["grid"] == 2 and e["ws"] == 2 * e["N"] * (e["k"] * e["k"] * e["C"] + 1)
