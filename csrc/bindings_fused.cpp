@@ -197,8 +197,9 @@ void head_train_py(std::vector<torch::Tensor> w, std::vector<c10::optional<torch
   const int64_t B = x.size(0);
   const int64_t ldt = (B + 31) / 32 * 32;
   TORCH_CHECK(x.numel() == B * K[0], "x must have B*K0 elements");
-  // (the weight-gradient phase alone streams X^T: any K0; the forward phase stages X rows in LDS)
-  TORCH_CHECK(K[0] % 8 == 0 && (K[0] <= 1024 || phases == 2), "head: K0 must be a multiple of 8 and <= 1024");
+  // (the weight-gradient phase alone streams X^T: any K0; the forward phase stages X rows in LDS, 16 bytes at a
+  // time when K0 is a multiple of 8 and element by element otherwise)
+  TORCH_CHECK(K[0] >= 1 && (K[0] <= 1024 || phases == 2), "head: K0 must be in [1, 1024]");
   TORCH_CHECK(N[nl - 1] <= 16, "head: at most 16 classes");
   dfa::HeadArgs a{};
   a.nl = nl;

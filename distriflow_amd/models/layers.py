@@ -292,6 +292,7 @@ class Conv2D(Layer):
         st = self.store
         kn = self.kernel_name
         gb = st.gradient(self.bias_name) if self.use_bias else None
+        dy = dy.reshape((dy.shape[0],) + self.out_shape)  # (a Dense above a Flatten hands down [B][OH * OW * N])
         ops.conv_wgrad(dy, self.x, st.grad_matrix(kn), gb, self.ws.wgrad, *self.geom)
 
     def backward_data(self, dy, residual=None, residual_mask=None, dx_mask=None, bn_acc: Optional[list] = None):
@@ -310,6 +311,7 @@ class Conv2D(Layer):
             if len(bn_acc) == 2:
                 b1 = bn_acc[1]
                 bacc.update(acc2=b1.acc_b, x2=b1.x, mean2=b1.mean, invstd2=b1.invstd)
+        dy = dy.reshape((dy.shape[0],) + self.out_shape)
         ops.conv_dgrad(dy, st.weight(kn), st.weight_t(kn), self.dx, *self.geom, mask=mask, residual=residual,
                        residual_mask=residual_mask, bacc=bacc)
         if bacc is not None:

@@ -311,3 +311,175 @@ def split_replicas(total, nrep, sentinel):
     f[-1] = 1 - f[:-1].sum(0)
     buf[:nrep] = f * total
     return buf, buf[:nrep]
+
+
+# ------------------------------------------------------------------- dense heads with a saturated softmax
+# A Dense chain + softmax cross-entropy is exact on integers once the softmax saturates: the last layer has
+# weights in 2048 * {-1, 0, 1} and the bias 128 * perm(16)[:C], so the logits of a row are congruent to distinct
+# multiples of 128 modulo 2048: pairwise >= 128 apart, the maximum unique.  exp(z - max) for z - max <= -104
+# is below 2^-150, exactly 0 in fp32, so sum = 1, 1 / sum = 1, log(sum) = 0 and the kernel must produce exactly
+# dZ_last = grad_scale * (onehot(argmax) - onehot(y)), row loss = max - z_y, correct = [argmax == y].
+def _r32(n):
+    return _r(n, 32)
+
+
+def head_ints(g, B, dims, with_idx=False, bias=True):
+    """Integer data of the head ``dims[0] -> ... -> dims[-1]`` (C = dims[-1] <= 16 classes): x in [-1, 2], hidden
+    weights in {-1, 0, 1} with about 48 non-zeros per row, hidden bias in [-3, 3], dense last-layer weights in
+    2048 * {-1, 0, 1} with the bias 128 * perm(16)[:C].  ``with_idx``: the labels are a table of 3 B rows read
+    through an index vector.  ``bias=False``: no bias anywhere; the distinct multiples of 128 then reach the
+    logits through a unit that is 1 in every row (x[:, 0] = 1, row 0 of each hidden layer passes it on, column 0
+    of the last layer holds 128 * perm(16)[:C])."""
+    nl, C = len(dims) - 1, dims[-1]
+    x = ints(g, (B, dims[0]), -1, 2)
+    W, b = [], []
+    for l in range(nl):
+        K, N = dims[l], dims[l + 1]
+        if l < nl - 1:
+            W.append(sparse_ints(g, (N, K), -1, 1, weight_density(K, 48)))
+            b.append(ints(g, (N,), -3, 3))
+        else:
+            W.append(2048.0 * ints(g, (N, K), -1, 1))
+            b.append(128.0 * torch.randperm(16, generator=g)[:C].double())
+    if not bias:
+        x[:, 0] = 1
+        for l in range(nl - 1):
+            W[l][0] = 0
+            W[l][0, 0] = 1
+        W[-1][:, 0] = b[-1]
+        b = [None] * nl
+    table = torch.randint(0, C, (3 * B if with_idx else B,), generator=g, dtype=torch.int32)
+    idx = torch.randperm(3 * B, generator=g)[:B] if with_idx else None
+    return {"dims": tuple(dims), "x": x, "W": W, "b": b, "labels": table, "idx": idx,
+            "y": (table[idx] if with_idx else table).long()}
+
+
+def head_ref(d, grad_scale, drop=None, dh_scale=1.0, x_relu=False, dx_scale=1.0):
+    """fp64 reference of everything a fused head kernel writes for the data ``d`` of :func:`head_ints`, with the
+    softmax saturated (see above; :func:`assert_exact_head` asserts that it is).
+
+    ``drop = (p, seed, step)``: a dropout folded after the LAST hidden layer, mask
+    ``reference.dropout_mask(B * N, p, seed ^ (step * 0x9E3779B1))`` over [B][N], forward * 1 / (1 - p), backward
+    * ``dh_scale``.  ``x_relu``: relu' of the input on dx.  ``dx_scale`` multiplies dx.
+
+    -> dict: acts (x and every hidden activation), pre_drop, logits, dz (per layer), dx, gw, gb, gw_terms,
+    logit_terms, loss_rows, loss_part [ceil(B/16)][2], stats [2], argmax."""
+    from distriflow_amd.ops import reference
+
+    x, W, b, y = d["x"], d["W"], d["b"], d["y"]
+    nl, B, C = len(W), x.shape[0], W[-1].shape[0]
+    acts, pre_drop, keep = [x], None, None
+    for l in range(nl - 1):
+        h = (acts[-1] @ W[l].t() + (b[l] if b[l] is not None else 0)).relu()
+        if drop is not None and l == nl - 2:
+            p, seed, step = drop
+            keep = reference.dropout_mask(B * h.shape[1], p, seed ^ (step * 0x9E3779B1)).double().view(B, -1)
+            pre_drop, h = h, h * keep / (1.0 - p)
+        acts.append(h)
+    logits = acts[-1] @ W[-1].t() + (b[-1] if b[-1] is not None else 0)
+    logit_terms = acts[-1].abs() @ W[-1].abs().t() + (b[-1].abs() if b[-1] is not None else 0)
+    mx, am = window_argmax(logits)          # the strict-> scan: first maximum
+    zy = logits.gather(1, y[:, None])[:, 0]
+    loss_rows, correct = mx - zy, (am == y).double()
+    dz = [None] * nl
+    dz[-1] = grad_scale * (F.one_hot(am, C).double() - F.one_hot(y, C).double())
+    for l in range(nl - 1, 0, -1):
+        dz[l - 1] = (dz[l] @ W[l]) * (acts[l] > 0) * (dh_scale if (keep is not None and l == nl - 1) else 1.0)
+    dx = dz[0] @ W[0]
+    if x_relu:
+        dx = dx * (x > 0)
+    dx = dx * dx_scale
+    nb = (B + 15) // 16
+    part = torch.zeros(nb * 16, 2, dtype=torch.float64)
+    part[:B, 0], part[:B, 1] = loss_rows, correct
+    part = part.view(nb, 16, 2).sum(1)
+    return {"acts": acts, "pre_drop": pre_drop, "logits": logits, "logit_terms": logit_terms, "argmax": am,
+            "dz": dz, "dx": dx, "gw": [dz[l].t() @ acts[l] for l in range(nl)], "gb": [dz[l].sum(0) for l in range(nl)],
+            "gw_terms": [dz[l].abs().t() @ acts[l].abs() for l in range(nl)], "loss_rows": loss_rows,
+            "loss_terms": mx.abs() + zy.abs(), "loss_part": part, "stats": part.sum(0)}
+
+
+def _unit(t):
+    """The largest power of two 2^-k (0 <= k <= 24) of which every entry of t is a multiple."""
+    for k in range(25):
+        if torch.equal(t * 2.0 ** k, (t * 2.0 ** k).round()):
+            return 2.0 ** -k
+    raise AssertionError("not a dyadic fraction with at most 24 fractional bits")
+
+
+def assert_exact_head(ref):
+    """The conditions under which a head kernel must reproduce ``ref`` (:func:`head_ref`) bit for bit.  C = 1 is the
+    one case whose gradients are all exactly zero (argmax = y = 0); it is held to that instead of to a density."""
+    C = ref["logits"].shape[1]
+    # activations: integers <= 256 (<= 128 before a dropout's * 2)
+    for h in ref["acts"]:
+        assert_exact_output(h)
+    if ref["pre_drop"] is not None:
+        assert float(ref["pre_drop"].abs().max()) <= 128, "pre-dropout activation above 128"
+    # saturation: the top-2 gap of every row
+    if C > 1:
+        top = ref["logits"].topk(2, dim=1).values
+        gap = float((top[:, 0] - top[:, 1]).min())
+        assert gap >= 104, f"top-2 logit gap {gap} < 104: the softmax does not saturate"
+    # logits and loss sums: multiples of 128, exact in fp32 while (sum |terms|) / 128 < 2^24
+    assert torch.equal(ref["logits"] / 128, (ref["logits"] / 128).round()), "logits are not multiples of 128"
+    assert float(ref["logit_terms"].max()) / 128 < FP32_INT_MAX, "logit terms too large"
+    assert float(ref["loss_terms"].sum()) / 128 < FP32_INT_MAX, "loss terms too large"
+    # weight / bias gradients: fp32 sums of multiples of a power of two, sum |dz h| / unit < 2^24 per element
+    for l, (dz, terms) in enumerate(zip(ref["dz"], ref["gw_terms"])):
+        u = min(_unit(dz), 1.0)
+        assert float(terms.max()) < FP32_INT_MAX, f"layer {l}: sum |dz h| not below 2^24"
+        assert float(terms.max()) / u < FP32_INT_MAX, f"layer {l}: sum |dz h| / {u} not below 2^24"
+        assert float(dz.abs().sum(0).max()) / u < FP32_INT_MAX, f"layer {l}: sum |dz| / {u} not below 2^24"
+    # every bf16 output is a bf16 value
+    for name, t in [("dx", ref["dx"])] + [(f"dz{l}", t) for l, t in enumerate(ref["dz"])]:
+        assert torch.equal(t.to(torch.bfloat16).double(), t), f"{name} is not representable in bf16"
+    # the comparison sees something: >= 5 % of each gradient non-zero (C = 1: all exactly zero)
+    for name, t in [("dx", ref["dx"])] + [(f"gw{l}", t) for l, t in enumerate(ref["gw"])] + \
+                   [(f"gb{l}", t) for l, t in enumerate(ref["gb"])]:
+        nz = float((t != 0).double().mean())
+        if C == 1:
+            assert nz == 0, f"{name}: a one-class head has zero gradients"
+        else:
+            assert nz >= 0.05, f"{name}: only {100 * nz:.1f} % non-zero"
+
+
+# The shapes of tests/test_head_exact_gpu.py, each the smallest that reaches its path; tests/test_exact_util.py
+# asserts the conditions above for every one of them without a GPU.
+KHEAD_N1 = 128
+HEAD_GRAD_SCALE = 2.0 ** -11           # dZ_last = +-2^-11, dZ_last W_last an integer in [-2, 2]
+HEAD_DROP = (0.5, 0x5EED, 5)           # (p, seed, step)
+# (B, K, C, dropout, labels through idx)
+KHEAD_CASES = [
+    (1, 256, 1, False, False),         # one row, KS = 1 (waves 2, 3 idle in the dP phase), C = 1: zero gradients
+    (33, 256, 10, False, False),       # a second row tile with a single valid row
+    (70, 512, 10, True, True),         # dropout 0.5, dh_scale 2, labels through idx
+    (100, 1536, 16, False, False),     # KS = 6 = PF exactly, C = 16
+    (47, 1792, 3, True, False),        # KS = 7 = PF + 1
+    (96, 3072, 10, False, False),      # KS = 12 = 2 PF, B a multiple of 32
+    (40, 3328, 10, False, False),      # KS = 13: the second trip of the ping-pong loop
+    (200, 4608, 10, True, True),       # the <18> instantiation
+    (40, 5376, 10, True, False),       # the largest supported K (KS = 21)
+    (1040, 256, 10, False, False),     # 264 jobs > 256 workgroups; 33 batch steps in the weight gradient
+]
+# (B, dims, labels through idx, x_relu, dx_scale)
+MLPHEAD_CASES = [
+    (50, (64, 48, 32, 10), False, False, 1.0),     # the last block has 2 rows
+    (19, (400, 120, 84, 10), True, True, 1.0),     # the LeNet-5 head
+    (96, (784, 10), False, False, 1.0),            # a single layer
+    (33, (30, 16), False, False, 1.0),             # D0 % 8 != 0: the scalar staging path; C = 16
+    (300, (200, 100, 10), False, False, 0.5),      # 19 blocks: the loss reduction spans lane rounds
+    (16, (256, 128, 1), False, False, 1.0),        # C = 1
+]
+
+
+def khead_case(B, K, C, drop, with_idx, bias=True, dp_mask=True, seed=0):
+    """(data, reference) of a khead case: Dense(K -> 128, ReLU) [-> Dropout 0.5] -> Dense(C), dP scaled by 0.5."""
+    d = head_ints(gen(1000 * seed + B + K + C), B, (K, KHEAD_N1, C), with_idx, bias)
+    ref = head_ref(d, HEAD_GRAD_SCALE, HEAD_DROP if drop else None, 2.0 if drop else 1.0, dp_mask, 0.5)
+    return d, ref
+
+
+def mlphead_case(B, dims, with_idx, x_relu, dx_scale, seed=0):
+    d = head_ints(gen(1000 * seed + B + sum(dims)), B, dims, with_idx)
+    return d, head_ref(d, HEAD_GRAD_SCALE, x_relu=x_relu, dx_scale=dx_scale)

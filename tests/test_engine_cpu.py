@@ -59,6 +59,25 @@ def test_grads_match_autograd(name, fuse):
         torch.testing.assert_close(net.store.gradient(s.name), params[s.name].grad, rtol=1e-4, atol=1e-5)
 
 
+def test_conv_below_flatten_grads_match_autograd():
+    """A Conv2D directly below Flatten -> Dense: the Dense hands its input gradient down as [B][OH * OW * N]."""
+    from distriflow_amd.models.layers import Flatten
+
+    layers = [Conv2D(8, 3, 1, "same", "relu", name="conv2d_1"), Conv2D(4, 3, 1, "valid", "relu", name="conv2d_2"),
+              Flatten(name="flatten_1"), Dense(16, "relu", name="dense_1"), Dense(10, "softmax", name="dense_2")]
+    net = Net(layers, (8, 8, 2), device="cpu", seed=1)
+    torch.manual_seed(0)
+    x = torch.rand(6, 8, 8, 2)
+    y = torch.randint(0, 10, (6,))
+    st = net.compute_gradients(x, y)
+    params = {s.name: net.store[s.name].detach().clone().requires_grad_(True) for s in net.store.specs}
+    loss = F.cross_entropy(torch_forward(net, x, params), y, reduction="mean")
+    loss.backward()
+    assert abs(float(st[0]) / 6 - loss.item()) < 1e-4
+    for s in net.store.specs:
+        torch.testing.assert_close(net.store.gradient(s.name), params[s.name].grad, rtol=1e-4, atol=1e-5)
+
+
 def test_resnet_block_grads_match_autograd():
     layers = [Conv2D(8, 3, 1, 1, use_bias=False, name="stem"), BatchNorm(relu=True, name="bn"),
               ResidualBlock(8, 1, name="b1"), ResidualBlock(16, 2, name="b2"), GlobalAveragePooling2D(name="gap"),

@@ -1,9 +1,12 @@
-"""The max-pool reference helpers of tests/exact_util.py themselves (CPU): the tie rule they encode, the two code
-conventions, and agreement with torch's own pooling where no tie is possible."""
+"""The reference helpers of tests/exact_util.py themselves (CPU): the tie rule the max-pool helpers encode, the two
+code conventions, agreement with torch's own pooling where no tie is possible; the saturated-head reference against
+fp64 autograd of the same chain with the real softmax, and its exactness conditions at every shape the GPU tests use."""
+import pytest
 import torch
 
 import exact_util as xu
 from distriflow_amd import ops
+from distriflow_amd.ops import reference as ref
 
 
 def test_window_argmax_takes_the_first_maximum():
@@ -48,3 +51,69 @@ def test_pool_max_ref_agrees_with_torch_without_ties_and_sums_overlaps():
     dx = xu.pool_max_bwd_ref(torch.zeros(1, 4, 4, 1), torch.ones(1, 4, 4, 1), geom, False)
     assert dx[0, :, :, 0].tolist() == [[4, 2, 2, 0], [2, 1, 1, 0], [2, 1, 1, 0], [0, 0, 0, 0]]
     assert float(xu.pool_max_bwd_ref(torch.zeros(1, 4, 4, 1), torch.ones(1, 4, 4, 1), geom, True).abs().sum()) == 0
+
+
+# ------------------------------------------------------------------------------- the saturated-head reference
+def _autograd_head(d, grad_scale, drop, x_relu, dx_scale):
+    """fp64 autograd of the same chain with the REAL softmax (F.cross_entropy)."""
+    x = d["x"].clone().requires_grad_(True)
+    W = [w.clone().requires_grad_(True) for w in d["W"]]
+    b = [None if v is None else v.clone().requires_grad_(True) for v in d["b"]]
+    h, nl = x, len(W)
+    for l in range(nl):
+        h = h @ W[l].t() + (b[l] if b[l] is not None else 0)
+        if l < nl - 1:
+            h = h.relu()
+            if drop is not None and l == nl - 2:
+                keep = ref.dropout_mask(h.numel(), drop[0], drop[1] ^ (drop[2] * 0x9E3779B1)).double().view_as(h)
+                h = h * keep / (1 - drop[0])
+    loss = torch.nn.functional.cross_entropy(h, d["y"], reduction="sum")
+    (loss * grad_scale).backward()
+    dx = x.grad * (d["x"] > 0) if x_relu else x.grad
+    return h.detach(), loss.detach(), dx * dx_scale, [w.grad for w in W], [None if v is None else v.grad for v in b]
+
+
+def _check_ref_against_autograd(d, r, drop, x_relu, dx_scale):
+    xu.assert_exact_head(r)
+    logits, loss, dx, gw, gb = _autograd_head(d, xu.HEAD_GRAD_SCALE, drop, x_relu, dx_scale)
+    tight = dict(rtol=0, atol=1e-40)   # the two differ by the fp64 exp tail alone (<= e^-104)
+    assert torch.equal(r["logits"], logits)
+    torch.testing.assert_close(r["stats"][0], loss, **tight)
+    torch.testing.assert_close(r["dx"], dx, **tight)
+    for l in range(len(gw)):
+        torch.testing.assert_close(r["gw"][l], gw[l], **tight)
+        if gb[l] is not None:
+            torch.testing.assert_close(r["gb"][l], gb[l], **tight)
+    assert float(r["stats"][1]) == float((logits.argmax(1) == d["y"]).sum())
+    assert torch.equal(r["loss_part"].sum(0), r["stats"])
+
+
+@pytest.mark.parametrize("case", xu.KHEAD_CASES, ids=lambda c: "-".join(str(int(v)) for v in c))
+def test_head_ref_matches_autograd_khead_cases(case):
+    d, r = xu.khead_case(*case)
+    _check_ref_against_autograd(d, r, xu.HEAD_DROP if case[3] else None, True, 0.5)
+    assert r["dx"].shape == (case[0], case[1]) and len(r["loss_part"]) == (case[0] + 15) // 16
+
+
+@pytest.mark.parametrize("case", xu.MLPHEAD_CASES, ids=lambda c: f"{c[0]}-" + "x".join(map(str, c[1])))
+def test_head_ref_matches_autograd_mlphead_cases(case):
+    d, r = xu.mlphead_case(*case)
+    _check_ref_against_autograd(d, r, None, case[3], case[4])
+
+
+def test_head_ref_without_bias_and_mask():
+    d, r = xu.khead_case(40, 512, 10, False, False, bias=False, dp_mask=False)
+    assert all(v is None for v in d["b"])
+    _check_ref_against_autograd(d, r, None, False, 0.5)
+
+
+def test_head_ref_takes_the_first_maximum_and_its_conditions_bite():
+    d, r = xu.khead_case(33, 256, 10, False, False)
+    assert torch.equal(r["argmax"], r["logits"].argmax(1))  # unique maxima: any rule agrees
+    bad = dict(r, logits=r["logits"].clone())
+    bad["logits"][5] = 128.0 * torch.tensor([3., 3, 0, 0, 0, 0, 0, 0, 0, 0])
+    with pytest.raises(AssertionError, match="gap"):
+        xu.assert_exact_head(bad)
+    bad = dict(r, dx=r["dx"] + 1.0 / 1024)
+    with pytest.raises(AssertionError, match="bf16"):
+        xu.assert_exact_head(bad)

@@ -54,6 +54,54 @@ def test_khead_matches_per_layer_head(monkeypatch, B):
         assert _rel(gf, gp) < 2e-2, (s.name, _rel(gf, gp))
 
 
+def _small_pair(monkeypatch, seed=3):
+    """Conv2D(8, 3x3, same, relu) on 8x8x2 -> Flatten (512) -> Dense 128 relu -> Dropout 0.5 -> Dense 10 softmax:
+    K = 512 plans the head kernel's generic (run-time loop) instantiation."""
+    from distriflow_amd.models.layers import Conv2D, Dense, Dropout, Flatten
+    from distriflow_amd.models.net import Net
+
+    def make():
+        layers = [Conv2D(8, 3, 1, "same", "relu", name="conv2d_1"), Flatten(name="flatten_1"),
+                  Dense(128, "relu", name="dense_1"), Dropout(0.5, name="dropout_1"),
+                  Dense(10, "softmax", name="dense_2")]
+        return Net(layers, (8, 8, 2), device=dev, name="small_khead", seed=seed)
+
+    f = make()
+    assert f.khead and f.exec_layers[-2].in_features == 512
+    monkeypatch.setenv("DISTRIFLOW_DIAG", "khead_fused=0")
+    p = make()
+    monkeypatch.delenv("DISTRIFLOW_DIAG")
+    assert not p.khead
+    p.store.set_flat(f.store.master.clone())
+    return f, p
+
+
+def test_khead_generic_kernel_matches_per_layer_head(monkeypatch):
+    """The same criteria as test_khead_matches_per_layer_head, on a head whose K is not the reference CNN's."""
+    B = 40
+    f, p = _small_pair(monkeypatch)
+    g = torch.Generator().manual_seed(9)
+    x = torch.rand(B, 8, 8, 2, generator=g).to(torch.bfloat16).to(dev)
+    y = torch.randint(0, 10, (B,), generator=g, dtype=torch.int32).to(dev)
+    f.step_dev.fill_(5)
+    p.step_dev.fill_(5)
+    sf = f.compute_gradients(x, y).clone()
+    sp = p.compute_gradients(x, y).clone()
+    torch.cuda.synchronize()
+    assert ops.khead_error(f.khead_ws, B) == 0
+    assert torch.equal(f.exec_layers[0].out, p.exec_layers[0].out)
+    assert abs(float(sf[0]) - float(sp[0])) <= 1e-3 * abs(float(sp[0])) + 1e-3, (sf, sp)
+    assert abs(float(sf[1]) - float(sp[1])) <= max(2.0, 0.01 * B), (sf, sp)
+    lf, lp = f.exec_layers[-1].out, p.exec_layers[-1].out
+    assert _rel(lf, lp) < 1e-2, _rel(lf, lp)
+    d1 = f.exec_layers[-2]
+    assert _rel(d1.dx, p.exec_layers[-2].dx) < 2e-2, _rel(d1.dx, p.exec_layers[-2].dx)
+    for s in f.store.specs:
+        gf, gp = f.store.gradient(s.name), p.store.gradient(s.name)
+        assert torch.isfinite(gf).all(), s.name
+        assert _rel(gf, gp) < 2e-2, (s.name, _rel(gf, gp))
+
+
 def test_khead_repeatable_across_launches(monkeypatch):
     """The flags compare against a per-launch tag: back-to-back steps on the same inputs give identical
     results (no stale flag, no lost ticket), batch not a multiple of the 32-row tile."""
