@@ -585,7 +585,7 @@ struct LeNetArgs {
   int prep;                   // 1: launch the fragment prep kernel first (0: the optimizer rebuilt them)
   const void* frag;           // [298][64] x 8 bf16 conv + dense weight fragments of this step (csrc/lenet_frag.h)
   const unsigned char* ftab;  // [98][2][16] conv2 dgrad gather table (lenet_tables)
-  const unsigned short* pxtab;  // [832] conv2 output row -> pool1 pixel (lenet_tables)
+  const unsigned short* pxtab;  // [832] physical dC2 row -> pool1 pixel, [104] per-image row table (lenet_tables)
   unsigned long long* stamps; // diagnostic phase clocks [grid][16] (lenet_set_stamps), or null
   int B, ldt;
   float grad_scale;

@@ -26,10 +26,16 @@
 //     dense 400-120-84-10 + softmax-CE + backward     MFMA, weight fragments streamed from L2 (one
 //                          lane-linear 1 KB load per fragment: 8 cache-line lookups, where a row-major
 //                          matrix cost one per 16-byte piece)
+//     conv2 output gradient dC2                       [8 images][104 rows][16] bf16, position (oy, ox) at
+//                          row place[t] of its image's block: bank class ((ox >> 1) + 7 oy + 4 (ox & 1)) mod 8
+//                          (tables: distriflow_amd.ops.lenet_conv2_tables; priced by scripts/lds_sim.py)
 //     conv2 weight gradient                           ds_read_b64_tr_b16 transposed reads of both
-//                          operands from their natural NHWC images; bias = a column of ones; the
-//                          waves split it as 2 K-halves x 4 column groups (one fp32 add through LDS)
-//     conv2 data gradient                             pair-banded MFMA (two output columns per row)
+//                          operands: dC2 rows in physical order (conflict-free), their pool-1 pixels from a
+//                          row-to-pixel table; bias = a column of ones; the waves split it as 2 K-halves x
+//                          4 column groups (one fp32 add through LDS)
+//     conv2 data gradient                             pair-banded MFMA (two output columns per row); the
+//                          rows a ds_read_b128 gathers together are distinct mod 8, a lane without a tap
+//                          reads the row of an 8-row zero block that has its position's class
 //     conv1 weight gradient                           A fragments unpooled in registers from the pool
 //                          gradient + argmax codes, B = 4 dword reads of the (shifted) input image
 //   and writes per-workgroup conv gradient partials plus transposed dense activations/gradients (as
@@ -66,7 +72,7 @@ constexpr int OFF_C1 = OFF_P1 + IMG * 196 * 16;     // [8][196] u32 pool1 codes 
 constexpr int DC2_RS = 104;
 constexpr int NM = IMG * DC2_RS;                    // 832 padded conv2 output rows
 constexpr int OFF_K = OFF_C1 + IMG * 196 * 4;       // 32 B ones (bf16)
-constexpr int OFF_PX = OFF_K + 32;                  // conv2 output row -> P1 pixel [832] u16 (host-built)
+constexpr int OFF_PX = OFF_K + 32;                  // physical dC2 row -> P1 pixel [832] u16 (host-built)
 constexpr int OFF_FT = OFF_PX + NM * 2;             // conv2 dgrad table [98][2][16] u8 (host-built)
 constexpr int OFF_W = OFF_FT + 98 * 2 * 16;         // f32: b1 [6], b2 [16], then 8 int labels
 constexpr int OFF_KZ = OFF_W + 128;                 // 32 B zeros (phase G's zero columns)
@@ -92,11 +98,15 @@ constexpr int OFF_DC2 = OFF_U;                      // [832][16] bf16 conv2 outp
 constexpr int U_DC2 = NM * 16 * 2;
 constexpr int OFF_RED = OFF_XS1 + XS_ELEMS * 2;     // [4][16][32] f32 cross-wave conv1 wgrad sums
 constexpr int U_G = 32 + XS_ELEMS * 2 + 4 * 16 * 32 * 4;
-// conv2 output-gradient row t of an image is stored at row dc2_swz(t) of the image's 104-row block: the
-// gathered A-operand reads of phase F then spread over the banks (scripts/lds_sim.py), and phase F's
-// table holds the swizzled row itself (no per-step swizzle arithmetic).  The padding rows hold zeros:
-// phase F's "no tap" entries read one (dc2_swz(100) = 96).
-__device__ __forceinline__ int dc2_swz(int t) { return t ^ ((t >> 3) & 7); }
+// The conv2 output gradient of position (oy, ox) of an image (window-order row t) is stored at physical row
+// place[t] of the image's 104-row block, a row of bank class ((ox >> 1) + 7 oy + 4 (ox & 1)) mod 8 (a row is
+// 32 bytes, 8 rows span the 64 banks, and a block is 13 x 8 rows: the class of a row does not depend on the
+// image).  The 16 pixel pairs of a phase F tile gather, for one tap, positions whose (ox >> 1) rises by one
+// from lane to lane and restarts one oy further: consecutive classes, so the 8 lanes that a ds_read_b128
+// serves together with the same 16-byte half read rows that are distinct mod 8 (scripts/lds_sim.py).  A lane
+// without a tap (a position outside the 10x10 map) reads the row of the zero block (OFF_ZB) that has the
+// class its position would have had.  Phase E reads the physical rows in order (the K order of its GEMM is
+// free) and takes their pixels from PX; the 4 padding rows of a block hold zeros.
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 // conv1 / conv2 B fragments (FR_C1, FR_C2: 22 x 1 KB, lane-linear), loaded once per workgroup in phase 0
 // and handed to the waves through LDS.  The conv1 image lies under Xs1: every wave has read it before
@@ -113,7 +123,14 @@ static_assert(OFF_FC1 + NFP1 * 16 <= OFF_XS1 + (XS_ELEMS / 8 - 1) * 16, "build_s
 // bias load never waits behind the weight prefetches issued before it
 constexpr int OFF_DB = OFF_U + (cmax(cmax(cmax(U_DENSE, U_DC2), U_G), U_FC2) + 15) / 16 * 16;
 constexpr int OFF_ST = OFF_DB + 864;                // u64 [16] diagnostic phase clocks (LN_STAMP)
-constexpr int LDS_BYTES = OFF_ST + 128;
+// per-image row table [104] u16 (host-built): entry t = pool1 pixel of window-order row t inside the image
+// (low byte: phase B) | place[t] << 8 (phase D)
+constexpr int OFF_RT = OFF_ST + 128;
+// 8 zero rows of 32 bytes for phase F's "no tap" lanes, row k of bank class k: a multiple of 256 bytes from
+// dC2.  Outside the union: written in phase 0 and never again.
+constexpr int OFF_ZB = OFF_DC2 + (OFF_RT + DC2_RS * 2 - OFF_DC2 + 255) / 256 * 256;
+constexpr int LDS_BYTES = OFF_ZB + 256;
+static_assert(OFF_RT % 16 == 0 && (OFF_ZB - OFF_DC2) % 256 == 0 && (DC2_RS * 32) % 256 == 0, "dC2 row classes");
 static_assert(OFF_U == OFF_C1 + IMG * 196 * 4 + 128 + 98 * 2 * 16 + 800 * 2 + 128 && OFF_U % 16 == 0 && OFF_KZ % 16 == 0 && OFF_H1 % 16 == 0 && OFF_ZR % 16 == 0 && OFF_C2 % 16 == 0 && OFF_RED % 16 == 0 && OFF_DB % 16 == 0 && OFF_ST % 16 == 0 &&
                   OFF_PX % 16 == 0 && OFF_W % 16 == 0 && OFF_FC1 % 16 == 0 && OFF_FC2 % 16 == 0,
               "LDS carve must stay 16-byte aligned");
@@ -402,6 +419,9 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   bf16* KO = reinterpret_cast<bf16*>(smem + OFF_K);       // 16 ones
   unsigned char* FT = reinterpret_cast<unsigned char*>(smem + OFF_FT);
   unsigned short* PX = reinterpret_cast<unsigned short*>(smem + OFF_PX);
+  unsigned short* RT = reinterpret_cast<unsigned short*>(smem + OFF_RT);
+  constexpr int NPXV = (NM + DC2_RS) / 8;  // 16-byte pieces of a.pxtab: PX, then RT
+  static_assert((NM + DC2_RS) % 8 == 0 && NM % 8 == 0, "pxtab pieces");
   float* WS = reinterpret_cast<float*>(smem + OFF_W);       // b1[6] b2[16]
   bf16* H0 = reinterpret_cast<bf16*>(smem + OFF_H0);
   bf16* H1 = reinterpret_cast<bf16*>(smem + OFF_H1);
@@ -446,8 +466,8 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   if (lload) lsrc = a.idx ? a.idx[r0 + tid - 256] : (long long)(r0 + tid - 256);
   uint4 tabv = {0u, 0u, 0u, 0u};
   if (tid < 98 * 2) tabv = reinterpret_cast<const uint4*>(a.ftab)[tid];
-  else if (tid >= 264 && tid < 264 + NM / 8) tabv = reinterpret_cast<const uint4*>(a.pxtab)[tid - 264];
-  static_assert(98 * 2 <= 256 && 264 + NM / 8 <= 448 && 448 + 22 <= NT, "phase 0 staging thread ranges");
+  else if (tid >= 264 && tid < 264 + NPXV) tabv = reinterpret_cast<const uint4*>(a.pxtab)[tid - 264];
+  static_assert(98 * 2 <= 256 && 264 + NPXV <= 448 && 448 + 22 <= NT, "phase 0 staging thread ranges");
   float biasv = 0.f, dbv = 0.f;
   if (tid >= 448 && tid < 448 + 22) biasv = *(tid < 454 ? a.b1 + (tid - 448) : a.b2 + (tid - 454));
   if (tid < 214) dbv = *(tid < 120 ? a.d1b + tid : (tid < 204 ? a.d2b + (tid - 120) : a.d3b + (tid - 204)));
@@ -513,6 +533,8 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   }
   if (tid < 98 * 2) reinterpret_cast<uint4*>(FT)[tid] = tabv;
   else if (tid >= 264 && tid < 264 + NM / 8) reinterpret_cast<uint4*>(PX)[tid - 264] = tabv;
+  else if (tid >= 264 + NM / 8 && tid < 264 + NPXV) reinterpret_cast<uint4*>(RT)[tid - 264 - NM / 8] = tabv;
+  if (tid >= 480 && tid < 480 + 16) st8(reinterpret_cast<bf16*>(smem + OFF_ZB) + 8 * (tid - 480), z8);
   if (tid >= 448 && tid < 448 + 22) WS[tid - 448] = biasv;  // b1 [6], b2 [16]
   float* DB = reinterpret_cast<float*>(smem + OFF_DB);
   if (tid < 214) DB[tid] = dbv;
@@ -608,7 +630,9 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
     const float b2 = WS[6 + i];
 #pragma unroll 2
     for (int mt = w; mt < nB; mt += NT / 64) {  // padded rows: window 25 of an image is padding
-      const bf16* abase = P1 + (int)PX[16 * mt + i] * 8;
+      // row m = image * 104 + t: the image from the 8-row block (m >> 3) / 13, the pixel from the per-image table
+      const int m = 16 * mt + i, img = ((m >> 3) * 79) >> 10;
+      const bf16* abase = P1 + (img * 196 + (int)(RT[m - DC2_RS * img] & 255u)) * 8;
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < 7; ++s) acc = mfma16x16x32(ld8(abase + toff[s]), bw[s], acc);
@@ -711,6 +735,7 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   {
     bf16x8 dp[2];
     unsigned long long cd[2];
+    uint2 pl[2];  // place[] of the window's 4 positions (read with the operands: no LDS round trip after the barrier)
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int it = tid + k * NT;
@@ -718,27 +743,31 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
         const int img = it / 50, rem = it - 50 * (it / 50), win = rem >> 1, nh = rem & 1;
         dp[k] = ld8(H0 + img * LD0 + win * 16 + 8 * nh);
         cd[k] = *reinterpret_cast<const unsigned long long*>(C2 + (img * 25 + win) * 16 + 8 * nh);
+        pl[k] = *reinterpret_cast<const uint2*>(RT + win * 4);
       }
     }
+    const unsigned zrow = RT[100 + ((tid >> 1) & 3)] >> 8;  // place[] of a padding row (threads < 64 use it)
     __syncthreads();  // dC2 overlays H0 / codes2
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int it = tid + k * NT;
       if (it < IMG * 50) {
         const int img = it / 50, rem = it - 50 * (it / 50), win = rem >> 1, nh = rem & 1;
+        const unsigned plw[2] = {pl[k].x, pl[k].y};
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
           bf16x8 o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = ((cd[k] >> (8 * e)) & 255u) == (unsigned)d ? dp[k][e] : (bf16)0.f;
-          st8(DC2 + ((img * DC2_RS + dc2_swz(win * 4 + d)) * 16 + 8 * nh), o);
+          const int row = (int)((plw[d >> 1] >> (16 * (d & 1) + 8)) & 255u);
+          st8(DC2 + ((img * DC2_RS + row) * 16 + 8 * nh), o);
         }
       }
     }
-  }
-  if (tid < IMG * 8) {  // the 4 zero rows of every image block (after the overlaid H0 / codes were read)
-    const int img = tid >> 3, rr = (tid >> 1) & 3, nh = tid & 1;
-    st8(DC2 + ((img * DC2_RS + dc2_swz(100 + rr)) * 16 + 8 * nh), zero8());
+    if (tid < IMG * 8) {  // the 4 zero rows of every image block (after the overlaid H0 / codes were read)
+      const int img = tid >> 3, nh = tid & 1;
+      st8(DC2 + ((img * DC2_RS + (int)zrow) * 16 + 8 * nh), zero8());
+    }
   }
   __syncthreads();
   LN_STAMP(7);
@@ -768,13 +797,13 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
     // the GEMM's M runs over the padded rows (26 steps of 32; the zero rows add nothing).  Step s + 1's
     // dC2 rows and pixel indices are read during step s: the P1 reads of a step depend on its
     // pixel-index reads, a second LDS round trip that was exposed once per step.
+    // K element 8 g + q + 4 k of step s is physical row 32 s + 16 k + 4 g + q: a transposed read's 32 lanes
+    // (two g) take 8 consecutive rows, all 64 banks once
     auto ldAv = [&](int s) -> bf16x8 {
-      const int mA = 32 * s + 8 * g + q;
-      // rows mA and mA + 4 lie in the 8-row block b = 4 s + g, block b - 13 img of image img = b / 13
-      const int b = 4 * s + g, sx = (b - 13 * ((b * 79) >> 10)) & 7;
-      return cat8(tr_read(DC2 + (mA ^ sx) * 16 + 4 * p), tr_read(DC2 + ((mA + 4) ^ sx) * 16 + 4 * p));
+      const int mA = 32 * s + 4 * g + q;
+      return cat8(tr_read(DC2 + mA * 16 + 4 * p), tr_read(DC2 + (mA + 16) * 16 + 4 * p));
     };
-    const unsigned short* pxl = PX + 8 * g + q;
+    const unsigned short* pxl = PX + 4 * g + q;
     // the step loop for a wave with KT tiles (one copy per tile count: a wave with 3 tiles issues 3
     // tiles' reads and MFMAs)
     auto run = [&](auto ktc) {
@@ -803,21 +832,21 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
       // odd count (13 of the 26 steps at 8 images) ends with one step from set a, which the last pair
       // has prefetched.
       bf16x8 ava = ldAv(sb);
-      unsigned pxa0 = pxl[32 * sb], pxa1 = pxl[32 * sb + 4];
+      unsigned pxa0 = pxl[32 * sb], pxa1 = pxl[32 * sb + 16];
       int s = sb;
 #pragma unroll 1
       for (; s + 1 < se; s += 2) {
         // (scheduling barriers keep the prefetches where they are: the scheduler otherwise hoists every
         // LDS read to the top of the loop body and waits for all of them there)
         const bf16x8 avb = ldAv(s + 1);
-        const unsigned pxb0 = pxl[32 * (s + 1)], pxb1 = pxl[32 * (s + 1) + 4];
+        const unsigned pxb0 = pxl[32 * (s + 1)], pxb1 = pxl[32 * (s + 1) + 16];
         __builtin_amdgcn_sched_barrier(0);
         step(ava, pxa0, pxa1);
         __builtin_amdgcn_sched_barrier(0);
         const int sn = s + 2 < se ? s + 2 : s;  // the last pair of an even count re-reads its own rows (unused)
         ava = ldAv(sn);
         pxa0 = pxl[32 * sn];
-        pxa1 = pxl[32 * sn + 4];
+        pxa1 = pxl[32 * sn + 16];
         __builtin_amdgcn_sched_barrier(0);
         step(avb, pxb0, pxb1);
         __builtin_amdgcn_sched_barrier(0);
@@ -863,22 +892,28 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   // ---------------------------------------------------------------- phase F: conv2 data gradient
   {
     const int bcol = i >> 3, c = i & 7;
+    // A row i of a tile holds pixel pair {0 .. 3, 8 .. 15, 4 .. 7}[i]: the lanes i = 0 .. 3, 12 .. 15 and the
+    // lanes 4 .. 11, which a ds_read_b128 serves together, then each take 8 consecutive pixel pairs (output
+    // rows 4 g + r accordingly: pixel pairs 4 gp + r)
+    const int ip = i < 4 ? i : (i < 12 ? i + 4 : i - 8);
+    const int gp = (0x1320 >> (4 * g)) & 3;  // {0, 2, 3, 1}[g]
 #pragma unroll 2
     for (int mt = w; mt < nF; mt += NT / 64) {
-      const int m = 16 * mt + i;
+      const int m = 16 * mt + ip;
       const int img = m / 98, rem = m - 98 * (m / 98);
       const uint4 tv = *reinterpret_cast<const uint4*>(FT + (rem * 2 + (g >> 1)) * 16);
       const unsigned tw[4] = {tv.x, tv.y, tv.z, tv.w};
-      // A row of step s: LDS byte offset computed branch-free (a t == 255 tap reads the zero block), read
-      // three steps ahead of its MFMA (a select of two addresses compiled to an exec-mask branch, and
-      // every read waited for its own data right before the MFMA: the LDS latency of all 15 steps was
-      // exposed in series)
-      // the table holds the stored row dc2_swz(t) inside the image's block (96, a zero padding row, for
-      // "no tap")
+      // A row of step s: LDS byte offset computed branch-free, read three steps ahead of its MFMA (a select
+      // of two addresses compiled to an exec-mask branch, and every read waited for its own data right
+      // before the MFMA: the LDS latency of all 15 steps was exposed in series).  The table holds the
+      // physical row t < 104 inside the image's block, or the zero code 128 + k: row k of the zero block,
+      // reached by adding zdelta (constant per tile) under the mask made of bit 7.
       const unsigned dbase = (unsigned)OFF_DC2 + 16u * (unsigned)(g & 1) + 32u * (unsigned)(img * DC2_RS);
+      const unsigned zdelta = (unsigned)(OFF_ZB - OFF_DC2 - 32 * 128) - 32u * (unsigned)(img * DC2_RS);
       auto ldA = [&](int st) -> bf16x8 {
         const unsigned t = (tw[st >> 2] >> (8 * (st & 3))) & 255u;
-        return *reinterpret_cast<const bf16x8*>(smem + dbase + 32u * t);
+        const unsigned zm = 0u - ((tw[st >> 2] >> (8 * (st & 3) + 7)) & 1u);
+        return *reinterpret_cast<const bf16x8*>(smem + dbase + 32u * t + (zm & zdelta));
       };
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       bf16x8 a0 = ldA(0), a1 = ldA(1), a2 = ldA(2);
@@ -893,7 +928,7 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           // pixel (image, y, 2 X2 + bcol) of row mm = (image * 14 + y) * 7 + X2: index 2 mm + bcol
-          const int mm = 16 * mt + 4 * g + r;
+          const int mm = 16 * mt + 4 * gp + r;
           P1[(2 * mm + bcol) * 8 + c] = f2bf(acc[r]);
         }
       }

@@ -987,40 +987,71 @@ def lenet_blocks(B: int) -> int:
 _LENET_TABLES = {}
 
 
+def lenet_dc2_class(oy: int, ox: int) -> int:
+    """Bank class (physical row mod 8) of conv2 output position (oy, ox) in the dC2 block; also defined
+    outside the 10x10 map, where it names the zero row a "no tap" lane of the data gradient reads."""
+    return ((ox >> 1) + 7 * oy + 4 * (ox & 1)) % 8
+
+
+def lenet_conv2_tables():
+    """Host (numpy) form of the fused LeNet-5 kernel's conv2 index tables; ``t`` is the window-order row
+    (window * 4 + position) of a conv2 output position inside an image's 104-row block, t = 100 .. 103 padding.
+    ``place`` [104] -- t -> physical row of the image's dC2 block: position (oy, ox) lies at a row of class
+    lenet_dc2_class(oy, ox) (rows class + 8 j, filled in t order), the padding rows take the rows left over;
+    ``ftab`` [98][2][16] u8 -- conv2 data gradient: for pool1 pixel pair (y, X2), k-half and step s, the
+    physical row of the position (oy, ox) = (y - ky, 2 X2 + 1 - u) it gathers, (ky, u) = divmod(2 s + half, 6);
+    outside the map (and for the unused step 15) the zero code 128 + class: row ``class`` of the zero block;
+    ``rowpix`` [104] -- physical row -> pool1 pixel of its position's window corner inside the image (the
+    padding rows: pixel 0, read against a zero gradient);
+    ``winpix`` [104] -- t -> the same pixel (conv2 forward, whose rows stay in window order)."""
+    import numpy as np
+
+    pos = {}
+    for oy in range(10):
+        for ox in range(10):
+            pos[(((oy >> 1) * 5 + (ox >> 1)) << 2) + ((oy & 1) << 1) + (ox & 1)] = (oy, ox)
+    place = np.full(104, -1, dtype=np.int64)
+    fill = [0] * 8
+    for t in range(100):
+        c = lenet_dc2_class(*pos[t])
+        place[t] = c + 8 * fill[c]
+        fill[c] += 1
+    assert max(fill) <= 13
+    place[100:] = sorted(set(range(104)) - set(place[:100].tolist()))
+    winpix = np.zeros(104, dtype=np.int64)
+    for t, (oy, ox) in pos.items():
+        winpix[t] = oy * 14 + ox
+    rowpix = np.zeros(104, dtype=np.int64)
+    rowpix[place] = winpix
+    ft = np.zeros((98, 2, 16), dtype=np.uint8)
+    for yx in range(98):
+        y, X2 = divmod(yx, 7)
+        for hf in range(2):
+            for s in range(16):
+                ky, u = divmod(2 * s + hf, 6)
+                oy, ox = y - ky, 2 * X2 + 1 - u
+                if ky < 5 and 0 <= oy < 10 and 0 <= ox < 10:
+                    t = (((oy >> 1) * 5 + (ox >> 1)) << 2) + ((oy & 1) << 1) + (ox & 1)
+                    ft[yx, hf, s] = place[t]
+                else:
+                    ft[yx, hf, s] = 128 + lenet_dc2_class(oy, ox)
+    return place, ft, rowpix, winpix
+
+
 def lenet_tables(device):
-    """Constant index tables of the fused LeNet-5 kernel (built once per device):
-    ``ftab`` [98][2][16] u8 — conv2 data gradient: for pool1 pixel pair (y, X2), k-half and step s, the
-    stored row swz(t) = t ^ ((t >> 3) & 7) of the window-major conv2 output row t it gathers, inside the
-    image's 104-row block (outside the 10x10 map: swz(100) = 96, a zero padding row);
-    ``pxtab`` [832] i16 — padded conv2 output row (image * 104 + window * 4 + position) -> pool1 pixel
-    index (padding rows 100..103 of an image: its pixel 0, read against a zero gradient);
-    ``frag`` — scratch for the per-step conv and dense weight fragments (written by the kernel's prep launch)."""
+    """Constant index tables of the fused LeNet-5 kernel (built once per device, from lenet_conv2_tables):
+    ``ftab`` [98][2][16] u8 -- phase F's gather table (physical dC2 rows and zero codes);
+    ``pxtab`` [832 + 104] i16 -- [0, 832): physical dC2 row (image * 104 + row) -> pool1 pixel index
+    image * 196 + rowpix[row], which phase E reads in physical row order; [832, 936): entry t =
+    winpix[t] | place[t] << 8, the per-image tables of phase B (low byte) and phase D (high byte);
+    ``frag`` -- scratch for the per-step conv and dense weight fragments (written by the kernel's prep launch)."""
     key = str(device)
     if key not in _LENET_TABLES:
         import numpy as np
 
-        swz = lambda t: t ^ ((t >> 3) & 7)  # noqa: E731  (csrc/lenet_fused.hip dc2_swz)
-        ft = np.full((98, 2, 16), swz(100), dtype=np.uint8)
-        for yx in range(98):
-            y, X2 = divmod(yx, 7)
-            for hf in range(2):
-                for s in range(16):
-                    P = 2 * s + hf
-                    if P >= 30:
-                        continue
-                    ky, u = divmod(P, 6)
-                    oy, ox = y - ky, 2 * X2 + 1 - u
-                    if 0 <= oy < 10 and 0 <= ox < 10:
-                        ft[yx, hf, s] = swz((((oy >> 1) * 5 + (ox >> 1)) << 2) + ((oy & 1) << 1) + (ox & 1))
-        px = np.zeros(832, dtype=np.int16)
-        for m in range(832):
-            img, q = divmod(m, 104)
-            if q >= 100:
-                px[m] = img * 196
-                continue
-            win, d = divmod(q, 4)
-            py, pxx = divmod(win, 5)
-            px[m] = img * 196 + (2 * py + (d >> 1)) * 14 + 2 * pxx + (d & 1)
+        place, ft, rowpix, winpix = lenet_conv2_tables()
+        px = np.concatenate([(np.arange(8)[:, None] * 196 + rowpix[None, :]).reshape(-1),
+                             winpix | (place << 8)]).astype(np.int16)
         nbytes = int(_C().lenet_frag_bytes())
         _LENET_TABLES[key] = (torch.from_numpy(ft.reshape(-1)).to(device), torch.from_numpy(px).to(device),
                               torch.zeros(nbytes, dtype=torch.uint8, device=device))

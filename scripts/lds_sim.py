@@ -6,13 +6,22 @@ workgroup's loop iterations and prices them with the gfx950 banking rules (MI355
 an instruction's lanes are serviced in fixed lane groups, one LDS cycle per group when conflict-free;
 each extra distinct dword address on a bank within a group costs one more cycle.  Prints, per phase,
 LDS-array cycles and the conflict share -- the same ratio as SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE.
-Phase E is replayed twice: as 8 waves x 26 steps over 16 tile slots (the kernel before the split) and as the
-2 K-halves x 4 column groups it runs now.
+Phase E is replayed as 8 waves x 26 steps over 16 tile slots (the kernel before the split) and as the
+2 K-halves x 4 column groups it runs now.  Phases D (stores), E and F are replayed for two dC2 layouts: the
+XOR swizzle t ^ ((t >> 3) & 7) of window-order rows (the kernel before the diagonal placement, kept for
+comparison) and the diagonal placement with class-matched zero rows (distriflow_amd.ops.lenet_conv2_tables,
+which the tables built here must equal).
+Phase B is replayed as the kernel runs it and, for the record, with the cross-image tiles and the searched tap
+order that were tried and measured no faster (docs/RESULTS.md).
 Usage: python3 scripts/lds_sim.py
 """
+import os
+import sys
 from collections import defaultdict
 
 import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 IMG, NT, NW = 8, 512, 8
 XS_ELEMS = IMG * 1024 + 32
@@ -33,6 +42,19 @@ OFF_H0 = OFF_U
 OFF_ZR = OFF_U + IMG * LD0 * 2 + IMG * LD1 * 2 + IMG * LD2 * 2 + IMG * LD3 * 2 + IMG * LD2 * 2 + IMG * LD1 * 2
 KO = OFF_K
 KZ = OFF_W + 128
+# behind the union: dense biases, stamps, the per-image row table, then the 8-row zero block of phase F at a
+# multiple of 256 bytes from dC2 (its row k has bank class k)
+U_DENSE = OFF_ZR + LD0 * 2 + IMG * 16 * 4 + IMG * 25 * 16 - OFF_U
+OFF_DB = OFF_U + (max(NM * 32, 32 + XS_ELEMS * 2 + 4 * 16 * 32 * 4, U_DENSE + 7 * 64 * 16) + 15) // 16 * 16
+OFF_RT = OFF_DB + 864 + 128
+OFF_ZB = OFF_DC2 + (OFF_RT + 208 - OFF_DC2 + 255) // 256 * 256
+LDS_BYTES = OFF_ZB + 256
+# conv2 forward, tried and not adopted: a tap order (tap of slot 4 s + g; 25 = none) found by
+# scripts/lds_tap_search.py for tiles made of one pool window of 4 consecutive images.  The kernel gives slot
+# k tap k (csrc/lenet_frag.h).
+C2_TAP_K = list(range(25)) + [25] * 3
+C2_ORDER = [0, 7, 1, 8, 4, 3, 6, 13, 9, 2, 10, 24, 14, 25, 15, 22, 16, 23, 17, 21, 18, 11, 19, 5, 20, 12, 25, 25]
+FPERM = [0, 1, 2, 3, 8, 9, 10, 11, 12, 13, 14, 15, 4, 5, 6, 7]  # phase F: A row of lane i (diagonal layout)
 
 B128_GROUPS = [list(range(0, 4)) + list(range(12, 16)) + list(range(20, 28)),
                list(range(4, 12)) + list(range(16, 20)) + list(range(28, 32)),
@@ -101,29 +123,83 @@ def phase_a(ph):
                 ph.add("b128", addr)
 
 
-def pxtab():
-    px = np.zeros(NM, dtype=np.int64)
-    for m in range(NM):
-        img, q = divmod(m, DC2_RS)
-        if q >= 100:
-            px[m] = img * 196
-            continue
-        win, d = divmod(q, 4)
-        py, pxx = divmod(win, 5)
-        px[m] = img * 196 + (2 * py + (d >> 1)) * 14 + 2 * pxx + (d & 1)
-    return px
+def trow(oy, ox):
+    """window-order row of conv2 output position (oy, ox)"""
+    return (((oy >> 1) * 5 + (ox >> 1)) << 2) + ((oy & 1) << 1) + (ox & 1)
 
 
-def phase_b(ph):
-    PX = pxtab()
+def dc2_class(oy, ox):
+    return ((ox >> 1) + 7 * oy + 4 * (ox & 1)) % 8
+
+
+def winpix():
+    """window-order row t of an image -> pool1 pixel inside the image (padding rows: pixel 0)"""
+    wp = np.zeros(DC2_RS, dtype=np.int64)
+    for oy in range(10):
+        for ox in range(10):
+            wp[trow(oy, ox)] = oy * 14 + ox
+    return wp
+
+
+def dc2_swz(t):
+    return t ^ ((t >> 3) & 7)
+
+
+def placement(diag):
+    """t -> physical row of the image's dC2 block"""
+    if not diag:
+        return np.array([dc2_swz(t) for t in range(DC2_RS)])
+    place, fill = np.full(DC2_RS, -1, dtype=np.int64), [0] * 8
+    for t, (oy, ox) in sorted((trow(oy, ox), (oy, ox)) for oy in range(10) for ox in range(10)):
+        c = dc2_class(oy, ox)
+        place[t] = c + 8 * fill[c]
+        fill[c] += 1
+    place[100:] = sorted(set(range(DC2_RS)) - set(place[:100].tolist()))
+    return place
+
+
+def pxtab(diag):
+    """physical dC2 row (image * 104 + row) -> pool1 pixel (phase E)"""
+    rp = np.zeros(DC2_RS, dtype=np.int64)
+    rp[placement(diag)] = winpix()
+    return (np.arange(IMG)[:, None] * 196 + rp[None, :]).reshape(-1)
+
+
+def phase_b(ph, cross=False, order=None):
+    """A reads of conv2: a tile is 16 consecutive rows of the padded per-image row space, slot 4 s + g of
+    K-step s holds tap 4 s + g.  Tried (cross, order): tile mt = pool window mt % 26 of images
+    4 (mt / 26) + (i >> 2), row i = position i & 3; another tap of slot 4 s + g."""
+    WP = winpix()
+    order = C2_TAP_K if order is None else order
     for w in range(NW):
         for mt in range(w, NM // 16, NW):
             for s in range(7):
                 addr = []
                 for lane, i, g in lanes():
-                    tap = 4 * s + g
+                    tap = order[4 * s + g]
                     toff = ((tap // 5) * 14 + tap % 5) * 8 if tap < 25 else 0
-                    addr.append(OFF_P1 + 2 * (int(PX[16 * mt + i]) * 8 + toff))
+                    if cross:
+                        img, t = 4 * (mt // 26) + (i >> 2), 4 * (mt % 26) + (i & 3)
+                    else:
+                        img, t = divmod(16 * mt + i, DC2_RS)
+                    addr.append(OFF_P1 + 2 * ((img * 196 + int(WP[t])) * 8 + toff))
+                ph.add("b128", addr)
+
+
+def phase_d(ph, diag=True):
+    """dC2 stores: thread (image, window, 16-byte half) writes the window's 4 rows"""
+    place = placement(diag)
+    for d in range(4):
+        for k in range(2):
+            for w in range(NW):
+                addr = []
+                for lane in range(64):
+                    it = 64 * w + lane + k * NT
+                    if it >= IMG * 50:
+                        addr.append(None)
+                        continue
+                    img, rem = divmod(it, 50)
+                    addr.append(OFF_DC2 + 2 * ((img * DC2_RS + int(place[(rem >> 1) * 4 + d])) * 16 + 8 * (rem & 1)))
                 ph.add("b128", addr)
 
 
@@ -141,77 +217,94 @@ def e_waves(split):
             yield 0, nE, [w + NW * k for k in range((13 + NW - 1) // NW)]
 
 
-def phase_e(ph, ph2=None, ph3=None, split=True):
+def phase_e(ph, ph2=None, ph3=None, split=True, diag=True):
     """A (dC2) reads into ph, the im2col B (P1) reads into ph2, the u16 pixel-index reads and (split) the
-    cross-half exchange through P1 into ph3 (default: ph for all)."""
-    PX = pxtab()
+    cross-half exchange through P1 into ph3 (default: ph for all).  A step's lane (g, q) takes physical
+    rows 32 s + 4 g + q and + 16 (diag) or, before, window-order rows 32 s + 8 g + q and + 4 through the XOR swizzle."""
+    PX = pxtab(diag)
     ph2 = ph2 if ph2 is not None else ph
     ph3 = ph3 if ph3 is not None else ph
     for w, (s0, s1, tiles) in enumerate(e_waves(split)):
         for s in range(s0, s1):
-            # A: two transposed reads of dC2 (ldAv: the swizzle term comes from the 8-row block)
+            # A: two transposed reads of dC2 (ldAv; before: row mA ^ sx, the swizzle term of its 8-row block)
             for half in range(2):
                 addr = []
                 for lane, i, g in lanes():
                     q, p = (lane & 15) >> 2, lane & 3
-                    mA = 32 * s + 8 * g + q + 4 * half
+                    mA = 32 * s + (16 * half + 4 * g + q if diag else 8 * g + q + 4 * half)
                     b = 4 * s + g
-                    sx = (b - 13 * ((b * 79) >> 10)) & 7
-                    img, t = divmod(mA, DC2_RS)
-                    assert (mA ^ sx) == img * DC2_RS + dc2_swz(t)
+                    sx = 0 if diag else (b - 13 * ((b * 79) >> 10)) & 7
                     addr.append(OFF_DC2 + 2 * ((mA ^ sx) * 16 + 4 * p))
                 ph.add("tr", addr)
             # the step's two pixel indices (PX + 8 g + q, + 4)
             for half in range(2):
-                ph3.add("b16", [OFF_PX + 2 * (32 * s + 8 * g + ((lane & 15) >> 2) + 4 * half) for lane, i, g in lanes()])
+                q = lambda lane: (lane & 15) >> 2  # noqa: E731
+                ph3.add("b16", [OFF_PX + 2 * (32 * s + (16 * half + 4 * g + q(lane) if diag else 8 * g + q(lane) + 4 * half))
+                                for lane, i, g in lanes()])
             for T in tiles:
                 for half in range(2):
                     addr = []
                     for lane, i, g in lanes():
                         q, p = (lane & 15) >> 2, lane & 3
-                        mA = 32 * s + 8 * g + q + 4 * half
+                        mA = 32 * s + (16 * half + 4 * g + q if diag else 8 * g + q + 4 * half)
                         tap = 2 * T + (p >> 1)
                         tp = tap if tap < 25 else 0
                         toff = ((tp // 5) * 14 + tp % 5) * 8 + 4 * (p & 1)
-                        addr.append(OFF_P1 + 2 * (int(PX[mA]) * 8 + toff))
+                        b = 4 * s + g
+                        sx = 0 if diag else (b - 13 * ((b * 79) >> 10)) & 7
+                        addr.append(OFF_P1 + 2 * (int(PX[mA ^ sx]) * 8 + toff))
                     ph2.add("tr", addr)
         if split:  # upper half writes, lower half reads [tile][lane] 16-byte pieces at the start of P1
             for T in tiles:
                 ph3.add("b128", [OFF_P1 + (T * 64 + lane) * 16 for lane in range(64)])
 
 
-def ftab():
-    ft = np.full((98, 2, 16), 100, dtype=np.int64)
+def ftab(diag):
+    """[98][2][16]: physical row of the position pixel pair (y, X2) gathers in step s of k-half hf; no tap:
+    128 + class, row `class` of the zero block (before: the image's zero padding row dc2_swz(100))"""
+    place = placement(diag)
+    ft = np.zeros((98, 2, 16), dtype=np.int64)
     for yx in range(98):
         y, X2 = divmod(yx, 7)
         for hf in range(2):
             for s in range(16):
-                P = 2 * s + hf
-                if P >= 30:
-                    continue
-                ky, u = divmod(P, 6)
+                ky, u = divmod(2 * s + hf, 6)
                 oy, ox = y - ky, 2 * X2 + 1 - u
-                if 0 <= oy < 10 and 0 <= ox < 10:
-                    ft[yx, hf, s] = (((oy >> 1) * 5 + (ox >> 1)) << 2) + ((oy & 1) << 1) + (ox & 1)
+                if ky < 5 and 0 <= oy < 10 and 0 <= ox < 10:
+                    ft[yx, hf, s] = place[trow(oy, ox)]
+                else:
+                    ft[yx, hf, s] = 128 + dc2_class(oy, ox) if diag else place[100]
     return ft
 
 
-def dc2_swz(t):
-    return t ^ ((t >> 3) & 7)
-
-
-def phase_f(ph):
-    FT = ftab()
+def phase_f(ph, diag=True, perm=True):
+    """A reads; perm: lane i holds A row FPERM[i] of the tile"""
+    FT = ftab(diag)
     for w in range(NW):
         for mt in range(w, 49, NW):
             for s in range(15):
                 addr = []
                 for lane, i, g in lanes():
-                    m = 16 * mt + i
+                    m = 16 * mt + (FPERM[i] if perm else i)
                     img, rem = divmod(m, 98)
                     t = int(FT[rem, g >> 1, s])
-                    addr.append(OFF_DC2 + 2 * ((img * DC2_RS + dc2_swz(t)) * 16 + 8 * (g & 1)))
+                    if t >= 128:
+                        addr.append(OFF_ZB + 32 * (t - 128) + 16 * (g & 1))
+                    else:
+                        addr.append(OFF_DC2 + 2 * ((img * DC2_RS + t) * 16 + 8 * (g & 1)))
                 ph.add("b128", addr)
+
+
+def check_tables():
+    """the tables replayed here are the ones the kernel is given"""
+    from distriflow_amd.ops import lenet_conv2_tables
+
+    place, ft, rowpix, wp = lenet_conv2_tables()
+    assert np.array_equal(place, placement(True)) and np.array_equal(ft, ftab(True)), "placement / ftab"
+    assert np.array_equal(wp, winpix()), "winpix"
+    assert np.array_equal((np.arange(IMG)[:, None] * 196 + rowpix[None, :]).reshape(-1), pxtab(True)), "pxtab"
+    assert (OFF_ZB - OFF_DC2) % 256 == 0 and 2 * LDS_BYTES <= 160 * 1024
+    assert sorted(C2_ORDER) == list(range(25)) + [25] * 3
 
 
 def phase_g(ph):
@@ -247,11 +340,22 @@ def phase_g(ph):
 
 
 def main():
+    check_tables()
+    old = "XOR swizzle (before)"
+    rows = [("A conv1 (A reads)", phase_a, True), ("B conv2 (A reads)", phase_b, True),
+            ("B conv2, tried: cross-image tiles", lambda p: phase_b(p, cross=True), False),
+            ("B conv2, tried: cross-image tiles, searched tap order", lambda p: phase_b(p, cross=True, order=C2_ORDER), False),
+            ("B conv2, tried: per-image tiles, searched tap order", lambda p: phase_b(p, order=C2_ORDER), False),
+            ("D dC2 stores, " + old, lambda p: phase_d(p, diag=False), False),
+            ("D dC2 stores", phase_d, True),
+            ("E conv2 wgrad, 8 x 26 steps, " + old, lambda *p: phase_e(*p, split=False, diag=False), False),
+            ("E conv2 wgrad, 2 x 4 split, " + old, lambda *p: phase_e(*p, diag=False), False),
+            ("E conv2 wgrad, 2 x 4 split", phase_e, True),
+            ("F conv2 dgrad, " + old, lambda p: phase_f(p, diag=False, perm=False), False),
+            ("F conv2 dgrad, rows i", lambda p: phase_f(p, perm=False), False),
+            ("F conv2 dgrad (A reads)", phase_f, True), ("G conv1 wgrad", phase_g, True)]
     tot = conf = 0
-    for name, fn in [("A conv1 (A reads)", phase_a), ("B conv2 (A reads)", phase_b),
-                     ("E conv2 wgrad, 8 x 26 steps", lambda *p: phase_e(*p, split=False)),
-                     ("E conv2 wgrad, 2 x 4 split", phase_e), ("F conv2 dgrad (A reads)", phase_f),
-                     ("G conv1 wgrad", phase_g)]:
+    for name, fn, counted in rows:  # (rows not counted: the kernel as it was, or a variant that was tried, shown for comparison)
         ph = Phase(name)
         if name.startswith("E "):
             ph_a, ph_b, ph_x = Phase("  dC2 (tr reads)"), Phase("  im2col P1 (tr reads)"), Phase("  indices, exchange")
@@ -266,10 +370,9 @@ def main():
         if name.startswith("E "):
             for q in (ph_a, ph_b, ph_x):
                 q.report()
-        if "8 x 26" in name:  # the kernel as it was: shown for comparison, not part of the total
-            continue
-        tot += c
-        conf += k
+        if counted:
+            tot += c
+            conf += k
     print(f"{'modelled total':<28} {'':13} LDS cycles {tot:7d}  conflict {conf:7d} ({100.0 * conf / tot:5.1f} %)")
 
 
