@@ -731,6 +731,11 @@ void bind_fused(py::module_& m) {
                               reinterpret_cast<long long*>(tr.data_ptr()));
     return std::make_tuple(fwd, tr);
   }, "bf16 element index in the LeNet fragment buffer of every weight of dense layer l: (forward [N][K], transposed [K][N])");
+  m.def("lenet_conv1_frag_map", []() {
+    auto mp = torch::empty({150, 8}, torch::kInt);
+    dfa::lenet_conv1_frag_map(reinterpret_cast<int*>(mp.data_ptr()));
+    return mp;
+  }, "bf16 element index in the LeNet fragment buffer of conv1 weight j = (c * 5 + ky) * 5 + kx at each of its 8 band positions: [150][8]");
   m.def("lenet_dense_part_floats", [](int64_t B) { return (int64_t)dfa::lenet_dense_part_floats((int)B); });
   m.def("lenet_red_err_offset", []() { return (int64_t)dfa::lenet_red_err_offset(); });
 }

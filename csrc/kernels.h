@@ -770,6 +770,7 @@ size_t lenet_frag_bytes();
 // dense layer l (0 .. 2): its N, K and (fwd / tr non-null) the fragment-buffer element of every weight,
 // fwd [N][K] and tr [K][N]
 void lenet_dense_frag_map(int l, int* N, int* K, long long* fwd, long long* tr);
+void lenet_conv1_frag_map(int* out);  // [150][8]
 // out[row * ldt + col] = element index of (row, col) in a transposed activation / gradient buffer of the
 // fused LeNet-5 step (H^T, dZ^T: blocks of 16 rows x 32 batch columns, csrc/lenet_frag.h lenet_act_pos)
 void lenet_act_map(int rows, int ldt, long long* out);

@@ -1,10 +1,12 @@
 // MFMA B fragments of the fused LeNet-5 step's conv weights (csrc/lenet_fused.hip), shared by its
 // prep launch and by the optimizer (csrc/optim.hip), which rebuilds them from the weights it just
 // updated so that a training step needs no separate prep launch.
-//   [NFRAG][64 lanes] x 8 bf16:  conv1 banded (f = ky * 3 + T: column j = output x offset 2 (j & 7)
-//   [+ row parity], channel 2T + (j >> 3); k = input column), conv2 forward (step s: column n,
-//   k = (tap 4s + g, channel e)), conv2 data gradient pair-banded (step s: column (b = j >> 3,
-//   c = j & 7), k = ((ky, u), n) with kx = u - 1 + b).
+//   [NFRAG][64 lanes] x 8 bf16:  conv1 banded, two kernel rows per K-step (f = ks * 3 + T, 9 fragments:
+//   column n = (output x offset j = n & 7, channel 2T + (n >> 3)); k = (s, p) = 16 s + p: kernel row
+//   2 ks + s, input column p = j + kx of 16, so each weight sits at 8 positions: lenet_conv1_frag_pos;
+//   fragments 9 .. 14 are unused and stay zero), conv2 forward (step s: column n, k = (tap 4s + g,
+//   channel e)), conv2 data gradient pair-banded (step s: column (b = j >> 3, c = j & 7),
+//   k = ((ky, u), n) with kx = u - 1 + b).
 // Behind them the six dense weight matrices of the step (forward [N][K] and transposed [K][N] of the
 // three layers) in the same lane-linear form: a matrix M[R][C] (R = MFMA row / column index, padded to
 // 16; C = reduction length, padded to 32; KS = C / 32) is tiles x KS fragments in [tile][k-step] order,
@@ -29,17 +31,40 @@ constexpr int kLeNetFragLanes = NFRAG_CONV * 64;            // conv fragment lan
 constexpr int kLeNetDenseFragLanes = (NFRAG - NFRAG_CONV) * 64;
 constexpr int kLeNetConvW = 2550;  // conv1 kernel [6][25] then conv2 kernel [16][150]
 
+// conv1 fragments in use (3 K-steps of two kernel rows x 3 channel pairs); FR_C1 + kConv1Frags .. FR_C2 - 1
+// are allocated and zero
+constexpr int kConv1Frags = 9;
+// THE position rule of the conv1 fragments: bf16 element index (into the fragment buffer) of conv1 weight
+// j = (channel * 5 + ky) * 5 + kx in the band of output column offset jj (0 .. 7).  Fragment
+// f = (ky >> 1) * 3 + (channel >> 1); B row k = 16 (ky & 1) + p with input column p = jj + kx (< 12), i.e.
+// lane group g = 2 (ky & 1) + (p >> 3), element p & 7; B column n = 8 (channel & 1) + jj.  The gather
+// (lenet_frag_lane), the scatter (lenet_frag_scatter) and the host's map (lenet_conv1_frag_map) all go
+// through this function.
+__host__ __device__ constexpr int lenet_conv1_frag_pos(int j, int jj) {
+  const int ch = j / 25, r = j - 25 * ch, ky = r / 5, kx = r - 5 * ky, p = jj + kx;
+  const int f = FR_C1 + (ky >> 1) * 3 + (ch >> 1), lane = (2 * (ky & 1) + (p >> 3)) * 16 + (ch & 1) * 8 + jj;
+  return (f * 64 + lane) * 8 + (p & 7);
+}
+
 // Fragment lane fl (fragment fl / 64, lane fl % 64); W(j) = conv weight j of the 2550 above.
 template <typename W>
 __device__ __forceinline__ bf16x8 lenet_frag_lane(int fl, W&& wt) {
   const int f = fl >> 6, lane = fl & 63, i = lane & 15, g = lane >> 4;
   bf16x8 o;
   if (f < FR_C2) {
-    const int ky = f / 3, T = f - 3 * (f / 3), c = 2 * T + (i >> 3), j8 = i & 7;
+    // the lane's column is (channel ch, offset jj), its B rows lie in kernel row ky: the weights (ch, ky, kx)
+    // whose position for jj falls into this lane
+    const int ks = f / 3, T = f - 3 * (f / 3), ch = 2 * T + (i >> 3), jj = i & 7, ky = 2 * ks + (g >> 1);
+    const bool live = f < FR_C1 + kConv1Frags && ky < 5;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const int kx = 8 * g + e - 2 * j8;
-      o[e] = f2bf((kx >= 0 && kx < 5) ? wt(c * 25 + ky * 5 + kx) : 0.f);
+      float v = 0.f;
+#pragma unroll
+      for (int kx = 0; kx < 5; ++kx) {
+        const int j = live ? (ch * 5 + ky) * 5 + kx : 0;
+        if (live && lenet_conv1_frag_pos(j, jj) == fl * 8 + e) v = wt(j);
+      }
+      o[e] = f2bf(v);
     }
   } else if (f < FR_DG) {
     const int s = f - FR_C2, tap = 4 * s + g;
@@ -68,13 +93,8 @@ __device__ __forceinline__ void lenet_frag_scatter(void* frag_buf, int j, float 
   const bf16 v = f2bf(w);
   auto put = [&](int f, int lane, int e) { fr[((f * 64) + lane) * 8 + e] = v; };
   if (j < 150) {  // conv1 [c][ky][kx]
-    const int c = j / 25, r = j - 25 * c, ky = r / 5, kx = r - 5 * ky;
-    const int f = ky * 3 + (c >> 1);
 #pragma unroll
-    for (int j8 = 0; j8 < 8; ++j8) {
-      const int t = kx + 2 * j8;
-      put(f, (t >> 3) * 16 + (c & 1) * 8 + j8, t & 7);
-    }
+    for (int jj = 0; jj < 8; ++jj) fr[lenet_conv1_frag_pos(j, jj)] = v;
     return;
   }
   // conv2 [n][tap = ky * 5 + kx][c]

@@ -11,17 +11,19 @@
 //                        conv2 data gradient: 37 x 1 KB) and the six dense matrices (forward and
 //                        transposed: 261 x 1 KB), normally kept fresh by whoever updates the weights (the
 //                        reduce launch's fused update, the optimizer launch).  A workgroup loads the
-//                        22 conv1 / conv2 forward fragments once (16-byte pieces, at most 3 per thread, in
+//                        9 + 7 conv1 / conv2 forward fragments once (16-byte pieces, two per thread, in
 //                        phase 0) into LDS scratch that later phases overwrite, and its 8 waves take them
 //                        from there with one ds_read_b128 per lane and fragment; the 15 data-gradient
 //                        fragments are still loaded by every wave (no LDS is free while dC2 is live; the
 //                        loads are in flight under the conv2 weight gradient)
 //   lenet_train_kernel   one workgroup = 8 images (fewer at small batches: lenet_ipw), 8 waves, ~78 KB of
 //                        LDS (two workgroups per CU):
-//     conv1 5x5 'same' + bias + ReLU + 2x2 max-pool   MFMA with a banded (Toeplitz) weight operand:
-//                          A = 32 consecutive input pixels of a row (one aligned ds_read_b128; odd
-//                          output columns read a copy of the image shifted by one pixel), so the
-//                          4 accumulator rows of a lane are one 2x2 pool window: the pool is in-lane
+//     conv1 5x5 'same' + bias + ReLU + 2x2 max-pool   MFMA with a banded (Toeplitz) weight operand, two
+//                          kernel rows per K-step: rows (image, y), A = 16 consecutive input pixels of
+//                          rows y + ky and y + ky + 1 (one aligned ds_read_b128 per lane), columns = 8
+//                          consecutive output x times 2 channels (3 K-steps where one kernel row of 32
+//                          pixels per step took 5); a lane's 4 accumulator rows are two vertical pool
+//                          pairs, the horizontal partner is the neighbouring lane (one DPP exchange)
 //     conv2 5x5 + bias + ReLU + pool                  implicit GEMM, output rows in pool-window order
 //     dense 400-120-84-10 + softmax-CE + backward     MFMA, weight fragments streamed from L2 (one
 //                          lane-linear 1 KB load per fragment: 8 cache-line lookups, where a row-major
@@ -76,11 +78,11 @@ constexpr int OFF_PX = OFF_K + 32;                  // physical dC2 row -> P1 pi
 constexpr int OFF_FT = OFF_PX + NM * 2;             // conv2 dgrad table [98][2][16] u8 (host-built)
 constexpr int OFF_W = OFF_FT + 98 * 2 * 16;         // f32: b1 [6], b2 [16], then 8 int labels
 constexpr int OFF_KZ = OFF_W + 128;                 // 32 B zeros (phase G's zero columns)
-// the union starts where it always did (OFF_XS1's bank offset from Xs, and so phase A / G's
-// conflict-free reads, depend on it)
+// the union starts where it always did (OFF_XS1's bank offset from Xs, and so phase G's conflict-free
+// reads, depend on it)
 constexpr int OFF_U = OFF_KZ + 32;
-// phases A and G: input shifted left by one pixel; 32 bytes into the union so that its rows sit 24 banks
-// from Xs's (the A-operand reads of phase A and the B-operand reads of phase G are then conflict-free:
+// phase G: input shifted left by one pixel (built after phase F; phase A reads Xs alone); 32 bytes into the
+// union so that its rows sit 24 banks from Xs's (the B-operand reads of phase G are then conflict-free:
 // scripts/lds_sim.py)
 constexpr int OFF_XS1 = OFF_U + 32;
 constexpr int LD0 = 424, LD1 = 136, LD2 = 104, LD3 = 40;  // dense row strides (elements)
@@ -108,17 +110,21 @@ constexpr int U_G = 32 + XS_ELEMS * 2 + 4 * 16 * 32 * 4;
 // class its position would have had.  Phase E reads the physical rows in order (the K order of its GEMM is
 // free) and takes their pixels from PX; the 4 padding rows of a block hold zeros.
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
-// conv1 / conv2 B fragments (FR_C1, FR_C2: 22 x 1 KB, lane-linear), loaded once per workgroup in phase 0
-// and handed to the waves through LDS.  The conv1 image lies under Xs1: every wave has read it before
-// the barrier in front of build_shift1, which overwrites all of it.  The conv2 image has to survive
-// phase A and be readable while other waves already write phase B's outputs, so it sits behind the
-// dense buffers (H0 .. C2); phase D's dC2 is the first to overwrite it.
-constexpr int NFP1 = (FR_C2 - FR_C1) * 64, NFP2 = (FR_DG - FR_C2) * 64;  // 16-byte pieces
+// conv1 / conv2 B fragments (FR_C1: the 9 in use, FR_C2: 7; 16 x 1 KB, lane-linear), loaded once per
+// workgroup in phase 0 and handed to the waves through LDS.  The conv1 image lies over H0 .. H2: every wave
+// has read it before the barrier in front of phase A, and phase B, behind the barrier after phase A, is
+// the first to write there.  What phase B does not write of it (H0's pad columns, H0 rows of images that
+// are not live) stays weight bytes: finite bf16 values, which phase C multiplies by zero weights or, for an
+// image past the batch, cuts off with its explicit zero gradient.  The conv2 image has to survive phase A
+// and be readable while other waves already write phase B's outputs, so it sits behind the dense buffers
+// (H0 .. C2); phase D's dC2 is the first to overwrite it.
+constexpr int NFP1 = kConv1Frags * 64, NFP2 = (FR_DG - FR_C2) * 64;  // 16-byte pieces
 constexpr int OFF_FC1 = OFF_XS1;
 constexpr int OFF_FC2 = OFF_U + U_DENSE;
 constexpr int U_FC2 = U_DENSE + NFP2 * 16;
-static_assert(FR_C1 == 0 && FR_C2 - FR_C1 == 15 && FR_DG - FR_C2 == 7, "phase 0 stages fragments 0 .. 21 as one range");
-static_assert(OFF_FC1 + NFP1 * 16 <= OFF_XS1 + (XS_ELEMS / 8 - 1) * 16, "build_shift1 overwrites the conv1 fragments");
+static_assert(FR_C1 == 0 && kConv1Frags <= FR_C2 - FR_C1 && FR_DG - FR_C2 == 7, "phase 0 stages fragments 0 .. 8 and 15 .. 21");
+static_assert(NFP1 + NFP2 == 2 * NT && NFP1 >= NT, "phase 0: two fragment pieces per thread, the first of conv1");
+static_assert(OFF_FC1 + NFP1 * 16 <= OFF_Z3, "the conv1 fragment image ends inside H2: ZR and Z3 are zero after phase 0");
 // dense biases (f32: dense-1 [120], dense-2 [84], dense-3 [10]), staged in phase 0: read from LDS, a
 // bias load never waits behind the weight prefetches issued before it
 constexpr int OFF_DB = OFF_U + (cmax(cmax(cmax(U_DENSE, U_DC2), U_G), U_FC2) + 15) / 16 * 16;
@@ -441,8 +447,8 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
             g = lane >> 4;
   const int r0 = lenet_img_group(blockIdx.x, a.nblk) * (TRIM ? a.ipw : IMG);
   const int rows = min(TRIM ? a.ipw : IMG, a.B - r0);
-  // per-image loop trip counts (tiles of 16 / 32 rows over rows-of-image blocks of 56, 104, 98, 14)
-  const int nA = TRIM ? 2 * ((7 * rows + 1) / 2) : 56;        // conv1: 3.5 M-tiles per image, 2 halves each
+  // per-image loop trip counts (tiles of 16 / 32 rows over rows-of-image blocks of 28, 104, 98, 14)
+  const int nA = TRIM ? 4 * ((28 * rows + 15) / 16) : 56;     // conv1: 1.75 M-tiles per image, 4 x tiles each
   const int nB = TRIM ? (13 * rows + 1) / 2 : NM / 16;        // conv2: 6.5 M-tiles per image
   const int nE = TRIM ? (13 * rows + 3) / 4 : NM / 32;        // conv2 wgrad: 3.25 K-steps of 32 rows per image
   const int nF = TRIM ? (49 * rows + 7) / 8 : 49;             // conv2 dgrad: 6.125 M-tiles per image
@@ -471,15 +477,15 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   float biasv = 0.f, dbv = 0.f;
   if (tid >= 448 && tid < 448 + 22) biasv = *(tid < 454 ? a.b1 + (tid - 448) : a.b2 + (tid - 454));
   if (tid < 214) dbv = *(tid < 120 ? a.d1b + tid : (tid < 204 ? a.d2b + (tid - 120) : a.d3b + (tid - 204)));
-  // conv1 and conv2 B fragments of this step (lenet_prep_kernel): 1408 pieces of 16 bytes, at most 3 per
-  // thread, once per workgroup (every wave loading all of them for itself was 8 x the traffic, in front
-  // of conv1's and conv2's first MFMA).  Unconditional for the same reason as the label and the row below
-  // (a thread past the last piece re-reads it): the wait for the indices then knows that exactly these
-  // loads follow them and does not wait for a fragment piece.
-  constexpr int NFK = ccdiv(NFP1 + NFP2, NT);
+  // conv1 and conv2 B fragments of this step (lenet_prep_kernel): 576 + 448 pieces of 16 bytes from two
+  // ranges of the buffer (the unused conv1 fragments 9 .. 14 lie between them), exactly two per thread,
+  // once per workgroup (every wave loading all of them for itself was 8 x the traffic, in front of conv1's
+  // and conv2's first MFMA).  Unconditional for the same reason as the label and the row below: the wait
+  // for the indices then knows that exactly these loads follow them and does not wait for a fragment piece.
+  constexpr int NFK = 2;
   bf16x8 fv[NFK];
-#pragma unroll
-  for (int k = 0; k < NFK; ++k) fv[k] = frag[FR_C1 * 64 + min(tid + NT * k, NFP1 + NFP2 - 1)];
+  fv[0] = frag[FR_C1 * 64 + tid];
+  fv[1] = frag[(tid + NT < NFP1 ? FR_C1 * 64 : FR_C2 * 64 - NFP1) + tid + NT];
   // The label and the input row are loaded by EVERY thread (one without a label / a row reads element 0:
   // one address per wave, its value unused).  A wait count is a compile-time constant, so behind a
   // conditional load the fragment pieces' wait had to assume no load followed them and became
@@ -512,7 +518,7 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   for (int e = tid; e < (OFF_K - OFF_XS) / 16; e += NT)
     st8(Xs + 8 * e, (e >= OFF_P1 / 16 && e < OFF_C1 / 16) ? one6 : z8);
   // the union, except the two fragment images (staged below by other threads: no zero may land on them;
-  // build_shift1 and phase D overwrite them before anything else reads those bytes)
+  // phase B and phase D are the first to write over them)
   static_assert(OFF_FC2 + NFP2 * 16 == OFF_DB, "the conv2 fragment image ends the union");
   if (tid < (OFF_FC1 - OFF_U) / 16) st8(reinterpret_cast<bf16*>(smem + OFF_U) + 8 * tid, z8);
   for (int e = (OFF_FC1 - OFF_U) / 16 + NFP1 + tid; e < (OFF_FC2 - OFF_U) / 16; e += NT)
@@ -542,11 +548,11 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
   int* LBL = reinterpret_cast<int*>(WS + 24);
   if (tid >= 256 && tid < 256 + IMG) LBL[tid - 256] = lbl;  // clamped where read (no wait for it here)
   __syncthreads();
-  // conv1 B fragments from the workgroup's copy (lane-linear ds_read_b128s); the barrier in front of
-  // build_shift1, which overwrites the copy, also ends these reads
-  bf16x8 bc[15];
+  // conv1 B fragments from the workgroup's copy (lane-linear ds_read_b128s); nothing writes the copy
+  // before phase B
+  bf16x8 bc[kConv1Frags];
 #pragma unroll
-  for (int f = 0; f < 15; ++f) bc[f] = ld8(reinterpret_cast<const bf16*>(smem + OFF_FC1) + 8 * (f * 64 + lane));
+  for (int f = 0; f < kConv1Frags; ++f) bc[f] = ld8(reinterpret_cast<const bf16*>(smem + OFF_FC1) + 8 * (f * 64 + lane));
   // input rows -> bf16, 2-pixel zero border ('same' padding)
   if (xload) {
     unsigned* dst = reinterpret_cast<unsigned*>(Xs + ximg * 1024 + (xrow + 2) * 32 + 2);
@@ -567,40 +573,53 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
     }
   }
   __syncthreads();
-  build_shift1(Xs, Xs1);
-  __syncthreads();
   LN_STAMP(1);
 
   // ---------------------------------------------------------------- phase A: conv1 + ReLU + pool
-  // rows m = (image, y, parity): A = row y of the image (parity 1: shifted by one pixel) from column
-  // x0; column j of channel-pair tile T = output x = x0 + 2 (j & 7) + parity, channel 2T + (j >> 3).
-  // A lane's 4 accumulator rows (y, y+1) x (parity 0, 1) are one 2x2 pool window.
+  // rows m = (image, y): 8 x 28 = 14 M-tiles; x tiles x0 = 8 xt (tile 3: x = 24 .. 27 and four columns that
+  // are dropped); column j of channel-pair tile T = output x = x0 + (j & 7), channel 2T + (j >> 3).  K-step
+  // ks holds kernel rows 2 ks and 2 ks + 1 with 16 input pixels each (8 consecutive outputs span 12): lane
+  // (i, g) reads padded row y + ky, ky = 2 ks + (g >> 1), pixels x0 + 8 (g & 1) .. + 7, one aligned
+  // ds_read_b128 (tile 3's second piece wraps into the next padded row, for image 7 into the tail pad: it
+  // meets weights only in the dropped columns).  The sixth slot (ky = 5) has zero weights and reads row
+  // ky = 4 again: finite, and in bounds (row y + 5 of image 7 would lie behind Xs).
+  // A lane's 4 accumulator rows are y0 .. y0 + 3 of one image, y0 a multiple of 4: two vertical pool pairs.
+  // The horizontal partner of column j is lane i ^ 1; after one exchange the even lane holds pool window row
+  // y0 / 2 and the odd lane window row y0 / 2 + 1 (the even lane sends rows y0 + 2, y0 + 3, the odd lane
+  // rows y0, y0 + 1).
   {
     const float b1c[3] = {WS[(i >> 3)], WS[2 + (i >> 3)], WS[4 + (i >> 3)]};
+    const bool odd = (i & 1) != 0;
+    int koff[3];  // element offset of the lane's kernel row in K-step ks
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) koff[ks] = min(2 * ks + (g >> 1), 4) * 32 + 8 * (g & 1);
 #pragma unroll 2
     for (int u = w; u < nA; u += NT / 64) {
-      const int mt = u >> 1, x0 = (u & 1) * 16;
+      const int mt = u >> 2, x0 = (u & 3) * 8;
       const int m = 16 * mt + i;
-      const int img = m / 56, rem = m - 56 * (m / 56);
-      const bf16* abase = ((rem & 1) ? Xs1 : Xs) + img * 1024 + (rem >> 1) * 32 + x0 + 8 * g;
+      const int img = m / 28, y = m - 28 * (m / 28);
+      const bf16* abase = Xs + img * 1024 + y * 32 + x0;
       f32x4 acc[3];
 #pragma unroll
       for (int T = 0; T < 3; ++T) acc[T] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ky = 0; ky < 5; ++ky) {
-        const bf16x8 av = ld8(abase + ky * 32);
+      for (int ks = 0; ks < 3; ++ks) {
+        const bf16x8 av = ld8(abase + koff[ks]);
 #pragma unroll
-        for (int T = 0; T < 3; ++T) acc[T] = mfma16x16x32(av, bc[ky * 3 + T], acc[T]);
+        for (int T = 0; T < 3; ++T) acc[T] = mfma16x16x32(av, bc[ks * 3 + T], acc[T]);
       }
       const int m0 = 16 * mt + 4 * g;
-      const int imgo = m0 / 56, py = (m0 - 56 * (m0 / 56)) >> 2;
-      const int px = (x0 >> 1) + (i & 7);
+      const int imgo = m0 / 28, py = ((m0 - 28 * (m0 / 28)) >> 1) + (i & 1);
+      const int px = (x0 >> 1) + ((i & 7) >> 1);  // >= 14: a dropped column of tile 3
       unsigned cw = 0;
 #pragma unroll
       for (int T = 0; T < 3; ++T) {
+        const float v0 = acc[T][0] + b1c[T], v1 = acc[T][1] + b1c[T], v2 = acc[T][2] + b1c[T], v3 = acc[T][3] + b1c[T];
+        const float q0 = dpp_f<0xB1>(odd ? v0 : v2), q1 = dpp_f<0xB1>(odd ? v1 : v3);  // the partner's two rows
         float best;
         unsigned code;
-        pool4(acc[T][0] + b1c[T], acc[T][1] + b1c[T], acc[T][2] + b1c[T], acc[T][3] + b1c[T], best, code);
+        // the window in (dy, dx) row-major order: the even lane is column dx = 0, the odd lane dx = 1
+        pool4(odd ? q0 : v0, odd ? v2 : q0, odd ? q1 : v1, odd ? v3 : q1, best, code);
         const int c = 2 * T + (i >> 3);
         if (px < 14) P1[((imgo * 14 + py) * 14 + px) * 8 + c] = f2bf(best);
         cw |= code << (3 * c);
@@ -695,9 +714,9 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
     const float e = c < 10 ? __expf(z - mx) : 0.f;
     const float ssum = row16_sum(e);
     if (c < 10) {
-      // an image past the batch takes a zero gradient: its Z3 row still holds what build_shift1 left
-      // there (pixels of image 5, non-zero when 6 or 7 images are live), which would otherwise flow
-      // back through the dense layers into the conv gradients
+      // an image past the batch takes a zero gradient: its logits come from whatever its H0 row holds
+      // (bytes of the conv1 fragment image, or conv outputs of a tile that reaches into it), and their
+      // softmax gradient would otherwise flow back through the dense layers into the conv gradients
       const float gv = live ? (e * (1.f / ssum) - (c == y ? 1.f : 0.f)) * a.grad_scale : 0.f;
       Z3[r * LD3 + c] = f2bf(gv);
       if (live) a.dz3T[lenet_act_pos(c, r0 + r, a.ldt)] = f2bf(gv);
@@ -935,7 +954,7 @@ __global__ void __launch_bounds__(NT, 2 * NT / 256) lenet_train_kernel(LeNetArgs
     }
   }
   __syncthreads();
-  build_shift1(Xs, Xs1);  // dC2 is no longer needed: the union takes the shifted input again
+  build_shift1(Xs, Xs1);  // dC2 is no longer needed: the union takes the shifted input (phase G's only)
   __syncthreads();
   LN_STAMP(9);
 
@@ -2228,6 +2247,11 @@ size_t lenet_frag_bytes() { return (size_t)NFRAG * 64 * 16; }
 void lenet_act_map(int rows, int ldt, long long* out) {
   for (int r = 0; r < rows; ++r)
     for (int c = 0; c < ldt; ++c) out[(long long)r * ldt + c] = lenet_act_pos(r, c, ldt);
+}
+// out[j * 8 + jj]: bf16 element index of conv1 weight j in the band of output column offset jj
+void lenet_conv1_frag_map(int* out) {
+  for (int j = 0; j < 150; ++j)
+    for (int jj = 0; jj < 8; ++jj) out[j * 8 + jj] = lenet_conv1_frag_pos(j, jj);
 }
 void lenet_dense_frag_map(int l, int* N, int* K, long long* fwd, long long* tr) {
   const LeNetDenseFrag d = lenet_dense_frag(l);

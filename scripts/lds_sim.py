@@ -6,6 +6,9 @@ workgroup's loop iterations and prices them with the gfx950 banking rules (MI355
 an instruction's lanes are serviced in fixed lane groups, one LDS cycle per group when conflict-free;
 each extra distinct dword address on a bank within a group costs one more cycle.  Prints, per phase,
 LDS-array cycles and the conflict share -- the same ratio as SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE.
+Phase A is replayed as the kernel runs it (two kernel rows x 16 pixels per K-step, from Xs alone), as it ran
+before (one kernel row x 32 pixels, odd columns from the shifted copy) and with a per-image skew of Xs that
+was priced and not built (the 2-way conflicts are between rows of one image, 4 rows = 256 bytes apart).
 Phase E is replayed as 8 waves x 26 steps over 16 tile slots (the kernel before the split) and as the
 2 K-halves x 4 column groups it runs now.  Phases D (stores), E and F are replayed for two dC2 layouts: the
 XOR swizzle t ^ ((t >> 3) & 7) of window-order rows (the kernel before the diagonal placement, kept for
@@ -109,9 +112,23 @@ def lanes():
         yield lane, lane & 15, lane >> 4
 
 
-def phase_a(ph):
+def phase_a(ph, rows2=True, skew=0):
+    """A reads of conv1.  rows2 (the kernel): rows (image, y), 4 x tiles of 8 columns, K-step ks = kernel rows
+    2 ks and 2 ks + 1 (the sixth slot reads row 4 again) x 16 pixels.  Before: rows (image, y, parity) from Xs /
+    Xs1, 2 x halves, one kernel row of 32 pixels per step.  skew: bytes by which image k's rows would be
+    shifted (k * skew), priced only."""
     for w in range(NW):
         for u in range(w, 56, NW):
+            if rows2:
+                mt, x0 = u >> 2, (u & 3) * 8
+                for ks in range(3):
+                    addr = []
+                    for lane, i, g in lanes():
+                        img, y = divmod(16 * mt + i, 28)
+                        ky = min(2 * ks + (g >> 1), 4)
+                        addr.append(OFF_XS + img * skew + 2 * (img * 1024 + (y + ky) * 32 + x0 + 8 * (g & 1)))
+                    ph.add("b128", addr)
+                continue
             mt, x0 = u >> 1, (u & 1) * 16
             for ky in range(5):
                 addr = []
@@ -342,7 +359,10 @@ def phase_g(ph):
 def main():
     check_tables()
     old = "XOR swizzle (before)"
-    rows = [("A conv1 (A reads)", phase_a, True), ("B conv2 (A reads)", phase_b, True),
+    rows = [("A conv1, one kernel row per step (before)", lambda p: phase_a(p, rows2=False), False),
+            ("A conv1 (A reads)", phase_a, True),
+            ("A conv1, priced: image k skewed by 32 k B", lambda p: phase_a(p, skew=32), False),
+            ("B conv2 (A reads)", phase_b, True),
             ("B conv2, tried: cross-image tiles", lambda p: phase_b(p, cross=True), False),
             ("B conv2, tried: cross-image tiles, searched tap order", lambda p: phase_b(p, cross=True, order=C2_ORDER), False),
             ("B conv2, tried: per-image tiles, searched tap order", lambda p: phase_b(p, order=C2_ORDER), False),
