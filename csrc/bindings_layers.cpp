@@ -103,7 +103,8 @@ void igemm_fwd_py(torch::Tensor src, torch::Tensor w, c10::optional<torch::Tenso
 // The plan of a launch with these shapes before any tensor exists: 16-byte aligned dummy operands stand in
 // for the real ones (torch allocations are at least that aligned).  bacc_mode >= 0: with BatchNorm sums.
 py::dict conv_plan_py(int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector<int64_t> geom, int64_t mode,
-                      int64_t bacc_mode, bool two, bool has_res, bool has_mask, bool pooled, int64_t lda, bool drop) {
+                      int64_t bacc_mode, bool two, bool has_res, bool has_mask, bool pooled, int64_t lda, bool drop,
+                      bool has_bias) {
   static dfa::bf16 dummy[8] __attribute__((aligned(16)));
   static double dacc[2] __attribute__((aligned(16)));
   static float dvec[2] __attribute__((aligned(16)));
@@ -113,6 +114,7 @@ py::dict conv_plan_py(int64_t M, int64_t N, int64_t K, int64_t Kpad, std::vector
   a.src = dummy; a.w = dummy; a.out = dummy;
   if (has_res) a.res = dummy;
   if (has_mask) a.mask = dummy;
+  if (has_bias) a.bias = dvec;
   if (pooled) a.pool_code = reinterpret_cast<uint8_t*>(dummy);
   if (drop) a.drop.on = 1;
   if (bacc_mode >= 0) {
@@ -512,6 +514,52 @@ void dwconv_wgrad_py(torch::Tensor dy, torch::Tensor x, torch::Tensor gw, c10::o
   check_hip(dfa::dwconv_wgrad((const dfa::bf16*)dy.data_ptr(), (const dfa::bf16*)x.data_ptr(), gw.data_ptr<float>(), gbp,
                               ws.data_ptr<float>(), (size_t)ws.numel(), g, cur_stream()),
             "dwconv_wgrad");
+}
+
+// ---- up-sampling and the transposed conv's bias gradient (csrc/upsample.hip)
+static dfa::UpGeom up_geom(const std::vector<int64_t>& g, bool bilinear, bool half_pixel) {
+  TORCH_CHECK(g.size() == 6, "upsample2d: geom = [B, H, W, C, sh, sw]");
+  for (int64_t v : g) TORCH_CHECK(v > 0 && v < (1LL << 30), "upsample2d: bad geometry");
+  TORCH_CHECK(g[1] * g[4] < (1LL << 30) && g[2] * g[5] < (1LL << 30), "upsample2d: output too large");
+  dfa::UpGeom p{};
+  p.B = (int)g[0]; p.H = (int)g[1]; p.W = (int)g[2]; p.C = (int)g[3]; p.sh = (int)g[4]; p.sw = (int)g[5];
+  p.bilinear = bilinear ? 1 : 0;
+  p.off = half_pixel ? 0.5f : 0.f;
+  return p;
+}
+
+void upsample2d_fwd_py(torch::Tensor x, torch::Tensor y, std::vector<int64_t> geom, bool bilinear, bool half_pixel) {
+  const dfa::UpGeom g = up_geom(geom, bilinear, half_pixel);
+  need(x, at::kBFloat16, "upsample2d x");
+  need(y, at::kBFloat16, "upsample2d y");
+  const int64_t n = (int64_t)g.B * g.H * g.W * g.C;
+  TORCH_CHECK(x.numel() == n && y.numel() == n * g.sh * g.sw, "upsample2d: tensor sizes do not match the geometry");
+  check_hip(dfa::upsample2d_fwd((const dfa::bf16*)x.data_ptr(), (dfa::bf16*)y.data_ptr(), g, cur_stream()),
+            "upsample2d_fwd");
+}
+
+void upsample2d_bwd_py(torch::Tensor dy, c10::optional<torch::Tensor> mask, torch::Tensor dx, std::vector<int64_t> geom,
+                       bool bilinear, bool half_pixel) {
+  const dfa::UpGeom g = up_geom(geom, bilinear, half_pixel);
+  need(dy, at::kBFloat16, "upsample2d dy");
+  need(dx, at::kBFloat16, "upsample2d dx");
+  const int64_t n = (int64_t)g.B * g.H * g.W * g.C;
+  TORCH_CHECK(dx.numel() == n && dy.numel() == n * g.sh * g.sw, "upsample2d: tensor sizes do not match the geometry");
+  const dfa::bf16* mp = opt_ptr<const dfa::bf16>(mask, at::kBFloat16, "upsample2d mask", n, "upsample2d mask too small");
+  check_hip(dfa::upsample2d_bwd((const dfa::bf16*)dy.data_ptr(), mp, (dfa::bf16*)dx.data_ptr(), g, cur_stream()),
+            "upsample2d_bwd");
+}
+
+void channel_sum_py(torch::Tensor dy, torch::Tensor gb, torch::Tensor ws, int64_t M, int64_t C, double scale) {
+  need(dy, at::kBFloat16, "channel_sum dy");
+  need(gb, at::kFloat, "channel_sum gb");
+  need(ws, at::kFloat, "channel_sum workspace");
+  TORCH_CHECK(M > 0 && C > 0 && C <= (1 << 20) && M < (1LL << 40), "channel_sum: bad sizes");
+  TORCH_CHECK(dy.numel() == M * C && gb.numel() >= C, "channel_sum: tensor sizes do not match [M][C]");
+  TORCH_CHECK(ws.numel() >= C, "channel_sum: the workspace does not hold one slab");
+  check_hip(dfa::channel_sum((const dfa::bf16*)dy.data_ptr(), gb.data_ptr<float>(), ws.data_ptr<float>(),
+                             (size_t)ws.numel(), M, (int)C, (float)scale, cur_stream()),
+            "channel_sum");
 }
 
 void gap_fwd_py(torch::Tensor x, torch::Tensor y, int64_t B, int64_t HW, int64_t C) {
@@ -989,7 +1037,7 @@ void bind_layers(py::module_& m) {
   m.def("conv_plan", &conv_plan_py, "the launch plan of igemm_fwd for these shapes (csrc/conv_plan.hip), as a dict",
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("Kpad"), py::arg("geom"), py::arg("mode"),
         py::arg("bacc_mode") = -1, py::arg("two") = false, py::arg("has_res") = false, py::arg("has_mask") = false,
-        py::arg("pooled") = false, py::arg("lda") = 0, py::arg("drop") = false);
+        py::arg("pooled") = false, py::arg("lda") = 0, py::arg("drop") = false, py::arg("has_bias") = false);
   m.def("unpool2", [](torch::Tensor dyp, torch::Tensor code, torch::Tensor dy) {
     need(dyp, at::kBFloat16, "unpool dyp");
     need(dy, at::kBFloat16, "unpool dy");
@@ -1033,6 +1081,9 @@ void bind_layers(py::module_& m) {
   m.def("dwconv_fwd", &dwconv_fwd_py, "depthwise conv forward, fp32 kernel [KH][KW][C*M] (csrc/dwconv.hip)");
   m.def("dwconv_dgrad", &dwconv_dgrad_py, "depthwise conv data gradient [* relu'(mask)]");
   m.def("dwconv_wgrad", &dwconv_wgrad_py, "depthwise conv weight / bias gradient (fixed-order slab sums)");
+  m.def("upsample2d_fwd", &upsample2d_fwd_py, "UpSampling2D forward, nearest / bilinear (csrc/upsample.hip)");
+  m.def("upsample2d_bwd", &upsample2d_bwd_py, "UpSampling2D backward, gather form [* relu'(mask)]");
+  m.def("channel_sum", &channel_sum_py, "gb[c] = scale * sum_m dy[m][c] (fixed-order slab sums)");
   m.def("gather_labels", &gather_labels_py);
   m.def("bn_stats_fwd", &bn_stats_fwd_py, "BN forward statistics (partials + last-workgroup finalize, one launch)");
   m.def("bn_stats_bwd", &bn_stats_bwd_py, "BN backward statistics: dgamma, dbeta and dx coefficients");

@@ -825,6 +825,20 @@ long long dwconv_wgrad_slab_floats(const DwConvGeom& g);
 hipError_t dwconv_wgrad(const bf16* dy, const bf16* x, float* gw, float* gb, float* ws, size_t ws_floats,
                         const DwConvGeom& g, hipStream_t st);
 
+// UpSampling2D and the transposed conv's bias gradient (csrc/upsample.hip): NHWC bf16, output H*sh x W*sw.
+struct UpGeom {
+  int B, H, W, C, sh, sw;
+  int bilinear;  // 0: nearest (repeat each pixel)
+  float off;     // bilinear: src = (dst + off) / s - off; 0.5 = half-pixel centres (Keras), 0 = tf.js
+};
+hipError_t upsample2d_fwd(const bf16* x, bf16* y, const UpGeom& g, hipStream_t st);
+// dx = [mask > 0] * sum of the dy pixels that read the pixel (gather, fp32, fixed order); mask nullable
+hipError_t upsample2d_bwd(const bf16* dy, const bf16* mask, bf16* dx, const UpGeom& g, hipStream_t st);
+// gb [C] = scale * sum_m dy[m][c], fp32, fixed summation order: per-workgroup slabs [C] in ws (at least one
+// must fit), then slab_reduce
+hipError_t channel_sum(const bf16* dy, float* gb, float* ws, size_t ws_floats, long long M, int C, float scale,
+                       hipStream_t st);
+
 // Direct convolution for C_in = 1 (csrc/smallc.hip); igemm_fwd / igemm_wgrad dispatch to it.
 constexpr int kSmallMaxK = 64, kSmallMaxN = 64;
 // the image-resident 3x3 x 32-channel variants: images per workgroup, output channels

@@ -10,7 +10,8 @@ What the reference saves with ``model.save('file://<dir>')`` / loads with ``tf.l
 
 Keras layouts are converted at this boundary only: Conv2D kernel HWIO [kh][kw][cin][cout] <-> engine
 OHWI [cout][kh][kw][cin] (a SeparableConv2D's ``pointwise_kernel`` likewise; a ``depthwise_kernel``
-[kh][kw][cin][multiplier] is the engine's [kh][kw][cin*multiplier] reshaped, no permutation); Dense kernel
+[kh][kw][cin][multiplier] is the engine's [kh][kw][cin*multiplier] reshaped, no permutation; a Conv2DTranspose
+kernel [kh][kw][filters][cin] <-> engine [cin][kh][kw][filters], the OHWI matrix of the conv it transposes); Dense kernel
 [in][out] <-> engine [out][in]; BatchNormalization
 gamma/beta(/moving_mean/moving_variance).  Weights are always stored fp32 on disk even when training
 runs in bf16.  Multi-shard manifests (``group1-shard1of1`` ... as in model.json:1) are read too.
@@ -25,8 +26,8 @@ import numpy as np
 import torch
 
 from ..models.keras import keras_config_from_layers
-from ..models.layers import (BatchNorm, Conv2D, ConvPoolGemm, Dense, DepthwiseConv2D, FusedConvPool, KerasConvBlock,
-                             ResidualBlock)
+from ..models.layers import (BatchNorm, Conv2D, Conv2DTranspose, ConvPoolGemm, Dense, DepthwiseConv2D, FusedConvPool,
+                             KerasConvBlock, ResidualBlock)
 
 FORMAT = "layers-model"
 GENERATED_BY = "distriflow_amd"
@@ -41,6 +42,8 @@ def _engine_to_keras(spec_name: str, value: torch.Tensor, layer) -> np.ndarray:
     if spec_name.endswith("/depthwise_kernel") and isinstance(layer, DepthwiseConv2D):
         # engine [KH][KW][C*M] is Keras [KH, KW, C, M] flattened: a reshape, no permutation
         return v.reshape(layer.kh, layer.kw, layer.in_shape[2], layer.depth_multiplier).contiguous().numpy()
+    if spec_name.endswith("/kernel") and isinstance(layer, Conv2DTranspose):
+        return v.permute(1, 2, 3, 0).contiguous().numpy()          # [cin][kh][kw][f] -> Keras [kh][kw][f][cin]
     if spec_name.endswith(_CONV_KERNELS) and conv:
         return v.permute(1, 2, 3, 0).contiguous().numpy()          # OHWI -> HWIO
     if spec_name.endswith("/kernel") and isinstance(layer, Dense):
@@ -51,7 +54,9 @@ def _engine_to_keras(spec_name: str, value: torch.Tensor, layer) -> np.ndarray:
 def _keras_to_engine(spec_name: str, arr: np.ndarray, layer, engine_shape) -> torch.Tensor:
     t = torch.from_numpy(np.ascontiguousarray(arr)).float()
     conv = isinstance(layer, (Conv2D, FusedConvPool, ConvPoolGemm, KerasConvBlock))
-    if spec_name.endswith(_CONV_KERNELS) and conv:
+    if spec_name.endswith("/kernel") and isinstance(layer, Conv2DTranspose):
+        t = t.permute(3, 0, 1, 2)                                  # Keras [kh][kw][f][cin] -> [cin][kh][kw][f]
+    elif spec_name.endswith(_CONV_KERNELS) and conv:
         t = t.permute(3, 0, 1, 2)                                  # HWIO -> OHWI
     elif spec_name.endswith("/kernel") and isinstance(layer, Dense):
         t = t.t()

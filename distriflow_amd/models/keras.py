@@ -12,7 +12,9 @@ Keras 2.1.4 Sequential (/root/reference/experiment/mnist/model.json:1).  Support
   the logits layer (the output) must be a Dense fed by a single chain;
 * InputLayer, Conv2D (any kernel size / strides pair, 'valid' or 'same' -- an odd 'same' total pads the
   bottom / right, as TensorFlow does), DepthwiseConv2D and SeparableConv2D (same geometries, any
-  depth_multiplier; no dilation), Dense, Activation (relu, relu6, sigmoid, tanh, elu, selu, softplus, softsign,
+  depth_multiplier; no dilation), Conv2DTranspose (same geometries, kernels smaller than the stride included;
+  no output_padding, no dilation), UpSampling2D (integer sizes, nearest or bilinear with Keras' half-pixel
+  centres), Dense, Activation (relu, relu6, sigmoid, tanh, elu, selu, softplus, softsign,
   hard_sigmoid, swish / silu, exponential, linear; softmax / sigmoid as the output), the ReLU layer class
   (max_value None or 6, no negative_slope / threshold), MaxPooling2D and
   AveragePooling2D (any pool / strides, 'valid' or 'same'), GlobalAveragePooling2D,
@@ -21,8 +23,9 @@ Keras 2.1.4 Sequential (/root/reference/experiment/mnist/model.json:1).  Support
 from __future__ import annotations
 
 from .graph import GraphLayer, Merge, split_chain
-from .layers import (Activation, AveragePooling2D, BatchNorm, Conv2D, Dense, DepthwiseConv2D, Dropout, Flatten,
-                     GlobalAveragePooling2D, GlobalMaxPooling2D, Layer, MaxPooling2D, SeparableConv2D)
+from .layers import (Activation, AveragePooling2D, BatchNorm, Conv2D, Conv2DTranspose, Dense, DepthwiseConv2D, Dropout,
+                     Flatten, GlobalAveragePooling2D, GlobalMaxPooling2D, Layer, MaxPooling2D, SeparableConv2D,
+                     UpSampling2D)
 
 _MERGES = ("Add", "Subtract", "Multiply", "Average", "Maximum", "Minimum", "Concatenate")
 
@@ -117,6 +120,17 @@ def _make_layer(k: str, c: dict) -> Layer:
             return DepthwiseConv2D(*geom, name=name, depthwise_initializer=dinit)
         return SeparableConv2D(c["filters"], *geom, name=name, depthwise_initializer=dinit,
                                pointwise_initializer=_init_name(c, "pointwise_initializer"))
+    if k == "Conv2DTranspose":
+        if c.get("output_padding") is not None:
+            raise NotImplementedError(f"Conv2DTranspose {name!r}: output_padding {c['output_padding']!r}")
+        if _pair(c.get("dilation_rate", [1, 1])) != (1, 1):
+            raise NotImplementedError(f"Conv2DTranspose {name!r}: dilation_rate {c['dilation_rate']!r}")
+        return Conv2DTranspose(c["filters"], _pair(c["kernel_size"]), _pair(c.get("strides", [1, 1])),
+                               c.get("padding", "valid"), c.get("activation", "linear"), c.get("use_bias", True),
+                               name=name, kernel_initializer=_init_name(c))
+    if k == "UpSampling2D":
+        # Keras' own sampling (half-pixel centres); tf.js' upSampling2d differs for 'bilinear', see PARITY.md
+        return UpSampling2D(c.get("size", [2, 2]), c.get("interpolation", "nearest"), name=name)
     if k == "Dense":
         return Dense(c["units"], c.get("activation", "linear"), c.get("use_bias", True), name=name,
                      kernel_initializer=_init_name(c))
@@ -187,7 +201,7 @@ def _graph_layers(order: list, parents: dict) -> tuple:
     out, newid = [], {0: 0}
     for j, (l, ins) in enumerate(mid, start=1):
         out.append((l, [newid[i] for i in ins]))
-        act = getattr(l, "activation", None) if isinstance(l, (Dense, Conv2D, DepthwiseConv2D,
+        act = getattr(l, "activation", None) if isinstance(l, (Dense, Conv2D, Conv2DTranspose, DepthwiseConv2D,
                                                                SeparableConv2D)) else None
         if act not in (None, "linear", "relu"):
             if act == "softmax":
@@ -296,6 +310,18 @@ def keras_config_from_layers(layers: list[Layer], input_shape: tuple, name: str 
                                              "config": {"scale": 1.0, "mode": "fan_avg", "distribution": "uniform",
                                                         "seed": None}},
                       "bias_initializer": {"class_name": "Zeros", "config": {}}})
+        elif isinstance(l, Conv2DTranspose):
+            cls = "Conv2DTranspose"
+            c.update(l.config())
+            c.update({"data_format": "channels_last", "dilation_rate": [1, 1], "output_padding": None,
+                      "kernel_initializer": {"class_name": "VarianceScaling",
+                                             "config": {"scale": 1.0, "mode": "fan_avg", "distribution": "uniform",
+                                                        "seed": None}},
+                      "bias_initializer": {"class_name": "Zeros", "config": {}}})
+        elif isinstance(l, UpSampling2D):
+            cls = "UpSampling2D"
+            c.update(l.config())
+            c["data_format"] = "channels_last"
         elif isinstance(l, (DepthwiseConv2D, SeparableConv2D)):
             cls = type(l).__name__
             glorot = {"class_name": "VarianceScaling",

@@ -495,6 +495,145 @@ class SeparableConv2D(Layer):
                 "depth_multiplier": d.depth_multiplier, "activation": self.activation, "use_bias": self.use_bias}
 
 
+class Conv2DTranspose(Layer):
+    """Keras Conv2DTranspose: the data gradient of the conv G from [OH][OW][filters] to the input [H][W][Cin]
+    with the same kernel size, strides and padding ('valid': H*sh + max(KH - sh, 0) rows; 'same': H*sh rows,
+    G's TensorFlow 'same' pads; no output_padding, no dilation).  The kernel is stored as G's OHWI matrix
+    [Cin][KH][KW][filters] (Keras [KH, KW, filters, Cin] permuted at I/O), so the conv kernels run the three
+    passes with their roles swapped: forward = G's data gradient on the dgrad-layout copy (bias and ReLU in
+    its epilogue), input gradient = G's forward (relu' of the input as its epilogue mask), kernel gradient =
+    G's with x and dy exchanged; the bias gradient is a channel sum of dy (csrc/upsample.hip).
+    Deliberately not a Conv2D: the conv+pool fusions, the BatchNorm-sum wiring and the checkpoint layouts
+    match on that class."""
+    has_params = True
+
+    def __init__(self, filters: int, kernel_size=(3, 3), strides=(1, 1), padding="valid", activation="linear",
+                 use_bias=True, name=None, kernel_initializer="glorot_uniform"):
+        super().__init__(name or "conv2d_transpose")
+        self.filters = int(filters)
+        self.kh, self.kw = ops._pair(kernel_size)
+        self.sh, self.sw = ops._pair(strides)
+        if padding not in ("valid", "same"):
+            raise NotImplementedError(f"Conv2DTranspose padding {padding!r}")
+        self.padding = padding
+        self.activation = activation
+        self.use_bias = use_bias
+        self.kernel_initializer = kernel_initializer
+        if activation == "relu":
+            self.relu = True
+        elif activation not in ops.ACT_KINDS:
+            raise NotImplementedError(f"Conv2DTranspose activation {activation!r}")
+
+    @property
+    def kernel_name(self) -> str:
+        return f"{self.name}/kernel"
+
+    @property
+    def bias_name(self) -> str:
+        return f"{self.name}/bias"
+
+    def _geom(self, B):
+        H, W, C = self.in_shape
+        return ops.deconv_geometry(B, H, W, C, self.filters, (self.kh, self.kw), (self.sh, self.sw), self.padding)
+
+    def build(self, in_shape):
+        H, W, C = in_shape
+        self.in_shape = (H, W, C)
+        g = self._geom(1)
+        self.out_shape = (g[5], g[6], self.filters)
+        return self.out_shape
+
+    def can_fuse_relu(self):
+        return True
+
+    def specs(self):
+        C, T = self.in_shape[2], self.kh * self.kw
+        # fans as Keras computes them from the kernel shape [KH, KW, filters, Cin]; the forward pass reads the
+        # dgrad-layout copy, so it is kept even when no input gradient is needed
+        s = [ParamSpec(self.kernel_name, (C, self.kh, self.kw, self.filters), "matrix", (C, T, self.filters),
+                       self.kernel_initializer, (T * self.filters, T * C), needs_dgrad=True)]
+        if self.use_bias:
+            s.append(ParamSpec(self.bias_name, (self.filters,), "vector", init="zeros"))
+        return s
+
+    def alloc(self, B, device, dtype, ws):
+        super().alloc(B, device, dtype, ws)
+        self.ws = ws
+
+    def forward(self, x, training):
+        self.x = x
+        st = self.store
+        kn = self.kernel_name
+        b = st[self.bias_name] if self.use_bias else None
+        ops.deconv_fwd(x, st.weight(kn), st.weight_t(kn), b, self.out, self._geom(x.shape[0]), relu=self.relu)
+        return self.out
+
+    def backward_weights(self, dy):
+        st = self.store
+        gb = st.gradient(self.bias_name) if self.use_bias else None
+        ops.deconv_wgrad(dy.reshape(self.out.shape), self.x, st.grad_matrix(self.kernel_name), gb, self.ws.wgrad,
+                         self._geom(self.x.shape[0]))
+
+    def backward_data(self, dy):
+        if not self.need_dx:
+            return None
+        ops.deconv_dgrad(dy.reshape(self.out.shape), self.store.weight(self.kernel_name), self.dx,
+                         self._geom(self.x.shape[0]), mask=self.x if self.in_relu else None)
+        return self.dx
+
+    def backward(self, dy):
+        self.backward_weights(dy)
+        return self.backward_data(dy)
+
+    def config(self):
+        return {"filters": self.filters, "kernel_size": [self.kh, self.kw], "strides": [self.sh, self.sw],
+                "padding": self.padding, "activation": self.activation, "use_bias": self.use_bias}
+
+
+class UpSampling2D(Layer):
+    """Keras UpSampling2D: [H][W][C] -> [H*sh][W*sw][C].  'nearest' repeats each pixel; 'bilinear' samples at
+    src = (dst + o) / s - o with o = 0.5 (``half_pixel_centers``: Keras / TF2, the default and what the loader
+    builds) or o = 0 (tf.js' own upSampling2d).  No parameters; the backward applies relu' of its input when
+    that is a fused-ReLU output (csrc/upsample.hip)."""
+
+    def __init__(self, size=(2, 2), interpolation="nearest", half_pixel_centers=True, name=None):
+        super().__init__(name or "up_sampling2d")
+        if isinstance(size, (list, tuple)):
+            fractional = any(int(v) != v for v in size)
+        else:
+            fractional = int(size) != size
+        if fractional:
+            raise NotImplementedError(f"UpSampling2D size {size!r}: integer factors only")
+        self.size = ops._pair(size)
+        if min(self.size) < 1:
+            raise ValueError(f"UpSampling2D size {size!r}")
+        if interpolation not in ops.UPSAMPLE_KINDS:
+            raise NotImplementedError(f"UpSampling2D interpolation {interpolation!r}")
+        self.interpolation = interpolation
+        self.half_pixel_centers = bool(half_pixel_centers)
+
+    def build(self, in_shape):
+        H, W, C = in_shape
+        self.in_shape = (H, W, C)
+        self.out_shape = (H * self.size[0], W * self.size[1], C)
+        return self.out_shape
+
+    def forward(self, x, training):
+        self.x = x
+        ops.upsample2d_fwd(x, self.out, self.size, self.interpolation, self.half_pixel_centers)
+        return self.out
+
+    def backward(self, dy):
+        if not self.need_dx:
+            return None
+        ops.upsample2d_bwd(dy.reshape(self.out.shape), self.dx, self.size, self.interpolation, self.half_pixel_centers,
+                           mask=self.x if self.in_relu else None)
+        return self.dx
+
+    def config(self):
+        return {"size": list(self.size), "interpolation": self.interpolation}
+
+
 def _pair(v, default=None):
     if v is None:
         return default

@@ -18,8 +18,8 @@ import torch
 
 from .. import ops
 from ..diagnostics import on as diag_on
-from .layers import (Activation, BatchNorm, Conv2D, ConvPoolGemm, Dense, DepthwiseConv2D, Dropout, Flatten,
-                     FusedConvPool, KerasConvBlock, Layer, MaxPooling2D, ResidualBlock, SeparableConv2D)
+from .layers import (Activation, BatchNorm, Conv2D, Conv2DTranspose, ConvPoolGemm, Dense, DepthwiseConv2D, Dropout,
+                     Flatten, FusedConvPool, KerasConvBlock, Layer, MaxPooling2D, ResidualBlock, SeparableConv2D)
 from .params import ParamStore
 
 
@@ -110,13 +110,13 @@ class Net:
     def _plan(self):
         shape = self.input_shape
         execd: list[Layer] = []
-        # a Dense / Conv2D / DepthwiseConv2D / SeparableConv2D activation other than relu / linear runs as its
-        # own streaming launch right after the layer, unless it ends the model (softmax / sigmoid fold into
-        # the loss)
+        # a Dense / Conv2D / Conv2DTranspose / DepthwiseConv2D / SeparableConv2D activation other than relu /
+        # linear runs as its own streaming launch right after the layer, unless it ends the model (softmax /
+        # sigmoid fold into the loss)
         pending = []
         for j, l in enumerate(self.layers_all):
             pending.append(l)
-            act = getattr(l, "activation", None) if isinstance(l, (Dense, Conv2D, DepthwiseConv2D,
+            act = getattr(l, "activation", None) if isinstance(l, (Dense, Conv2D, Conv2DTranspose, DepthwiseConv2D,
                                                                    SeparableConv2D)) else None
             last = j == len(self.layers_all) - 1
             if act not in (None, "linear", "relu") and not (last and act in ("softmax", "sigmoid")):
@@ -330,11 +330,11 @@ class Net:
 
     # ------------------------------------------------------------------ buffers
     def wgrad_layers(self):
-        """The Conv2D leaves, those inside the fused conv blocks included."""
+        """The Conv2D and Conv2DTranspose leaves, those inside the fused conv blocks included."""
         convs = [c for l in self._all_leaf_layers()
                  for c in ((l.conv,) if isinstance(l, ConvPoolGemm) else
                            (l.conv1, l.conv2) if isinstance(l, KerasConvBlock) else (l,))]
-        return [l for l in convs if isinstance(l, Conv2D)]
+        return [l for l in convs if isinstance(l, (Conv2D, Conv2DTranspose))]
 
     def wgrad_ws_floats(self) -> int:
         """Split-m weight-gradient slabs: room for 4 slabs of the largest conv kernel (>= 16 MB).  A launch
@@ -815,6 +815,10 @@ class Net:
             if isinstance(l, DepthwiseConv2D):  # one input channel per output channel (a SeparableConv2D's
                 OH, OW, N = l.out_shape         # stages are leaves: this one and a 1x1 Conv2D)
                 f = 2 * OH * OW * N * l.kh * l.kw
+                return f * (3 if l.need_dx else 2)
+            if isinstance(l, Conv2DTranspose):  # every input pixel meets every tap (the useful multiplies)
+                H, W, C = l.in_shape
+                f = 2 * H * W * C * l.kh * l.kw * l.filters
                 return f * (3 if l.need_dx else 2)
             return 0
 

@@ -636,6 +636,131 @@ def dwconv_wgrad(dy, x, gw, gb, workspace, geom):
     return gw
 
 
+# ---- transposed convolution: the data gradient of the conv G from [B][OH][OW][F] to [B][H][W][Cin] with the
+# same kernel size, strides and padding; kernel = G's OHWI matrix [Cin][KH*KW*F].  The conv kernels run it
+# with their roles swapped (forward = G's data gradient, input gradient = G's forward, kernel gradient = G's
+# with x and dy exchanged).
+def deconv_geometry(B, H, W, Cin, F, kernel, strides, padding):
+    """[B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl] of a Keras Conv2DTranspose: 'valid' gives
+    H*sh + max(KH - sh, 0) rows, 'same' H*sh rows with G's TensorFlow 'same' top / left pads (no
+    output_padding, no dilation)."""
+    (kh, kw), (sh, sw) = _pair(kernel), _pair(strides)
+    if min(int(B), int(H), int(W), int(Cin), int(F), kh, kw, sh, sw) < 1:
+        raise ValueError(f"transposed conv: kernel {kh}x{kw} / strides {sh},{sw} / {F} filters do not fit a "
+                         f"{H}x{W}x{Cin} input")
+    if padding == "same":
+        OH, OW = H * sh, W * sw
+        (gh, gw), (pt, pl) = same_padding(OH, OW, kh, kw, (sh, sw))
+    elif padding == "valid":
+        OH, OW = H * sh + max(kh - sh, 0), W * sw + max(kw - sw, 0)
+        pt = pl = 0
+        gh, gw = conv_out_hw(OH, OW, kh, kw, (sh, sw), 0)
+    else:
+        raise ValueError(f"transposed conv padding {padding!r}")
+    if (gh, gw) != (H, W):
+        raise ValueError(f"transposed conv: no {kh}x{kw} / {sh},{sw} {padding!r} conv maps {OH}x{OW} to {H}x{W}")
+    return [int(B), int(H), int(W), int(Cin), int(F), OH, OW, kh, kw, sh, sw, pt, pl]
+
+
+def deconv_plans(geom, w, wt, has_bias=False, has_mask=False, ws_floats=0) -> dict:
+    """The kernel families (csrc/conv_plan.hip) the three launches of a transposed conv take: ``fwd`` (a
+    MODE_DGRAD launch), ``dgrad`` (a MODE_FWD launch) and ``wgrad``; {} without the native extension.  A bias
+    changes the forward's plan (the halo kernel refuses one)."""
+    m = native.get(build_if_missing=False)
+    if m is None:
+        return {}
+    B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl = geom
+    st, pd = (sh, sw), (pt, pl)
+    fwd = m.conv_plan(B * OH * OW, F, KH * KW * Cin, int(wt.shape[1]), _geom(H, W, Cin, OH, OW, KH, KW, st, pd),
+                      MODE_DGRAD, has_bias=bool(has_bias))
+    dg =m.conv_plan(B * H * W, Cin, KH * KW * F, int(w.shape[1]), _geom(OH, OW, F, H, W, KH, KW, st, pd), MODE_FWD,
+                     has_mask=bool(has_mask))
+    wg = m.wgrad_plan(B * H * W, Cin, KH * KW * F, Cin, 0, _geom(OH, OW, F, H, W, KH, KW, st, pd), MODE_FWD, False,
+                      int(ws_floats))
+    return {"fwd": fwd, "dgrad": dg, "wgrad": wg}
+
+
+def deconv_fwd(x, w, wt, bias, out, geom, relu=False):
+    """out [B][OH][OW][F] = [relu](transposed conv of NHWC ``x`` + bias).  ``w``: the kernel [Cin][KH*KW*F]
+    (CPU) ; ``wt``: its dgrad-layout bf16 copy [Fpad][pad(KH*KW*Cin)] (GPU)."""
+    B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl = geom
+    if x.is_cuda:
+        _C().igemm_fwd(x, wt, bias, None, out, B * OH * OW, F, KH * KW * Cin, wt.shape[1], 0, F,
+                       _geom(H, W, Cin, OH, OW, KH, KW, (sh, sw), (pt, pl)), MODE_DGRAD, bool(relu), 1.0)
+    else:
+        y = ref.conv_dgrad(x.reshape(B, H, W, Cin), w, (B, OH, OW, F), KH, KW, (sh, sw), (pt, pl))
+        if bias is not None:
+            y = y + bias.float()
+        if relu:
+            y = torch.relu(y)
+        out.copy_(y.reshape(out.shape))
+    return out
+
+
+def deconv_dgrad(dy, w, dx, geom, mask=None):
+    """dx [B][H][W][Cin] = G(dy) * relu'(mask): the forward of the conv G on the output gradient."""
+    B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl = geom
+    if dy.is_cuda:
+        _C().igemm_fwd(dy, w, None, mask, dx, B * H * W, Cin, KH * KW * F, w.shape[1], 0, Cin,
+                       _geom(OH, OW, F, H, W, KH, KW, (sh, sw), (pt, pl)), MODE_FWD, False, 1.0)
+    else:
+        g = ref.conv_fwd(dy.reshape(B, OH, OW, F), w, None, KH, KW, (sh, sw), (pt, pl), False, out_hw=(H, W))
+        if mask is not None:
+            g = g * (mask.float().reshape(g.shape) > 0)
+        dx.copy_(g.reshape(dx.shape))
+    return dx
+
+
+def channel_sum(dy, gb, workspace, scale=1.0):
+    """gb [C] = scale * sum over every leading position of dy [..][C], fp32, the same bits for the same inputs
+    (``workspace``: fp32 slab scratch of at least C floats, GPU only)."""
+    C = dy.shape[-1]
+    if dy.is_cuda:
+        _C().channel_sum(dy.contiguous(), gb, workspace, dy.numel() // C, C, float(scale))
+    else:
+        gb.copy_(dy.float().reshape(-1, C).sum(0) * scale)
+    return gb
+
+
+def deconv_wgrad(dy, x, gw, gb, workspace, geom):
+    """gw [Cin][KH*KW*F]: G's kernel gradient with x in the output-gradient slot and dy in the input slot (no
+    bias column: it would sum x); gb [F] = sum over positions of dy (None: no bias)."""
+    B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl = geom
+    conv_wgrad(x.reshape(B, H, W, Cin), dy.reshape(B, OH, OW, F), gw, None, workspace, KH, KW, (sh, sw), (pt, pl))
+    if gb is not None:
+        channel_sum(dy.reshape(B * OH * OW, F), gb, workspace)
+    return gw
+
+
+# ---- up-sampling (csrc/upsample.hip)
+UPSAMPLE_KINDS = ("nearest", "bilinear")
+
+
+def upsample2d_fwd(x, out, size, interpolation="nearest", half_pixel_centers=True):
+    """out [B][H*sh][W*sw][C]: every pixel repeated ('nearest'), or 'bilinear' sampling at
+    src = (dst + o) / s - o with o = 0.5 (``half_pixel_centers``, Keras / TF2) or 0 (tf.js)."""
+    B, H, W, C = x.shape
+    sh, sw = _pair(size)
+    bil = UPSAMPLE_KINDS.index(interpolation) == 1
+    if x.is_cuda:
+        _C().upsample2d_fwd(x.contiguous(), out, [B, H, W, C, sh, sw], bil, bool(half_pixel_centers))
+    else:
+        out.copy_(ref.upsample2d_fwd(x, (sh, sw), bil, half_pixel_centers).reshape(out.shape))
+    return out
+
+
+def upsample2d_bwd(dy, dx, size, interpolation="nearest", half_pixel_centers=True, mask=None):
+    """dx [B][H][W][C] = (sum of the dy pixels that read the pixel, weighted) * relu'(mask)."""
+    B, H, W, C = dx.shape
+    sh, sw = _pair(size)
+    bil = UPSAMPLE_KINDS.index(interpolation) == 1
+    if dy.is_cuda:
+        _C().upsample2d_bwd(dy.contiguous(), mask, dx, [B, H, W, C, sh, sw], bil, bool(half_pixel_centers))
+    else:
+        dx.copy_(ref.upsample2d_bwd(dy.reshape(B, H * sh, W * sw, C), (sh, sw), bil, half_pixel_centers, mask))
+    return dx
+
+
 def relu_bwd(y, dy, dx):
     if y.is_cuda:
         _C().relu_bwd(y, dy, dx)

@@ -123,6 +123,45 @@ def dwconv_wgrad(dy, x, geom, with_bias=True):
     return gw, gb
 
 
+# ---------------------------------------------------------------- up-sampling
+def upsample_matrix(n, s, bilinear=False, half_pixel_centers=True):
+    """[n*s][n] fp32 interpolation matrix of one axis, by the kernels' own index and weight arithmetic
+    (csrc/upsample.hip): nearest reads d // s; bilinear samples at src = (d + o) / s - o (o = 0.5: half-pixel
+    centres, Keras / TF2; o = 0: tf.js resizeBilinear), lower index max(floor(src), 0), upper index
+    min(ceil(src), n - 1), upper weight src - floor(src)."""
+    d = torch.arange(n * s)
+    A = torch.zeros(n * s, n, dtype=torch.float32)
+    if not bilinear:
+        A[d, d // s] = 1.0
+        return A
+    o = 0.5 if half_pixel_centers else 0.0
+    src = (d.float() + o) / float(s) - o
+    fl = torch.floor(src)
+    lo = fl.long().clamp(0, n - 1)
+    hi = torch.ceil(src).long().clamp(0, n - 1)
+    wt = src - fl
+    A.index_put_((d, lo), 1.0 - wt, accumulate=True)
+    A.index_put_((d, hi), wt, accumulate=True)
+    return A
+
+
+def upsample2d_fwd(x, size, bilinear=False, half_pixel_centers=True):
+    B, H, W, C = x.shape
+    Ah = upsample_matrix(H, size[0], bilinear, half_pixel_centers).to(x.device)
+    Aw = upsample_matrix(W, size[1], bilinear, half_pixel_centers).to(x.device)
+    return torch.einsum("ph,qw,bhwc->bpqc", Ah, Aw, x.float())
+
+
+def upsample2d_bwd(dy, size, bilinear=False, half_pixel_centers=True, mask=None):
+    B, OH, OW, C = dy.shape
+    Ah = upsample_matrix(OH // size[0], size[0], bilinear, half_pixel_centers).to(dy.device)
+    Aw = upsample_matrix(OW // size[1], size[1], bilinear, half_pixel_centers).to(dy.device)
+    dx = torch.einsum("ph,qw,bpqc->bhwc", Ah, Aw, dy.float())
+    if mask is not None:
+        dx = dx * (mask.float().reshape(dx.shape) > 0)
+    return dx
+
+
 def dense_fwd(x, w2d, bias, relu):
     N = bias.shape[0] if bias is not None else w2d.shape[0]
     K = x.shape[-1]
