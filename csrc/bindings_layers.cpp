@@ -414,6 +414,54 @@ void loss_grad_py(torch::Tensor logits, c10::optional<torch::Tensor> labels, c10
             "loss_grad");
 }
 
+// The launch plan of the image loss as a dict (no GPU needed): what the launcher will do for these sizes.
+py::dict image_loss_plan_py(int64_t B, int64_t E, bool aligned) {
+  using namespace pybind11::literals;
+  const dfa::ImageLossPlan p = dfa::image_loss_plan(B, E, aligned);
+  return py::dict("ok"_a = p.ok, "vec"_a = p.vec, "threads"_a = p.threads, "elems_per_wg"_a = p.elems_per_wg,
+                  "wgs_per_image"_a = p.wgs_per_image, "grid"_a = p.grid, "ws_floats"_a = p.ws_floats);
+}
+
+void image_loss_grad_py(torch::Tensor z, torch::Tensor targets, c10::optional<torch::Tensor> idx,
+                        c10::optional<torch::Tensor> dz, c10::optional<torch::Tensor> stats,
+                        c10::optional<torch::Tensor> ws, int64_t B, int64_t E, int64_t kind, int64_t out_act,
+                        double grad_scale, double target_scale, bool out_relu) {
+  TORCH_CHECK(B > 0 && E > 0 && E <= (1ll << 40), "image_loss_grad: B and E must be positive (E <= 2^40)");
+  TORCH_CHECK(kind >= 0 && kind <= dfa::kMetricSigmoidCE,
+              "image_loss_grad: the loss kind must be one of the mean kinds 0..5, got ", kind);
+  TORCH_CHECK(out_act == 0 || out_act == 2, "image_loss_grad: out_act is 0 (linear) or 2 (sigmoid)");
+  need(z, at::kBFloat16, "image_loss_grad z");
+  TORCH_CHECK(z.numel() == B * E, "image_loss_grad: z must hold [B][E]");
+  TORCH_CHECK(targets.is_cuda() && targets.is_contiguous(), "image_loss_grad: targets must be a contiguous GPU tensor");
+  const bool u8 = targets.scalar_type() == at::kByte;
+  TORCH_CHECK(u8 || targets.scalar_type() == at::kFloat, "image_loss_grad: targets must be fp32 or uint8");
+  TORCH_CHECK(targets.numel() % E == 0, "image_loss_grad: the target table must be [N][E]");
+  const int64_t nrows = targets.numel() / E;
+  const long long* ip = opt_ptr<const long long>(idx, at::kLong, "idx", B, "image_loss_grad: idx needs B entries");
+  TORCH_CHECK(nrows >= (ip ? 1 : B), "image_loss_grad: the target table needs B rows");
+  dfa::bf16* dp = nullptr;
+  if (has(dz)) {
+    need(*dz, at::kBFloat16, "image_loss_grad dz");
+    TORCH_CHECK(dz->numel() == B * E, "image_loss_grad: dz must hold [B][E]");
+    dp = reinterpret_cast<dfa::bf16*>(dz->data_ptr());
+  }
+  float* sp = opt_ptr<float>(stats, at::kFloat, "stats", 2, "image_loss_grad: stats needs 2 floats");
+  const dfa::ImageLossPlan p = dfa::image_loss_plan(B, E, false);  // grid and workspace do not depend on alignment
+  TORCH_CHECK(p.ok, "image_loss_grad: B * ceil(E / ", dfa::kImageLossElems, ") workgroups exceed 2^31 - 1");
+  float* wp = nullptr;
+  size_t wn = 0;
+  if (sp) {
+    TORCH_CHECK(has(ws), "image_loss_grad: stats needs a workspace of ", p.ws_floats, " floats");
+    wp = opt_ptr<float>(ws, at::kFloat, "workspace", p.ws_floats, "image_loss_grad: the workspace is too small");
+    wn = (size_t)ws->numel();
+  }
+  check_hip(dfa::image_loss_grad(reinterpret_cast<const dfa::bf16*>(z.data_ptr()),
+                                 u8 ? nullptr : targets.data_ptr<float>(), u8 ? targets.data_ptr<uint8_t>() : nullptr,
+                                 (float)target_scale, ip, nrows, dp, sp, wp, wn, B, E, (int)kind, (int)out_act,
+                                 out_relu ? 1 : 0, (float)grad_scale, cur_stream()),
+            "image_loss_grad");
+}
+
 static dfa::Pool2DGeom pool_geom(const std::vector<int64_t>& g) {
   TORCH_CHECK(g.size() == 12, "pool2d: geom = [B, H, W, C, OH, OW, ph, pw, sh, sw, pt, pl]");
   dfa::Pool2DGeom p{};
@@ -1076,6 +1124,14 @@ void bind_layers(py::module_& m) {
   m.def("sigmoid_ce", &sigmoid_ce_py, "sigmoid cross-entropy on logits vs one-hot labels (+ dlogits)");
   m.def("loss_grad", &loss_grad_py,
         "any lossesMap loss on act(logits) vs int labels or dense targets, optionally through idx (+ dlogits, stats)");
+  m.def("image_loss_grad", &image_loss_grad_py,
+        "a mean lossesMap loss on act(z) of a bf16 output map vs an fp32 / uint8 target table, optionally through "
+        "idx (+ dz, stats; fixed-order sums)",
+        py::arg("z"), py::arg("targets"), py::arg("idx"), py::arg("dz"), py::arg("stats"), py::arg("workspace"),
+        py::arg("B"), py::arg("E"), py::arg("kind"), py::arg("out_act"), py::arg("grad_scale"),
+        py::arg("target_scale") = 1.0, py::arg("out_relu") = false);
+  m.def("image_loss_plan", &image_loss_plan_py, "the launch plan of image_loss_grad", py::arg("B"), py::arg("E"),
+        py::arg("aligned") = true);
   m.def("pool2d_fwd", &pool2d_fwd_py, "general 2-D max / average pooling, any window / stride / padding");
   m.def("pool2d_bwd", &pool2d_bwd_py, "backward of pool2d_fwd (input-centric, no atomics)");
   m.def("dwconv_fwd", &dwconv_fwd_py, "depthwise conv forward, fp32 kernel [KH][KW][C*M] (csrc/dwconv.hip)");

@@ -790,6 +790,26 @@ hipError_t loss_grad(const float* z, const int* labels, const float* targets, co
                      bf16* dlogits, float* stats, int B, int C, int ldl, int ldt, int ldg, int kind, int out_act,
                      float grad_scale, hipStream_t st);
 
+// Fused per-pixel training loss of an image output (csrc/loss_image.hip): bf16 z [B][E], the mean kinds
+// (kMetricMSE .. kMetricSigmoidCE), out_act 0 linear / 2 sigmoid.  dz = grad_scale * dL_b/dz (bf16 [B][E]) and
+// stats[0] += sum_b L_b; both nullable.  out_relu: z is a fused-ReLU output, dz takes its relu' (z > 0) too.
+// Exactly one of t_f32 / t_u8 (t = u8 * target_scale), a table
+// [nrows][E]; image b reads row idx[b] (clamped) when idx is given, else row b.  stats needs a workspace of
+// image_loss_plan(...).ws_floats floats (per-workgroup partials, summed in a fixed order: bitwise reproducible).
+constexpr int kImageLossElems = 2048;  // elements of one image a workgroup covers
+struct ImageLossPlan {
+  bool ok;                  // the sizes are launchable (the workgroup index fits blockIdx.x)
+  bool vec;                 // a lane owns 8 adjacent elements: E % 8 == 0 and aligned base pointers
+  int threads, elems_per_wg;
+  long long wgs_per_image, grid, ws_floats;
+};
+// The one decision of a launch; ``aligned``: z / dz on 16 bytes, the targets on 16 (fp32) or 8 (uint8) bytes.
+ImageLossPlan image_loss_plan(long long B, long long E, bool aligned);
+hipError_t image_loss_grad(const bf16* z, const float* t_f32, const uint8_t* t_u8, float target_scale,
+                           const long long* idx, long long nrows, bf16* dz, float* stats, float* ws,
+                           size_t ws_floats, long long B, long long E, int kind, int out_act, int out_relu,
+                           float grad_scale, hipStream_t st);
+
 // Generic Keras layers (csrc/act.hip): standalone activations, sigmoid-CE loss, general pooling.
 enum ActKind {
   kActLinear = 0, kActRelu = 1, kActRelu6 = 2, kActSigmoid = 3, kActTanh = 4, kActElu = 5, kActSelu = 6,

@@ -78,6 +78,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="train this lossesMap entry (meanSquaredError, huberLoss, ...) against the one-hot labels "
                         "instead of the cross-entropy of the model's output; model = the loss the model.json's "
                         "training_config names")
+    p.add_argument("--target", default=None, choices=["input"],
+                   help="input = train a model whose output is an image (conv_autoencoder_mnist) against its own "
+                        "input: the per-pixel --loss reads the dataset through the step's index vector")
     p.add_argument("--graph", default=None, choices=["full", "split", "none"])
     p.add_argument("--save-dir", default=None, help="checkpoint directory: weights and optimizer state per version")
     p.add_argument("--resume", action="store_true")
@@ -288,9 +291,9 @@ def sync_optimizer(args, net) -> dict:
           "betas": (args.beta1, args.beta2), "eps": args.eps, "weight_decay": args.weight_decay}
     if args.optimizer == "model":
         from .models.keras import optimizer_from_keras
-        from .models.zoo import keras_cnn_topology
+        from .models.zoo import TOPOLOGIES
 
-        topo = getattr(net, "topology", None) or (keras_cnn_topology() if net.name == "keras_cnn" else None)
+        topo = getattr(net, "topology", None) or (TOPOLOGIES[net.name]() if net.name in TOPOLOGIES else None)
         oc = optimizer_from_keras(topo) if topo else None
         if oc is None:
             raise SystemExit(f"--optimizer model: model {net.name!r} carries no Keras training_config")
@@ -310,9 +313,9 @@ def sync_loss(args) -> str | None:
     loss = getattr(args, "loss", None)
     if loss == "model":
         from .models.keras import loss_from_keras
-        from .models.zoo import keras_cnn_topology
+        from .models.zoo import TOPOLOGIES
 
-        topo = keras_cnn_topology() if args.model == "keras_cnn" else None
+        topo = TOPOLOGIES[args.model]() if args.model in TOPOLOGIES else None
         loss = loss_from_keras(topo) if topo else None
         if loss is None:
             raise SystemExit(f"--loss model: model {args.model!r} carries no Keras training_config")
@@ -381,7 +384,15 @@ def run_sync(args) -> dict:
     rank, world, dev = env.rank, env.world_size, env.device
     log = _logger(args, f"Distributed Worker {rank}")
     faults = Faults(args, rank)
-    net = build_model(args.model, device=dev, seed=args.seed, loss=sync_loss(args))
+    try:
+        net = build_model(args.model, device=dev, seed=args.seed, loss=sync_loss(args))
+    except (ValueError, NotImplementedError) as e:  # an image-output model without / with an unfit --loss
+        raise SystemExit(f"--model {args.model}: {e}") from e
+    target = getattr(args, "target", None)
+    if getattr(net, "image_output", False) != (target == "input"):
+        raise SystemExit(f"--target input belongs to a model whose output is an image (conv_autoencoder_mnist); "
+                         f"--model {args.model} "
+                         + ("needs it" if getattr(net, "image_output", False) else "ends in class logits"))
     if net.loss is not None:
         log.log(f"training loss {net.loss} on the {net.final_act} output")
     x, y = _load_data(args, dev)
@@ -408,7 +419,7 @@ def run_sync(args) -> dict:
     # and epoch count, and a resumed job skips the steps already taken: it trains on exactly the batches an
     # uninterrupted job would have.
     ds = DistriDataset(x, y, {"batchSize": B, "epochs": args.epochs}, shuffle=True, seed=args.seed)
-    tr.bind_dataset(ds.x, ds.y, B, scale=scale)
+    tr.bind_dataset(ds.x, "input" if target == "input" else ds.y, B, scale=scale)
     if tr.min_updates is not None:  # K microbatches of the one FCFS stream per version (count barrier)
         g_rows, g_epochs = ds.index_stream(0, 1, device=dev, with_epochs=True)
         rows, row_epoch = fedsgd_rows(g_rows, tr.min_updates, rank, world, g_epochs)

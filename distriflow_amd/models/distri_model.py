@@ -179,7 +179,8 @@ def fetch_model(src: ModelSource, device=None, loss: Optional[str] = None) -> Ne
 
     if isinstance(src, Net) or callable(src):
         net = src if isinstance(src, Net) else src()
-        if loss is not None and net.loss != normalise_loss(loss, net.final_act):
+        want = loss if getattr(net, "image_output", False) else normalise_loss(loss, net.final_act)
+        if loss is not None and net.loss != want:
             raise ValueError(f"the Net trains loss={net.loss!r}; build it with loss={loss!r}")
         return net
     if isinstance(src, str):
@@ -216,7 +217,10 @@ class EngineModel(DistriModel):
                  strict_loss: bool = False, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-7,
                  train_compile_loss: bool = False):
         """``train_compile_loss``: minimise the compile loss itself (any lossesMap entry, csrc/loss.hip)
-        instead of the cross-entropy of the model's output; a 2-D floating ``y`` is then a dense target."""
+        instead of the cross-entropy of the model's output; a 2-D floating ``y`` is then a dense target.  A
+        model whose output is an image requires it: ``y`` is then a target map of the output's shape (``y = x``
+        for an autoencoder, csrc/loss_image.hip) and ``evaluate`` reports 0.0 for the accuracy, which is not
+        defined for an image."""
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         self._src = model
@@ -247,6 +251,9 @@ class EngineModel(DistriModel):
         so once when the compile loss differs, instead of silently training another loss."""
         if self.train_compile_loss:
             return  # the compile loss is the one minimised
+        if getattr(self.net, "image_output", False):
+            raise ValueError("a model whose output is an image needs EngineModel(train_compile_loss=True): there is "
+                             "no cross-entropy of class labels to train")
         loss = self.compile["loss"]
         trained = "sigmoidCrossEntropy" if getattr(self.net, "final_act", "") == "sigmoid" else "softmax cross-entropy"
         ok = loss == "sigmoidCrossEntropy" if trained == "sigmoidCrossEntropy" else loss in _CE_LOSSES
@@ -295,7 +302,18 @@ class EngineModel(DistriModel):
             if xx.dim() == len(net.input_shape):
                 xx = xx.unsqueeze(0)
             xx = xx.reshape((xx.shape[0],) + tuple(net.input_shape))
+        if y is None:  # predict: no targets
+            return xx, None
         y = y.to(net.device)
+        if getattr(net, "image_output", False):
+            # target maps of the output's shape ([B, H, W, C] or [B, E]); y = x for an autoencoder
+            if not self.train_compile_loss:
+                raise ValueError("a model whose output is an image needs EngineModel(train_compile_loss=True)")
+            if not y.is_floating_point():
+                raise ValueError(f"an image-output model trains on float target maps, got {y.dtype}")
+            if y.dim() == len(net.output_shape):
+                y = y.unsqueeze(0)
+            return xx, y.to(torch.float32).reshape((y.shape[0],) + tuple(net.output_shape))
         if self.train_compile_loss and net.loss is not None and y.dim() == 2 and y.is_floating_point():
             return xx, y.to(torch.float32)  # dense targets of the compile loss, as they stand
         if y.dim() > 1:  # one-hot labels (reference convention) -> class indices
@@ -331,7 +349,7 @@ class EngineModel(DistriModel):
 
     def predict(self, x) -> torch.Tensor:
         net = self._need()
-        xx, _ = self._prep(x, torch.zeros(1))
+        xx, _ = self._prep(x, None)
         return net.predict(xx)
 
     def evaluate(self, x, y) -> list[float]:
@@ -341,6 +359,12 @@ class EngineModel(DistriModel):
         xx, yy = self._prep(x, y)
         n = xx.shape[0]
         loss = self.compile["loss"]
+        if getattr(net, "image_output", False):
+            # the per-pixel training loss (the training kernel, stats only); accuracy is not defined for an image
+            out = [net._evaluate_image(xx, yy, 4096)]
+            if "accuracy" in self.compile["metrics"] or "acc" in self.compile["metrics"]:
+                out.append(0.0)
+            return out
         if net.is_gpu and loss in ops.METRIC_KINDS:
             z = net._forward_eval(xx.to(net.dtype) if not isinstance(xx, ops.GatherRef) else xx)
             if not hasattr(self, "_metric_buf") or self._metric_buf.device != z.device:
@@ -382,7 +406,8 @@ class EngineModel(DistriModel):
 
     @property
     def output_shape(self) -> list:
-        return [self._need().num_classes]
+        net = self._need()
+        return list(net.output_shape) if getattr(net, "image_output", False) else [net.num_classes]
 
 
 class DynamicModel(DistriModel):

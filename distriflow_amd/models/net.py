@@ -5,7 +5,9 @@ This is the engine behind ``DistriModel.fit`` / ``update`` (reference: Distribut
 ``tf.variableGrads(softmaxCE(predictOnBatch(x), y).mean())`` and update = per-tensor ``w -= lr*g``,
 /root/reference/src/common/models.ts:128-142).  Deliberate differences:
 the loss is a correct, fused softmax-cross-entropy on pre-softmax logits, and a trailing softmax
-activation is folded into it rather than executed.
+activation is folded into it rather than executed.  A model whose output is an image [H][W][C] (an
+autoencoder, a U-Net-style decoder) trains a per-pixel lossesMap loss on its output map instead
+(csrc/loss_image.hip), as the reference's DistributedDynamicModel.fit does for any lossesMap entry.
 """
 from __future__ import annotations
 
@@ -19,7 +21,8 @@ import torch
 from .. import ops
 from ..diagnostics import on as diag_on
 from .layers import (Activation, BatchNorm, Conv2D, Conv2DTranspose, ConvPoolGemm, Dense, DepthwiseConv2D, Dropout,
-                     Flatten, FusedConvPool, KerasConvBlock, Layer, MaxPooling2D, ResidualBlock, SeparableConv2D)
+                     Flatten, FusedConvPool, KerasConvBlock, Layer, MaxPooling2D, ResidualBlock, SeparableConv2D,
+                     UpSampling2D)
 from .params import ParamStore
 
 
@@ -157,14 +160,24 @@ class Net:
                     and KerasConvBlock.matches(execd[0], execd[1].conv)):
                 execd = [KerasConvBlock(execd[0], execd[1].conv, execd[1].pool)] + execd[2:]
         last = execd[-1]
+        self.image_output = False  # the model's output is a map [H][W][C] trained by a per-pixel loss
         if isinstance(last, Dense):
             if last.activation in ("softmax", "sigmoid"):
                 self.final_act = last.activation
             last.out_f32 = True
             if last.relu:
                 raise ValueError("the logits layer must not end in ReLU")
+        elif len(shape) == 3 and self._image_output_layer(last):
+            self.image_output = True
+            act = getattr(pending[-1], "activation", None)
+            if pending[-1] is last and act in ("softmax", "sigmoid"):
+                self.final_act = act  # folded into the loss, as on a Dense output
+            self._check_image_loss()
         else:
-            raise NotImplementedError("the last executed layer must be Dense (logits)")
+            raise NotImplementedError(f"the last executed layer must be Dense (logits) or a layer with an image "
+                                      f"output [H][W][C] (Conv2D, Conv2DTranspose, SeparableConv2D, DepthwiseConv2D, "
+                                      f"UpSampling2D, a merge graph, an Activation); got {type(last).__name__} with "
+                                      f"output shape {tuple(shape)}")
         # relu' bookkeeping + first-layer dgrad elision
         for j, l in enumerate(execd):
             l.need_dx = j > 0
@@ -191,12 +204,39 @@ class Net:
                 l.dx_bn_sinks = [prev]
         self.exec_layers = execd
         self.output_shape = shape
-        self.loss = normalise_loss(self.loss, self.final_act)
+        if not self.image_output:  # (an image output always keeps its loss: there is no default path)
+            self.loss = normalise_loss(self.loss, self.final_act)
         self.head_start = self._plan_head(execd) if self.fuse else None
         self.khead = self._plan_khead(execd) if self.fuse else False
         if self.khead:
             self.head_start = len(execd) - 2
         self.lenet_fused = self._plan_lenet(execd) if self.fuse else False
+
+    @staticmethod
+    def _image_output_layer(last) -> bool:
+        from .graph import GraphLayer
+
+        return isinstance(last, (Conv2D, Conv2DTranspose, SeparableConv2D, DepthwiseConv2D, UpSampling2D, GraphLayer,
+                                 Activation))
+
+    def _check_image_loss(self):
+        """An image output trains one of the six mean lossesMap kinds per pixel (csrc/loss_image.hip); the
+        constructor says why anything else cannot."""
+        if self.final_act == "softmax":
+            raise NotImplementedError("per-pixel softmax on an image output (segmentation) is not supported; end the "
+                                      "model in a linear or sigmoid map")
+        mean = sorted(k for k, v in ops.METRIC_KINDS.items() if v < ops.IMAGE_LOSS_KINDS)
+        if self.loss is None:
+            raise ValueError(f"a model whose output is an image [H][W][C] has no default loss: build it with loss= "
+                             f"one of {mean}")
+        from ..losses import get_loss
+
+        get_loss(self.loss)
+        if self.loss not in ops.METRIC_KINDS:
+            raise KeyError(f"loss {self.loss!r} is not trainable by the engine; available: {mean}")
+        if ops.METRIC_KINDS[self.loss] >= ops.IMAGE_LOSS_KINDS:
+            raise NotImplementedError(f"per-pixel softmax / categorical cross-entropy ({self.loss!r}) on an image "
+                                      f"output is not supported (class-map targets); use one of {mean}")
 
     def _plan_lenet(self, execd) -> bool:
         """True when the executed graph is exactly LeNet-5 (conv5x5x6 'same' + relu + pool, conv5x5x16 +
@@ -351,7 +391,14 @@ class Net:
         self.ws = Workspace(ws_wgrad, ws_bn)
         for l in self.exec_layers:
             l.alloc(B, self.device, self.dtype, self.ws)
-        self.dlogits = torch.empty((B, self.num_classes), dtype=self.dtype, device=self.device)
+        if self.image_output:
+            self.dlogits = torch.empty((B,) + tuple(self.output_shape), dtype=self.dtype, device=self.device)
+            E = self.dlogits[0].numel()
+            # per-workgroup loss partials of the image loss (summed in a fixed order)
+            self.loss_ws = (torch.empty(ops.image_loss_workspace_floats(B, E), dtype=torch.float32,
+                                        device=self.device) if self.is_gpu else None)
+        else:
+            self.dlogits = torch.empty((B, self.num_classes), dtype=self.dtype, device=self.device)
         self.stats = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.x_buf = torch.empty((B,) + self.input_shape, dtype=self.dtype, device=self.device)
         self.y_buf = torch.empty((B,), dtype=torch.int32, device=self.device)
@@ -397,7 +444,8 @@ class Net:
         self._bn_acc_dirty = True
 
     def forward(self, x, training: bool = False) -> torch.Tensor:
-        """Returns fp32 logits [B][classes] (a view of an engine buffer).  ``x`` is a tensor or an
+        """Returns fp32 logits [B][classes], or for an image output the bf16 map [B][H][W][C] before a folded
+        sigmoid (a view of an engine buffer).  ``x`` is a tensor or an
         :class:`ops.GatherRef` (rows of the HBM dataset; fused into the first layer when it can)."""
         self.bind(x.shape[0])
         if training:
@@ -436,11 +484,17 @@ class Net:
         for a model that ends in sigmoid, sigmoid cross-entropy against the one-hot labels.  A Net built
         with ``loss=`` (the general loss path) trains that lossesMap entry on its output instead, against int
         labels, dense fp32 targets [B, C], or an :class:`ops.LabelRef` / :class:`ops.TargetRef` read through
-        its index vector."""
+        its index vector.  A Net whose output is an image trains its ``loss=`` per pixel (csrc/loss_image.hip)
+        against target maps (:meth:`_image_target`); stats[1], the accuracy count, stays 0: it is not defined for
+        an image."""
         B = logits.shape[0]
         self.stats.zero_()
         gs = self._loss_scale(B) if grad_scale is None else grad_scale
-        if self.loss is not None:
+        if self.image_output:
+            target, idx, scale = self._image_target(labels, B)
+            ops.image_loss_grad(logits, target, self.loss, self.final_act, self.dlogits, self.stats, gs, idx=idx,
+                                target_scale=scale, workspace=self.loss_ws, out_relu=self.exec_layers[-1].relu)
+        elif self.loss is not None:
             target, idx = self._loss_target(labels)
             ops.loss_grad(logits, target, self.loss, self.final_act, self.dlogits, self.stats, gs, idx=idx)
         elif self.final_act == "sigmoid":
@@ -448,6 +502,38 @@ class Net:
         else:
             ops.softmax_ce(logits, labels, self.dlogits, self.stats, gs)
         return self.stats
+
+    def _image_target(self, labels, B, u8_scale=None):
+        """(table, idx, scale) of ops.image_loss_grad from what a step of an image-output Net was given: dense
+        fp32 maps [B, H, W, C] or [B, E], an :class:`ops.TargetRef` (fp32 or uint8 table, read through its index
+        vector) or an :class:`ops.GatherRef` (the uint8 input itself: an autoencoder)."""
+        E = 1
+        for d in self.output_shape:
+            E *= int(d)
+        if isinstance(labels, ops.TargetRef):
+            table, idx, scale = labels.targets, labels.idx, getattr(labels, "scale", 1.0)
+        elif isinstance(labels, ops.GatherRef):
+            table, idx, scale = labels.data, labels.idx, labels.scale
+        elif isinstance(labels, ops.LabelRef) or not isinstance(labels, torch.Tensor):
+            raise ValueError("an image-output model trains on target maps, not class labels")
+        elif labels.dtype == torch.uint8 and u8_scale is not None:  # evaluate: uint8 maps, t = u8 * u8_scale
+            table, idx, scale = labels, None, u8_scale
+        else:
+            if not labels.is_floating_point():
+                raise ValueError(f"an image-output model trains on float target maps of shape "
+                                 f"[B, {', '.join(map(str, self.output_shape))}], got {labels.dtype} "
+                                 f"{tuple(labels.shape)}")
+            table, idx, scale = (labels if labels.dtype == torch.float32 else labels.float()), None, 1.0
+        rows = int(table.shape[0]) if table.dim() else 0
+        if table.dim() < 2 or rows == 0 or table.numel() != rows * E or (
+                table.dim() > 2 and tuple(table.shape[1:]) != tuple(self.output_shape)):
+            raise ValueError(f"image targets must be [., {', '.join(map(str, self.output_shape))}] or [., {E}], got "
+                             f"{tuple(table.shape)}")
+        if idx is None and rows != B:
+            raise ValueError(f"{rows} target maps for {B} examples")
+        if table.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"an image target table must be fp32 or uint8, got {table.dtype}")
+        return table.contiguous(), idx, scale
 
     def _loss_target(self, labels):
         """(target, idx) of ops.loss_grad from what a general-loss step was given."""
@@ -484,7 +570,9 @@ class Net:
             return self._compute_gradients_lenet(x, labels, grad_ready)
         if self.head_start is not None:
             return self._compute_gradients_head(x, labels, grad_ready)
-        if self.loss is None:
+        if self.image_output:
+            self._image_target(labels, x.shape[0])  # a wrong target is reported before anything runs
+        elif self.loss is None:
             if isinstance(labels, ops.TargetRef) or (isinstance(labels, torch.Tensor) and labels.dim() == 2
                                                      and labels.is_floating_point()):
                 raise ValueError("dense targets need a Net built with loss= (the general loss path)")
@@ -717,10 +805,14 @@ class Net:
     @torch.no_grad()
     def evaluate(self, x, labels, batch_size: int = 4096):
         """-> (mean loss, accuracy) over the given examples (inference mode, chunked).  The loss is the
-        training loss: with ``loss=`` that lossesMap entry, ``labels`` int classes or dense [N, C] targets."""
+        training loss: with ``loss=`` that lossesMap entry, ``labels`` int classes or dense [N, C] targets.
+        For an image output ``labels`` are target maps [N, H, W, C] (float, or uint8 read with the scale 1/255
+        of the datasets) and the accuracy is 0.0: it is not defined for an image."""
         n = x.shape[0]
         loss = 0.0
         correct = 0.0
+        if self.image_output:
+            return self._evaluate_image(x, labels, batch_size), 0.0
         for s in range(0, n, batch_size):
             xb = x[s: s + batch_size].to(self.device, self.dtype)
             dense = self.loss is not None and labels.is_floating_point()
@@ -736,6 +828,27 @@ class Net:
             loss += float(st[0])
             correct += float(st[1])
         return loss / max(n, 1), correct / max(n, 1)
+
+    def _evaluate_image(self, x, targets, batch_size):
+        """Mean per-pixel training loss over the examples: the training kernel with dz=None."""
+        n = x.shape[0]
+        st = torch.zeros(2, dtype=torch.float32, device=self.device)
+        for s in range(0, n, batch_size):
+            xb = x[s: s + batch_size].to(self.device, self.dtype)
+            tb = targets[s: s + batch_size]
+            scale = 1.0
+            if tb.dtype == torch.uint8:
+                tb, scale = tb.to(self.device), 1.0 / 255.0
+            else:
+                tb = tb.to(self.device, torch.float32)
+            table, _, _ = self._image_target(tb, xb.shape[0], u8_scale=scale)
+            z = self._forward_eval(xb)
+            ws = None
+            if self.is_gpu:
+                ws = torch.empty(ops.image_loss_workspace_floats(z.shape[0], z[0].numel()), dtype=torch.float32,
+                                 device=self.device)
+            ops.image_loss_grad(z, table, self.loss, self.final_act, None, st, 1.0, target_scale=scale, workspace=ws)
+        return float(st[0]) / max(n, 1)
 
     def _forward_eval(self, xb):
         """Logits for any batch size WITHOUT rebinding: a bound engine (whose buffers a captured

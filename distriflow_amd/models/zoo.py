@@ -8,14 +8,19 @@
                     conv5x5x16 + relu, maxpool2, dense 120 relu, dense 84 relu, dense 10; 61,706 params
 * ``resnet18_cifar`` — ResNet-18 for CIFAR-10 (BASELINE.json configs[3]): 3x3 stem, 4 stages x 2 basic
                     blocks (64/128/256/512), global average pool, dense 10; 11.17M params
+* ``conv_autoencoder_mnist`` — a convolutional autoencoder for MNIST, 28x28x1 -> 28x28x1: conv3x3x16 s2 relu,
+                    conv3x3x32 s2 relu, conv-transpose 3x3x16 s2 relu, conv-transpose 3x3x1 s2 sigmoid ('same'
+                    throughout); 9,569 params.  Its output is an image: it trains a per-pixel loss
+                    (``loss=``; its Keras topology names binary_crossentropy = logLoss) against a target map,
+                    usually its own input.
 """
 from __future__ import annotations
 
 import json
 import os
 
-from .keras import layers_from_keras
-from .layers import (Activation, BatchNorm, Conv2D, Dense, Dropout, Flatten, GlobalAveragePooling2D,
+from .keras import keras_config_from_layers, layers_from_keras
+from .layers import (Activation, BatchNorm, Conv2D, Conv2DTranspose, Dense, Dropout, Flatten, GlobalAveragePooling2D,
                      MaxPooling2D, ResidualBlock)
 from .net import Net
 
@@ -66,11 +71,36 @@ def resnet18_cifar_layers(num_classes: int = 10):
     return ls, (32, 32, 3)
 
 
+def conv_autoencoder_mnist_layers():
+    return [
+        Conv2D(16, 3, 2, "same", "relu", name="conv2d_1"),
+        Conv2D(32, 3, 2, "same", "relu", name="conv2d_2"),
+        Conv2DTranspose(16, 3, 2, "same", "relu", name="conv2d_transpose_1"),
+        Conv2DTranspose(1, 3, 2, "same", "sigmoid", name="conv2d_transpose_2"),
+    ], (28, 28, 1)
+
+
+def conv_autoencoder_mnist_topology() -> dict:
+    """modelTopology of the autoencoder as Keras writes it: the Sequential config (keras_config_from_layers) and
+    the ``training_config`` it is compiled with, binary cross-entropy per pixel (``loss_from_keras``: logLoss)."""
+    layers, shape = conv_autoencoder_mnist_layers()
+    return {"model_config": keras_config_from_layers(layers, shape, name="conv_autoencoder_mnist"),
+            "training_config": {"loss": "binary_crossentropy", "metrics": [],
+                                "optimizer_config": {"class_name": "SGD",
+                                                     "config": {"lr": 0.01, "momentum": 0.0, "decay": 0.0,
+                                                                "nesterov": False}}}}
+
+
+# zoo models that carry a Keras topology (training_config: --loss model / --optimizer model)
+TOPOLOGIES = {"keras_cnn": keras_cnn_topology, "conv_autoencoder_mnist": conv_autoencoder_mnist_topology}
+
+
 MODELS = {
     "mlp_mnist": mlp_mnist_layers,
     "lenet5": lenet5_layers,
     "keras_cnn": keras_cnn_layers,
     "resnet18_cifar": resnet18_cifar_layers,
+    "conv_autoencoder_mnist": conv_autoencoder_mnist_layers,
 }
 
 

@@ -921,11 +921,14 @@ class LabelRef:
 
 class TargetRef:
     """Dense fp32 targets of a batch that has not been gathered: ``targets[idx]`` ([N, C] table, int64
-    batch indices).  :func:`loss_grad` reads through the index vector, so no gather launch exists."""
+    batch indices).  :func:`loss_grad` reads through the index vector, so no gather launch exists.
 
-    def __init__(self, targets, idx):
-        self.targets, self.idx = targets, idx
-        self.shape = (idx.shape[0], targets.shape[1])
+    For an image output (:func:`image_loss_grad`) the table is [N, ...] of the output's shape, fp32 or uint8;
+    a uint8 table is read as ``u8 * scale`` (the HBM dataset itself as an autoencoder's target)."""
+
+    def __init__(self, targets, idx, scale: float = 1.0):
+        self.targets, self.idx, self.scale = targets, idx, float(scale)
+        self.shape = (idx.shape[0],) + tuple(targets.shape[1:])
 
 
 def head_supported() -> bool:
@@ -1071,6 +1074,78 @@ def loss_grad(logits, target, loss: str, out_act, dlogits=None, stats=None, grad
     if stats is not None:
         stats[0] += terms.sum()
         stats[1] += (z.argmax(1) == ref_class).float().sum()
+    return stats
+
+
+IMAGE_LOSS_KINDS = 6  # the mean kinds of METRIC_KINDS, codes 0..5, are defined per pixel
+
+
+def image_loss_plan(B: int, E: int, aligned: bool = True) -> dict:
+    """The launch plan of :func:`image_loss_grad` for ``B`` images of ``E`` elements (csrc/loss_image.hip
+    image_loss_plan, the function its launcher reads; needs no GPU): ``ok``, ``vec`` (a lane owns 8 adjacent
+    elements; needs ``E % 8 == 0`` and ``aligned`` base pointers), ``threads``, ``elems_per_wg``,
+    ``wgs_per_image``, ``grid`` and ``ws_floats`` (the fp32 workspace the loss sum needs)."""
+    return dict(_C().image_loss_plan(int(B), int(E), bool(aligned)))
+
+
+def image_loss_workspace_floats(B: int, E: int) -> int:
+    return int(image_loss_plan(B, E)["ws_floats"])
+
+
+def _image_loss_codes(loss: str, out_act):
+    kind = METRIC_KINDS[loss]
+    act = _out_act_code(out_act)
+    if act == 1 or kind >= IMAGE_LOSS_KINDS:
+        raise NotImplementedError(f"per-pixel softmax and class-map targets are not supported: loss {loss!r} with "
+                                  f"output activation {out_act!r} on an image output (use one of the mean losses "
+                                  f"{sorted(k for k, v in METRIC_KINDS.items() if v < IMAGE_LOSS_KINDS)} on a "
+                                  f"linear or sigmoid output)")
+    return kind, act
+
+
+def image_loss_grad(z, target, loss: str, out_act, dz=None, stats=None, grad_scale=1.0, idx=None, target_scale=1.0,
+                    workspace=None, out_relu=False):
+    """A mean ``lossesMap`` loss (METRIC_KINDS codes 0..5) between ``act(z)`` and a target map, for a model whose
+    output is an image: ``z`` [B, ...] (bf16 on the GPU, any trailing shape, viewed as [B][E]), per-example loss
+    L_b = mean over the E elements.  dz = grad_scale * dL_b/dz (same shape as ``z``); stats[0] += sum_b L_b
+    (stats[1], the accuracy count, is not defined for an image and is left alone).  ``target``: an fp32 table
+    [N, ...], or a uint8 table read as ``u8 * target_scale``; image b reads ``target[idx[b]]`` (``idx`` int64 [B],
+    clamped to the table) or row b.  ``out_act``: "linear" | "sigmoid".  ``out_relu``: ``z`` is the output of a
+    fused ReLU (a model that ends in one), whose relu' (z > 0) multiplies dz.  One streaming launch on the GPU
+    (csrc/loss_image.hip) plus the fixed-order sum of its per-workgroup partials in ``workspace`` (fp32,
+    :func:`image_loss_workspace_floats`; required with ``stats``): the loss sum is bitwise reproducible.  The CPU
+    path is the same closed forms in fp32 torch."""
+    kind, act = _image_loss_codes(loss, out_act)
+    B = int(z.shape[0])
+    E = int(z.numel() // max(B, 1))
+    if target.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"image targets must be fp32 or uint8, got {target.dtype}")
+    if target.dim() < 1 or target.numel() % E or target.numel() // E != target.shape[0]:
+        raise ValueError(f"image targets must be [N, ...] with {E} elements per row, got {tuple(target.shape)}")
+    N = int(target.shape[0])
+    if N < (1 if idx is not None else B):
+        raise ValueError(f"{N} target rows for {B} images")
+    if dz is not None and dz.numel() != z.numel():
+        raise ValueError(f"dz must have the shape of z {tuple(z.shape)}, got {tuple(dz.shape)}")
+    if z.is_cuda:
+        if stats is not None and workspace is None:
+            raise ValueError("image_loss_grad: stats needs a workspace (ops.image_loss_workspace_floats)")
+        _C().image_loss_grad(z, target, idx, dz, stats, workspace if stats is not None else None, B, E, kind, act,
+                             float(grad_scale), float(target_scale), bool(out_relu))
+        return stats
+    zz = z.reshape(B, E).float()
+    tab = target.reshape(N, E)
+    tt = (tab if idx is None else tab.index_select(0, idx.long().clamp(0, N - 1)))[:B]
+    t = tt.float() * float(target_scale) if target.dtype == torch.uint8 else tt
+    p = torch.sigmoid(zz) if act == 2 else zz
+    terms, g = _loss_terms(kind, p, t)
+    if dz is not None:
+        d = g * p * (1 - p) if act == 2 else g
+        if out_relu:
+            d = d * (zz > 0)
+        dz.copy_((d * grad_scale).to(dz.dtype).reshape(dz.shape))
+    if stats is not None:
+        stats[0] += terms.sum()
     return stats
 
 

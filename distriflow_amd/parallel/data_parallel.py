@@ -39,6 +39,10 @@ def require_sgd(optimizer: str, who: str, why: str):
 
 def require_default_loss(net, who: str):
     """The device parameter-server engines train classification with the model's cross-entropy only."""
+    if getattr(net, "image_output", False):
+        raise NotImplementedError(f"{who} trains the model's cross-entropy on class labels only; this net's output "
+                                  f"is an image {tuple(net.output_shape)} trained by a per-pixel loss "
+                                  f"(loss={net.loss!r}): use DataParallelTrainer")
     if getattr(net, "loss", None) is not None:
         raise NotImplementedError(f"{who} trains the model's cross-entropy on class labels only; this net was "
                                   f"built with loss={net.loss!r} (the general loss path)")
@@ -414,19 +418,53 @@ class DataParallelTrainer:
 
     def train_step(self, x: torch.Tensor, y: torch.Tensor):
         """Eager step on an explicit batch; returns device stats [loss_sum, correct].  ``y``: int labels, or
-        dense fp32 targets [B, C] when the net was built with ``loss=`` (the general loss path)."""
+        dense fp32 targets [B, C] when the net was built with ``loss=`` (the general loss path), or target maps
+        [B, H, W, C] for a net whose output is an image."""
         self.steps += 1
         return self._step_body(x, y)
 
     # ------------------------------------------------------------------ graph-captured step over an HBM dataset
-    def bind_dataset(self, data: torch.Tensor, labels: torch.Tensor, batch_size: int, scale: float = 1.0):
+    def bind_dataset(self, data: torch.Tensor, labels, batch_size: int, scale: float = 1.0,
+                     target_scale: Optional[float] = None):
         """Attach an HBM-resident dataset (uint8/bf16 [N, ...], int32 labels); steps then take index batches.
         ``batch_size``: rows per step per rank; with ``min_updates_per_version`` it is the MICROBATCH size
         and a step takes ``micro_per_rank[rank]`` microbatches (their rows concatenated).  A net built with
         ``loss=`` (the general loss path) also takes a float [N, C] target table as ``labels``: the loss
-        kernel reads its rows through the step's index vector (no gather launch)."""
-        self.dense_targets = labels.is_floating_point()
-        if self.dense_targets:
+        kernel reads its rows through the step's index vector (no gather launch).  A net whose output is an
+        image takes a target table of the output's shape as ``labels``: float [N, H, W, C], uint8 read as
+        ``u8 * target_scale``, or the string ``"input"``: the uint8 ``data`` itself with ``scale`` (an
+        autoencoder; no second table, no gather launch)."""
+        self.target_scale = 1.0
+        image = getattr(self.net, "image_output", False)
+        if isinstance(labels, str):
+            if labels != "input":
+                raise ValueError(f"labels must be a tensor or the string 'input', got {labels!r}")
+            if not image:
+                raise ValueError("labels='input' needs a net whose output is an image (an autoencoder)")
+            if data.dtype != torch.uint8:
+                raise ValueError(f"labels='input' reads the uint8 dataset as the target; data is {data.dtype}")
+            labels, target_scale = data, scale
+        if image:
+            out = tuple(self.net.output_shape)
+            E = 1
+            for d in out:
+                E *= int(d)
+            if labels.dim() < 2 or (tuple(labels.shape[1:]) != out and tuple(labels.shape[1:]) != (E,)):
+                raise ValueError(f"the target table must be [N, {', '.join(map(str, out))}] (the net's output), got "
+                                 f"{tuple(labels.shape)}")
+            if labels.dtype == torch.uint8:
+                if target_scale is None:
+                    raise ValueError("a uint8 target table needs target_scale= (t = u8 * target_scale)")
+                self.target_scale = float(target_scale)
+            elif not labels.is_floating_point():
+                raise ValueError(f"an image-output net trains on float or uint8 target maps, got {labels.dtype}")
+            if self.preprocess_callbacks:
+                raise NotImplementedError("preprocess callbacks with a dense target table")
+            self.dense_targets = True
+            labels = labels.contiguous() if labels.dtype == torch.uint8 else labels.to(torch.float32).contiguous()
+        else:
+            self.dense_targets = labels.is_floating_point()
+        if self.dense_targets and not image:
             if getattr(self.net, "loss", None) is None:
                 raise ValueError("a float target table needs a net built with loss= (the general loss path)")
             if labels.dim() != 2 or labels.shape[1] != self.net.num_classes:
@@ -499,8 +537,10 @@ class DataParallelTrainer:
             return
         if getattr(self.net, "loss", None) is not None:
             # the loss kernel reads labels / dense targets through the index vector: no gather launch
-            ref = ops.TargetRef if self.dense_targets else ops.LabelRef
-            self.yb = ref(self.labels, self.idx)
+            if self.dense_targets:
+                self.yb = ops.TargetRef(self.labels, self.idx, getattr(self, "target_scale", 1.0))
+            else:
+                self.yb = ops.LabelRef(self.labels, self.idx)
             if not isinstance(self.xb, ops.GatherRef):
                 ops.gather_batch(self.data, None, self.idx, self.xb, None, self.scale)
             return
