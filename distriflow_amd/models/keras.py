@@ -22,6 +22,7 @@ Keras 2.1.4 Sequential (/root/reference/experiment/mnist/model.json:1).  Support
 """
 from __future__ import annotations
 
+from ..ops.geometry import pair as _pair
 from .graph import GraphLayer, Merge, split_chain
 from .layers import (Activation, AveragePooling2D, BatchNorm, Conv2D, Conv2DTranspose, Dense, DepthwiseConv2D, Dropout,
                      Flatten, GlobalAveragePooling2D, GlobalMaxPooling2D, Layer, MaxPooling2D, SeparableConv2D,
@@ -74,10 +75,6 @@ def _graph_order(layer_cfgs: list, model_cfg: dict) -> tuple:
 
     visit(name_of(outs[0]))
     return [by_name[n] for n in order], parents
-
-
-def _pair(v) -> tuple:
-    return (int(v[0]), int(v[1])) if isinstance(v, (list, tuple)) else (int(v), int(v))
 
 
 def _init_name(cfg, key: str = "kernel_initializer"):

@@ -25,6 +25,7 @@ import torch
 
 from .. import ops
 from ..diagnostics import on as diag_on
+from ..ops.geometry import ConvGeom, DwGeom, PoolGeom, pair
 from .params import ParamSpec, dgrad_shape, primary_kpad
 
 
@@ -171,64 +172,79 @@ class Dense(Layer):
         return {"units": self.units, "activation": self.activation, "use_bias": self.use_bias}
 
 
-class Conv2D(Layer):
-    """NHWC conv, kernel stored OHWI [Cout][KH*KW*Cin] (Keras HWIO converted at I/O)."""
+class _ConvLike(Layer):
+    """What Conv2D, DepthwiseConv2D and Conv2DTranspose share: kernel size and strides, the padding and
+    activation checks, the parameter names, one geometry descriptor per batch size (``descriptor``, built by
+    ``alloc``) and backward = weights, then data."""
     has_params = True
+    # parameter names: under ``owner_name`` when set (the pointwise stage of a SeparableConv2D carries Keras' names)
+    kernel_suffix, owner_name = "kernel", None
+    kernel_name = property(lambda self: f"{self.owner_name or self.name}/{self.kernel_suffix}")
+    bias_name = property(lambda self: f"{self.owner_name or self.name}/bias")
+    _ks = property(lambda self: ((self.kh, self.kw), (self.sh, self.sw)))
+
+    def __init__(self, name, kernel_size, strides, padding, activation, use_bias, explicit_padding=False):
+        super().__init__(name)
+        self.kh, self.kw = pair(kernel_size)
+        self.sh, self.sw = pair(strides)
+        if padding not in ("valid", "same") and not explicit_padding:
+            raise NotImplementedError(f"{type(self).__name__} padding {padding!r}")
+        self.padding, self.activation, self.use_bias = padding, activation, use_bias
+        if activation == "relu":
+            self.relu = True
+        elif activation not in ops.ACT_KINDS:
+            raise NotImplementedError(f"{type(self).__name__} activation {activation!r}")
+
+    def can_fuse_relu(self):
+        return True
+
+    def alloc(self, B, device, dtype, ws):
+        super().alloc(B, device, dtype, ws)
+        self.ws = ws
+        self.g = self.descriptor(B)
+
+    def _bias(self, grad=False):
+        if not self.use_bias:
+            return None
+        return self.store.gradient(self.bias_name) if grad else self.store[self.bias_name]
+
+    def backward(self, dy):
+        self.backward_weights(dy)
+        return self.backward_data(dy)
+
+
+class Conv2D(_ConvLike):
+    """NHWC conv, kernel stored OHWI [Cout][KH*KW*Cin] (Keras HWIO converted at I/O)."""
 
     def __init__(self, filters: int, kernel_size=(3, 3), strides=(1, 1), padding="valid", activation="linear",
                  use_bias=True, name=None, kernel_initializer="glorot_uniform"):
-        super().__init__(name or "conv2d")
+        super().__init__(name or "conv2d", kernel_size, strides, padding, activation, use_bias, explicit_padding=True)
         self.filters = int(filters)
-        self.kh, self.kw = ops._pair(kernel_size)
-        self.sh, self.sw = ops._pair(strides)
         # k / stride / pad: the square kernel, single stride and symmetric padding of a regular conv (what
         # the fused and specialised paths match on); None when the geometry is not regular, which then runs
         # on the generic implicit-GEMM kernels (csrc/igemm.hip) with per-axis strides and top/left padding
         self.k = self.kh if self.kh == self.kw else None
         self.stride = self.sh if self.sh == self.sw else None
-        self.padding = padding
-        self.activation = activation
-        self.use_bias = use_bias
         self.kernel_initializer = kernel_initializer
-        if activation == "relu":
-            self.relu = True
-        elif activation not in ops.ACT_KINDS:
-            raise NotImplementedError(f"Conv2D activation {activation!r}")
 
-    # parameter names (the pointwise stage of a SeparableConv2D carries Keras' names for it)
-    @property
-    def kernel_name(self) -> str:
-        return f"{self.name}/kernel"
-
-    @property
-    def bias_name(self) -> str:
-        return f"{self.name}/bias"
+    def descriptor(self, B) -> ConvGeom:
+        """The launches' geometry at batch size ``B`` (geometry.window: 'valid', Keras 'same', or explicit)."""
+        return ConvGeom.build(B, *self.in_shape, self.filters, *self._ks, self.padding)
 
     def build(self, in_shape):
-        H, W, C = in_shape
-        self.in_shape = (H, W, C)
-        if self.padding == "same":
-            (OH, OW), self.pads = ops.same_padding(H, W, self.kh, self.kw, (self.sh, self.sw))
-        else:
-            self.pads = (0, 0) if self.padding == "valid" else ops._pair(self.padding)
-            OH, OW = ops.conv_out_hw(H, W, self.kh, self.kw, (self.sh, self.sw), self.pads)
-        if OH < 1 or OW < 1:
-            raise ValueError(f"Conv2D {self.name}: input {H}x{W} too small for kernel {self.kh}x{self.kw}")
-        sym = (OH, OW) == ops.conv_out_hw(H, W, self.kh, self.kw, (self.sh, self.sw), self.pads)
-        self.pad = self.pads[0] if sym and self.pads[0] == self.pads[1] else None
-        self.regular = self.k is not None and self.stride is not None and self.pad is not None
-        self.out_shape = (OH, OW, self.filters)
+        self.in_shape = tuple(in_shape)
+        g = self.descriptor(1)
+        self.pads = g.pad
+        self.pad = g.pt if g.symmetric and g.pt == g.pl else None
+        self.regular = g.regular
+        self.out_shape = (g.OH, g.OW, self.filters)
         return self.out_shape
 
     @property
     def geom(self):
         """(KH, KW, stride, pad) as the conv ops take them: ints when regular, else per-axis tuples."""
-        if self.regular:
-            return self.k, self.k, self.stride, self.pad
-        return self.kh, self.kw, (self.sh, self.sw), self.pads
-
-    def can_fuse_relu(self):
-        return True
+        r = self.regular
+        return (self.k, self.k, self.stride, self.pad) if r else (self.kh, self.kw, (self.sh, self.sw), self.pads)
 
     def specs(self):
         H, W, C = self.in_shape
@@ -250,18 +266,13 @@ class Conv2D(Layer):
             return False
         key = (dgrad, mode, two, has_res, has_mask)
         if key not in self._bacc_cache:
-            H, W, C = self.in_shape
-            OH, OW, N = self.out_shape
             kp = dgrad_kpad_of(self) if dgrad else primary_kpad_of(self)
-            self._bacc_cache[key] = ops.conv_bacc_ok(self._B, H, W, C, OH, OW, N, self.k, self.k, self.stride, self.pad,
-                                                     kp, dgrad=dgrad, mode=mode, two=two, has_res=has_res,
+            self._bacc_cache[key] = ops.conv_bacc_ok(*self.g.args, kp, dgrad=dgrad, mode=mode, two=two, has_res=has_res,
                                                      has_mask=has_mask)
         return self._bacc_cache[key]
 
     def alloc(self, B, device, dtype, ws):
         super().alloc(B, device, dtype, ws)
-        self.ws = ws
-        self._B = B
         self._bacc_cache = {}
 
     def forward(self, x, training, bn: Optional["BatchNorm"] = None):
@@ -269,13 +280,12 @@ class Conv2D(Layer):
         statistics come from this launch when it can: the epilogue accumulates their sums (csrc/bn_acc.h)
         -- no statistics pass over the output."""
         self.x = x
-        st = self.store
-        b = st[self.bias_name] if self.use_bias else None
         bn = bn if bn is not None else self.fwd_bn
         bacc = None
         if bn is not None and training and bn.acc_on and self.bacc_ok(False, 0):
             bacc = dict(acc=bn.acc, mode=0)
-        ops.conv_fwd(x, st.weight(self.kernel_name), b, self.out, *self.geom, relu=self.relu, bacc=bacc)
+        ops.conv_fwd(x, self.store.weight(self.kernel_name), self._bias(), self.out, g=self.g, relu=self.relu,
+                     bacc=bacc)
         if bacc is not None:
             bn.x = self.out
             bn._fwd_acc_ready = True
@@ -289,11 +299,9 @@ class Conv2D(Layer):
         return self.backward_data(dy, residual, residual_mask, dx_mask)
 
     def backward_weights(self, dy):
-        st = self.store
-        kn = self.kernel_name
-        gb = st.gradient(self.bias_name) if self.use_bias else None
-        dy = dy.reshape((dy.shape[0],) + self.out_shape)  # (a Dense above a Flatten hands down [B][OH * OW * N])
-        ops.conv_wgrad(dy, self.x, st.grad_matrix(kn), gb, self.ws.wgrad, *self.geom)
+        dy = dy.reshape(self.g.y_shape)  # (a Dense above a Flatten hands down [B][OH * OW * N])
+        ops.conv_wgrad(dy, self.x, self.store.grad_matrix(self.kernel_name), self._bias(grad=True), self.ws.wgrad,
+                       g=self.g)
 
     def backward_data(self, dy, residual=None, residual_mask=None, dx_mask=None, bn_acc: Optional[list] = None):
         """``bn_acc``: the (one or two) BatchNorms whose output gradient this data gradient IS (relu' applied
@@ -311,9 +319,8 @@ class Conv2D(Layer):
             if len(bn_acc) == 2:
                 b1 = bn_acc[1]
                 bacc.update(acc2=b1.acc_b, x2=b1.x, mean2=b1.mean, invstd2=b1.invstd)
-        dy = dy.reshape((dy.shape[0],) + self.out_shape)
-        ops.conv_dgrad(dy, st.weight(kn), st.weight_t(kn), self.dx, *self.geom, mask=mask, residual=residual,
-                       residual_mask=residual_mask, bacc=bacc)
+        ops.conv_dgrad(dy.reshape(self.g.y_shape), st.weight(kn), st.weight_t(kn), self.dx, g=self.g, mask=mask,
+                       residual=residual, residual_mask=residual_mask, bacc=bacc)
         if bacc is not None:
             for b in bn_acc:
                 b._bwd_acc_ready = True
@@ -326,55 +333,30 @@ class Conv2D(Layer):
                 "activation": self.activation, "use_bias": self.use_bias}
 
 
-class DepthwiseConv2D(Layer):
+class DepthwiseConv2D(_ConvLike):
     """Keras DepthwiseConv2D: every input channel convolved with its own ``depth_multiplier`` filters (output
     channel co reads input channel co // depth_multiplier).  Any kernel size / strides pair, 'valid' or
     'same' (the odd pixel of padding goes bottom / right).  The kernel is stored [KH][KW][C*M] -- Keras'
     ``depthwise_kernel`` [KH, KW, C, M] flattened -- as a flat fp32 parameter the kernels read straight from
     the master (csrc/dwconv.hip): it is a few tens of KB, so there is no bf16 compute copy."""
-    has_params = True
+    kernel_suffix = "depthwise_kernel"
 
     def __init__(self, kernel_size=(3, 3), strides=(1, 1), padding="valid", depth_multiplier=1, activation="linear",
                  use_bias=True, name=None, depthwise_initializer="glorot_uniform"):
-        super().__init__(name or "depthwise_conv2d")
-        self.kh, self.kw = ops._pair(kernel_size)
-        self.sh, self.sw = ops._pair(strides)
-        if padding not in ("valid", "same"):
-            raise NotImplementedError(f"DepthwiseConv2D padding {padding!r}")
-        self.padding = padding
+        super().__init__(name or "depthwise_conv2d", kernel_size, strides, padding, activation, use_bias)
         self.depth_multiplier = int(depth_multiplier)
         if self.depth_multiplier < 1:
             raise ValueError("depth_multiplier must be >= 1")
-        self.activation = activation
-        self.use_bias = use_bias
         self.depthwise_initializer = depthwise_initializer
-        if activation == "relu":
-            self.relu = True
-        elif activation not in ops.ACT_KINDS:
-            raise NotImplementedError(f"DepthwiseConv2D activation {activation!r}")
 
-    @property
-    def kernel_name(self) -> str:
-        return f"{self.name}/depthwise_kernel"
-
-    @property
-    def bias_name(self) -> str:
-        return f"{self.name}/bias"
+    def descriptor(self, B) -> DwGeom:
+        return DwGeom.build(B, *self.in_shape, self.depth_multiplier, *self._ks, self.padding)
 
     def build(self, in_shape):
-        H, W, C = in_shape
-        self.in_shape = (H, W, C)
-        g = ops.dwconv_geometry(1, H, W, C, self.depth_multiplier, (self.kh, self.kw), (self.sh, self.sw), self.padding)
-        self.out_shape = (g[5], g[6], C * self.depth_multiplier)
+        self.in_shape = tuple(in_shape)
+        g = self.descriptor(1)
+        self.out_shape = (g.OH, g.OW, g.C * g.M)
         return self.out_shape
-
-    def _geom(self, B):
-        H, W, C = self.in_shape
-        return ops.dwconv_geometry(B, H, W, C, self.depth_multiplier, (self.kh, self.kw), (self.sh, self.sw),
-                                   self.padding)
-
-    def can_fuse_relu(self):
-        return True
 
     def specs(self):
         CO, M = self.out_shape[2], self.depth_multiplier
@@ -385,33 +367,21 @@ class DepthwiseConv2D(Layer):
             s.append(ParamSpec(self.bias_name, (CO,), "vector", init="zeros"))
         return s
 
-    def alloc(self, B, device, dtype, ws):
-        super().alloc(B, device, dtype, ws)
-        self.ws = ws
-
     def forward(self, x, training):
         self.x = x
-        st = self.store
-        b = st[self.bias_name] if self.use_bias else None
-        ops.dwconv_fwd(x, st[self.kernel_name], b, self.out, self._geom(x.shape[0]), relu=self.relu)
+        ops.dwconv_fwd(x, self.store[self.kernel_name], self._bias(), self.out, self.g, relu=self.relu)
         return self.out
 
     def backward_weights(self, dy):
-        st = self.store
-        gb = st.gradient(self.bias_name) if self.use_bias else None
-        ops.dwconv_wgrad(dy.reshape(self.out.shape), self.x, st.gradient(self.kernel_name), gb, self.ws.wgrad,
-                         self._geom(self.x.shape[0]))
+        ops.dwconv_wgrad(dy.reshape(self.out.shape), self.x, self.store.gradient(self.kernel_name),
+                         self._bias(grad=True), self.ws.wgrad, self.g)
 
     def backward_data(self, dy):
         if not self.need_dx:
             return None
-        ops.dwconv_dgrad(dy.reshape(self.out.shape), self.store[self.kernel_name], self.dx, self._geom(self.x.shape[0]),
+        ops.dwconv_dgrad(dy.reshape(self.out.shape), self.store[self.kernel_name], self.dx, self.g,
                          mask=self.x if self.in_relu else None)
         return self.dx
-
-    def backward(self, dy):
-        self.backward_weights(dy)
-        return self.backward_data(dy)
 
     def config(self):
         return {"kernel_size": [self.kh, self.kw], "strides": [self.sh, self.sw], "padding": self.padding,
@@ -421,17 +391,11 @@ class DepthwiseConv2D(Layer):
 class _PointwiseConv(Conv2D):
     """The 1x1 stage of a SeparableConv2D: a Conv2D under Keras' parameter names for it."""
 
+    kernel_suffix = "pointwise_kernel"
+
     def __init__(self, owner_name: str, *args, **kw):
         super().__init__(*args, **kw)
         self.owner_name = owner_name
-
-    @property
-    def kernel_name(self) -> str:
-        return f"{self.owner_name}/pointwise_kernel"
-
-    @property
-    def bias_name(self) -> str:
-        return f"{self.owner_name}/bias"
 
 
 class SeparableConv2D(Layer):
@@ -495,56 +459,31 @@ class SeparableConv2D(Layer):
                 "depth_multiplier": d.depth_multiplier, "activation": self.activation, "use_bias": self.use_bias}
 
 
-class Conv2DTranspose(Layer):
+class Conv2DTranspose(_ConvLike):
     """Keras Conv2DTranspose: the data gradient of the conv G from [OH][OW][filters] to the input [H][W][Cin]
-    with the same kernel size, strides and padding ('valid': H*sh + max(KH - sh, 0) rows; 'same': H*sh rows,
-    G's TensorFlow 'same' pads; no output_padding, no dilation).  The kernel is stored as G's OHWI matrix
-    [Cin][KH][KW][filters] (Keras [KH, KW, filters, Cin] permuted at I/O), so the conv kernels run the three
-    passes with their roles swapped: forward = G's data gradient on the dgrad-layout copy (bias and ReLU in
-    its epilogue), input gradient = G's forward (relu' of the input as its epilogue mask), kernel gradient =
-    G's with x and dy exchanged; the bias gradient is a channel sum of dy (csrc/upsample.hip).
+    with the same kernel size, strides and padding (ConvGeom.transposed: 'valid' gives H*sh + max(KH - sh, 0)
+    rows, 'same' H*sh rows with G's TensorFlow 'same' pads; no output_padding, no dilation).  The kernel is
+    stored as G's OHWI matrix [Cin][KH][KW][filters] (Keras [KH, KW, filters, Cin] permuted at I/O), so the
+    conv kernels run G's three launches with their roles swapped (ConvGeom.t_fwd): the forward reads the
+    dgrad-layout copy, with bias and ReLU in its epilogue; the input gradient takes relu' of the input as its
+    epilogue mask; the bias gradient is a channel sum of dy (csrc/upsample.hip).
     Deliberately not a Conv2D: the conv+pool fusions, the BatchNorm-sum wiring and the checkpoint layouts
     match on that class."""
-    has_params = True
 
     def __init__(self, filters: int, kernel_size=(3, 3), strides=(1, 1), padding="valid", activation="linear",
                  use_bias=True, name=None, kernel_initializer="glorot_uniform"):
-        super().__init__(name or "conv2d_transpose")
+        super().__init__(name or "conv2d_transpose", kernel_size, strides, padding, activation, use_bias)
         self.filters = int(filters)
-        self.kh, self.kw = ops._pair(kernel_size)
-        self.sh, self.sw = ops._pair(strides)
-        if padding not in ("valid", "same"):
-            raise NotImplementedError(f"Conv2DTranspose padding {padding!r}")
-        self.padding = padding
-        self.activation = activation
-        self.use_bias = use_bias
         self.kernel_initializer = kernel_initializer
-        if activation == "relu":
-            self.relu = True
-        elif activation not in ops.ACT_KINDS:
-            raise NotImplementedError(f"Conv2DTranspose activation {activation!r}")
 
-    @property
-    def kernel_name(self) -> str:
-        return f"{self.name}/kernel"
-
-    @property
-    def bias_name(self) -> str:
-        return f"{self.name}/bias"
-
-    def _geom(self, B):
-        H, W, C = self.in_shape
-        return ops.deconv_geometry(B, H, W, C, self.filters, (self.kh, self.kw), (self.sh, self.sw), self.padding)
+    def descriptor(self, B):
+        return ops.deconv_geometry(B, *self.in_shape, self.filters, *self._ks, self.padding)
 
     def build(self, in_shape):
-        H, W, C = in_shape
-        self.in_shape = (H, W, C)
-        g = self._geom(1)
-        self.out_shape = (g[5], g[6], self.filters)
+        self.in_shape = tuple(in_shape)
+        g = self.descriptor(1)
+        self.out_shape = (g.OH, g.OW, self.filters)
         return self.out_shape
-
-    def can_fuse_relu(self):
-        return True
 
     def specs(self):
         C, T = self.in_shape[2], self.kh * self.kw
@@ -556,34 +495,22 @@ class Conv2DTranspose(Layer):
             s.append(ParamSpec(self.bias_name, (self.filters,), "vector", init="zeros"))
         return s
 
-    def alloc(self, B, device, dtype, ws):
-        super().alloc(B, device, dtype, ws)
-        self.ws = ws
-
     def forward(self, x, training):
         self.x = x
-        st = self.store
-        kn = self.kernel_name
-        b = st[self.bias_name] if self.use_bias else None
-        ops.deconv_fwd(x, st.weight(kn), st.weight_t(kn), b, self.out, self._geom(x.shape[0]), relu=self.relu)
+        st, kn = self.store, self.kernel_name
+        ops.deconv_fwd(x, st.weight(kn), st.weight_t(kn), self._bias(), self.out, self.g, relu=self.relu)
         return self.out
 
     def backward_weights(self, dy):
-        st = self.store
-        gb = st.gradient(self.bias_name) if self.use_bias else None
-        ops.deconv_wgrad(dy.reshape(self.out.shape), self.x, st.grad_matrix(self.kernel_name), gb, self.ws.wgrad,
-                         self._geom(self.x.shape[0]))
+        ops.deconv_wgrad(dy.reshape(self.out.shape), self.x, self.store.grad_matrix(self.kernel_name),
+                         self._bias(grad=True), self.ws.wgrad, self.g)
 
     def backward_data(self, dy):
         if not self.need_dx:
             return None
-        ops.deconv_dgrad(dy.reshape(self.out.shape), self.store.weight(self.kernel_name), self.dx,
-                         self._geom(self.x.shape[0]), mask=self.x if self.in_relu else None)
+        ops.deconv_dgrad(dy.reshape(self.out.shape), self.store.weight(self.kernel_name), self.dx, self.g,
+                         mask=self.x if self.in_relu else None)
         return self.dx
-
-    def backward(self, dy):
-        self.backward_weights(dy)
-        return self.backward_data(dy)
 
     def config(self):
         return {"filters": self.filters, "kernel_size": [self.kh, self.kw], "strides": [self.sh, self.sw],
@@ -604,7 +531,7 @@ class UpSampling2D(Layer):
             fractional = int(size) != size
         if fractional:
             raise NotImplementedError(f"UpSampling2D size {size!r}: integer factors only")
-        self.size = ops._pair(size)
+        self.size = pair(size)
         if min(self.size) < 1:
             raise ValueError(f"UpSampling2D size {size!r}")
         if interpolation not in ops.UPSAMPLE_KINDS:
@@ -634,12 +561,6 @@ class UpSampling2D(Layer):
         return {"size": list(self.size), "interpolation": self.interpolation}
 
 
-def _pair(v, default=None):
-    if v is None:
-        return default
-    return (int(v[0]), int(v[1])) if isinstance(v, (list, tuple)) else (int(v), int(v))
-
-
 class MaxPooling2D(Layer):
     """Keras MaxPooling2D: any pool_size / strides, 'valid' or 'same' padding.  Square pool == stride,
     'valid' (the MNIST CNNs) takes the vectorised max-pool kernels, which also fold a following Dropout
@@ -648,8 +569,8 @@ class MaxPooling2D(Layer):
 
     def __init__(self, pool_size=2, strides=None, padding="valid", name=None):
         super().__init__(name or ("average_pooling2d" if self.avg else "max_pooling2d"))
-        self.pool = _pair(pool_size)
-        self.strides = _pair(strides, self.pool)
+        self.pool = pair(pool_size)
+        self.strides = pair(strides, self.pool)
         self.padding = padding
         if padding not in ("valid", "same"):
             raise NotImplementedError(f"pooling padding {padding!r}")
@@ -661,26 +582,25 @@ class MaxPooling2D(Layer):
     def simple(self) -> bool:
         return self.p > 0
 
+    def descriptor(self, B) -> PoolGeom:
+        return PoolGeom.build(B, *self.in_shape, self.pool, self.strides, self.padding)
+
     def build(self, in_shape):
-        H, W, C = in_shape
-        self.in_shape = (H, W, C)
-        if self.simple:
-            self.out_shape = (H // self.p, W // self.p, C)
-        else:
-            g = ops.pool_geometry(1, H, W, C, self.pool, self.strides, self.padding)
-            self.out_shape = (g[4], g[5], C)
+        self.in_shape = tuple(in_shape)
+        g = self.descriptor(1)
+        self.out_shape = (g.OH, g.OW, g.C)
         return self.out_shape
 
-    def _geom(self, B):
-        H, W, C = self.in_shape
-        return ops.pool_geometry(B, H, W, C, self.pool, self.strides, self.padding)
+    def alloc(self, B, device, dtype, ws):
+        super().alloc(B, device, dtype, ws)
+        self.g = self.descriptor(B)
 
     def forward(self, x, training):
         self.x = x
         if self.simple:
             ops.maxpool_fwd(x, self.out, self.p, drop=self.drop_spec(training))
             return self.out
-        ops.pool2d_fwd(x, self.out, self._geom(x.shape[0]), avg=self.avg)
+        ops.pool2d_fwd(x, self.out, self.g, avg=self.avg)
         d = self.drop_spec(training)
         if d is not None:
             ops.dropout(self.out, self.out, d[0], d[1], step=d[2], step_add=d[3] if len(d) > 3 else 0)
@@ -692,8 +612,7 @@ class MaxPooling2D(Layer):
         if self.simple:
             ops.maxpool_bwd(self.x, dy, self.dx, self.p, relu_fused=self.in_relu)
         else:
-            ops.pool2d_bwd(self.x, dy.reshape(self.out.shape), self.dx, self._geom(self.x.shape[0]), avg=self.avg,
-                           in_relu=self.in_relu)
+            ops.pool2d_bwd(self.x, dy.reshape(self.out.shape), self.dx, self.g, avg=self.avg, in_relu=self.in_relu)
         return self.dx
 
     def config(self):
@@ -1183,8 +1102,8 @@ class FusedConvPool(Layer):
         sp = self.conv.specs()
         # the forward reads the row-segment weight layout chosen by the kernel (csrc/convpool.hip)
         H, W, C = self.in_shape
-        cp, _, pair = ops.convpool_fwd_layout(H, W, C, self.k, self.k, self.pad, self.conv.filters)
-        sp[0].row_pad, sp[0].row_cp, sp[0].row_pair = self.k, cp, bool(pair)
+        cp, _, paired = ops.convpool_fwd_layout(H, W, C, self.k, self.k, self.pad, self.conv.filters)
+        sp[0].row_pad, sp[0].row_cp, sp[0].row_pair = self.k, cp, bool(paired)
         if self.need_dx:
             sp[0].t_pair = bool(ops.convpool_dgrad_layout(H, W, C, self.k, self.k, self.pad, self.conv.filters)[0])
         return sp
@@ -1253,7 +1172,7 @@ class ConvPoolGemm(Layer):
 
     def alloc(self, B, device, dtype, ws):
         c = self.conv
-        c.in_relu, c.need_dx, c.ws, c.store = self.in_relu, self.need_dx, ws, self.store
+        c.in_relu, c.need_dx, c.ws, c.store, c.g = self.in_relu, self.need_dx, ws, self.store, c.descriptor(B)
         c.dx = torch.empty((B,) + c.in_shape, device=device, dtype=dtype) if self.need_dx else None
         self.out = torch.empty((B,) + self.out_shape, device=device, dtype=dtype)
         self.code = torch.empty((B,) + self.out_shape, device=device, dtype=torch.uint8)
@@ -1265,9 +1184,9 @@ class ConvPoolGemm(Layer):
         c = self.conv
         c.x = x
         st = self.store
-        b = st[f"{c.name}/bias"] if c.use_bias else None
-        ops.conv_pool_fwd(x, st.weight(f"{c.name}/kernel"), b, self.out, self.code, c.k, c.k, c.stride, c.pad,
-                          relu=c.relu, drop=self.drop_spec(training))
+        b = st[c.bias_name] if c.use_bias else None
+        ops.conv_pool_fwd(x, st.weight(c.kernel_name), b, self.out, self.code, g=c.g, relu=c.relu,
+                          drop=self.drop_spec(training))
         return self.out
 
     def backward(self, dy):

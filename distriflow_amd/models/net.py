@@ -22,7 +22,7 @@ from .. import ops
 from ..diagnostics import on as diag_on
 from .layers import (Activation, BatchNorm, Conv2D, Conv2DTranspose, ConvPoolGemm, Dense, DepthwiseConv2D, Dropout,
                      Flatten, FusedConvPool, KerasConvBlock, Layer, MaxPooling2D, ResidualBlock, SeparableConv2D,
-                     UpSampling2D)
+                     UpSampling2D, primary_kpad_of)
 from .params import ParamStore
 
 
@@ -348,8 +348,8 @@ class Net:
             if (isinstance(l, Conv2D) and isinstance(nxt, MaxPooling2D) and l.relu and l.regular and l.stride == 1
                     and nxt.p == 2
                     and l.out_shape[0] % 2 == 0 and l.out_shape[1] % 2 == 0
-                    and ops.conv_pool_supported(l.in_shape[0], l.in_shape[1], l.in_shape[2], l.k, l.k, l.stride,
-                                                l.pad, l.filters)):
+                    and ops.conv_pool_supported(*l.in_shape, l.k, l.k, l.stride, l.pad, l.filters,
+                                                Kpad=primary_kpad_of(l))):
                 out.append(ConvPoolGemm(l, nxt))
                 i += 2
                 continue

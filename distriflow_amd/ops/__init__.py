@@ -16,8 +16,9 @@ import torch
 from .. import native
 from ..diagnostics import on as _diag_on
 from . import reference as ref
-
-MODE_DIRECT, MODE_FWD, MODE_DGRAD = 0, 1, 2
+from .geometry import (MODE_DGRAD, MODE_DIRECT, MODE_FWD, ConvGeom, ConvPoolGeom, DeconvGeom,  # noqa: F401
+                       DenseGeom, DwGeom, PoolGeom, UpGeom, out_hw, window)
+from .geometry import pair as _pair
 
 
 class _DebugSync:
@@ -70,32 +71,25 @@ def graph_upload(g) -> bool:
         return False
 
 
-def _pair(v):
-    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
-
-
 def _geom(SH=1, SW=1, SC=1, OH=1, OW=1, KH=1, KW=1, stride=1, pad=0):
-    """Native conv geometry.  ``stride`` = s or (row, column); ``pad`` = p or (top, left) -- the bottom /
-    right padding is whatever the output size implies (asymmetric Keras 'same')."""
-    (sh, sw), (ph, pw) = _pair(stride), _pair(pad)
-    g = [int(SH), int(SW), int(SC), int(OH), int(OW), int(KH), int(KW), sh, ph]
-    return g if (sh, ph) == (sw, pw) else g + [sw, pw]
+    """Native conv geometry list (:meth:`ConvGeom.geom`) of a source [SH][SW][SC] and an output OH x OW."""
+    return ConvGeom.of(0, SH, SW, SC, OH, OW, 0, KH, KW, stride, pad).geom()
 
 
 def conv_out_hw(H, W, KH, KW, stride, pad):
     """Output size of a conv with symmetric padding ``pad`` = p or (ph, pw) and ``stride`` = s or (sh, sw)."""
-    (sh, sw), (ph, pw) = _pair(stride), _pair(pad)
-    return (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
+    return out_hw(H, W, (KH, KW), stride, pad)
 
 
 def same_padding(H, W, KH, KW, stride):
-    """Keras / TF 'same': output ceil(in / stride); total padding max((out - 1) * s + k - in, 0) split with
-    the odd element at the bottom / right.  Returns ((OH, OW), (top, left))."""
-    sh, sw = _pair(stride)
-    OH, OW = -(-H // sh), -(-W // sw)
-    th = max((OH - 1) * sh + KH - H, 0)
-    tw = max((OW - 1) * sw + KW - W, 0)
-    return (OH, OW), (th // 2, tw // 2)
+    """Keras / TF 'same' (:func:`geometry.window`).  Returns ((OH, OW), (top, left))."""
+    OH, OW, pt, pl = window(H, W, (KH, KW), stride, "same")
+    return (OH, OW), (pt, pl)
+
+
+def _conv_geom(xs, ys, KH, KW, stride, pad) -> ConvGeom:
+    """The conv from shape ``xs`` = [B][H][W][C] to ``ys`` = [B][OH][OW][N]."""
+    return ConvGeom.of(*xs, *ys[1:], KH, KW, stride, pad)
 
 
 # ----------------------------------------------------------------------------------- dense
@@ -110,11 +104,9 @@ def _drop_kw(drop) -> dict:
 def dense_fwd(x, w, bias, out, relu=False, drop=None):
     """out[B][N] = act(x[B][K] @ W^T + b); out may be bf16 or fp32 (logits).  ``drop = (p, seed, step)``:
     a Dropout that follows, folded into the epilogue (the mask of :func:`dropout` on ``out``)."""
-    B, K = x.shape[0], x.shape[-1]
-    N = out.shape[-1]
     if x.is_cuda:
-        dkw = _drop_kw(drop)
-        _C().igemm_fwd(x, w, bias, None, out, B, N, K, w.shape[1], K, N, _geom(), MODE_DIRECT, relu, 1.0, **dkw)
+        g = DenseGeom(x.shape[0], x.shape[-1], out.shape[-1])
+        _C().igemm_fwd(x, w, bias, None, out, *g.fwd(w.shape[1]), relu, 1.0, **_drop_kw(drop))
     else:
         out.copy_(ref.dense_fwd(x, w, bias, relu))
         if drop is not None:
@@ -124,22 +116,18 @@ def dense_fwd(x, w, bias, out, relu=False, drop=None):
 
 def dense_dgrad(dy, w, wt, out, mask=None, alpha=1.0):
     """out[B][K] = alpha * (dy[B][N] @ W) * relu'(mask)."""
-    B, N = dy.shape[0], dy.shape[-1]
-    K = out.shape[-1]
+    g = DenseGeom(dy.shape[0], out.shape[-1], dy.shape[-1])
     if dy.is_cuda:
-        _C().igemm_fwd(dy, wt, None, mask, out, B, K, N, wt.shape[1], N, K, _geom(), MODE_DIRECT, False,
-                       float(alpha))
+        _C().igemm_fwd(dy, wt, None, mask, out, *g.dgrad(wt.shape[1]), False, float(alpha))
     else:
-        out.copy_(ref.dense_dgrad(dy, w, K, mask) * alpha)
+        out.copy_(ref.dense_dgrad(dy, w, g.K, mask) * alpha)
     return out
 
 
 def dense_wgrad(dy, x, gw, gb, workspace=None, scale=1.0):
     """gw[N][K] = dy^T x * scale ; gb[N] = sum_b dy * scale."""
-    B, N = dy.shape[0], dy.shape[-1]
-    K = x.shape[-1]
     if dy.is_cuda:
-        _C().igemm_wgrad(dy, x, gw, gb, workspace, B, N, K, N, K, _geom(), MODE_DIRECT, scale)
+        _C().igemm_wgrad(dy, x, gw, gb, workspace, *DenseGeom(dy.shape[0], x.shape[-1], dy.shape[-1]).wgrad(), scale)
     else:
         g, b = ref.dense_wgrad(dy, x, gb is not None)
         gw.copy_(g.reshape(gw.shape) * scale)
@@ -165,10 +153,14 @@ def _bacc_kwargs(bacc):
 def conv_plan(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad=False, **flags) -> dict:
     """The launch plan (csrc/conv_plan.hip: kernel family, variant, grid, scratch) of the conv
     forward, or of the data gradient with output [B][H][W][C]; {} without the native extension."""
+    g = ConvGeom.of(B, H, W, C, OH, OW, N, KH, KW, stride, pad)
+    return _view_plan(g.dgrad(Kpad) if dgrad else g.fwd(Kpad), **flags)
+
+
+def _view_plan(view, **flags) -> dict:
+    """csrc/conv_plan.hip's plan of the ``igemm_fwd`` launch that takes ``view`` (a geometry.GemmView)."""
     m = native.get(build_if_missing=False)
-    g = ((B * H * W, C, KH * KW * N, Kpad, _geom(OH, OW, N, H, W, KH, KW, stride, pad), MODE_DGRAD) if dgrad else
-         (B * OH * OW, N, KH * KW * C, Kpad, _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD))
-    return m.conv_plan(*g, **flags) if m is not None else {}
+    return m.conv_plan(*view.plan, **flags) if m is not None else {}
 
 
 def conv_bacc_ok(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad=False, mode=0, two=False,
@@ -180,42 +172,37 @@ def conv_bacc_ok(B, H, W, C, OH, OW, N, KH, KW, stride, pad, Kpad, dgrad=False, 
     return bool(p.get("bacc_ok", False))
 
 
-def conv_fwd(x, w, bias, out, KH, KW, stride=1, pad=0, relu=False, bacc=None):
-    """NHWC conv: out[B][OH][OW][N]; w = [Npad][Kpad] with K = KH*KW*C.
+def conv_fwd(x, w, bias, out, KH=None, KW=None, stride=1, pad=0, relu=False, bacc=None, g=None):
+    """NHWC conv: out[B][OH][OW][N]; w = [Npad][Kpad] with K = KH*KW*C.  ``g``: the layer's ConvGeom, in place
+    of KH / KW / stride / pad.
     ``bacc``: the consuming BatchNorm's sums are accumulated by the epilogue (:func:`_bacc_kwargs`)."""
-    B, H, W, C = x.shape
-    _, OH, OW, N = out.shape
+    g = g or _conv_geom(x.shape, out.shape, KH, KW, stride, pad)
     if x.is_cuda:
-        K = KH * KW * C
-        _C().igemm_fwd(x, w, bias, None, out, B * OH * OW, N, K, w.shape[1], 0, N,
-                       _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD, relu, 1.0, **_bacc_kwargs(bacc))
+        _C().igemm_fwd(x, w, bias, None, out, *g.fwd(w.shape[1]), relu, 1.0, **_bacc_kwargs(bacc))
     else:
-        out.copy_(ref.conv_fwd(x, w, bias, KH, KW, stride, pad, relu, out_hw=(OH, OW)))
+        out.copy_(ref.conv_fwd(x, w, bias, g.KH, g.KW, g.stride, g.pad, relu, out_hw=(g.OH, g.OW)))
     return out
 
 
-def conv_pool_supported(H, W, C, KH, KW, stride, pad, N) -> bool:
-    """Conv + 2x2 max-pool in the igemm64 epilogue (pooled map + argmax codes only)."""
+def conv_pool_supported(H, W, C, KH, KW, stride, pad, N, Kpad=None) -> bool:
+    """Conv + 2x2 max-pool in the igemm64 epilogue (pooled map + argmax codes only).  ``Kpad``: the row length
+    of the weight copy the launch will read (default: the plain layout's, K rounded up to 32)."""
     if stride != 1 or N % 8:
         return False
-    OH, OW = conv_out_hw(H, W, KH, KW, stride, pad)
-    return bool(conv_plan(1, H, W, C, OH, OW, N, KH, KW, stride, pad, -(-KH * KW * C // 32) * 32,
-                          pooled=True).get("pool", False))
+    g = ConvGeom.of(1, H, W, C, *conv_out_hw(H, W, KH, KW, stride, pad), N, KH, KW, stride, pad)
+    Kpad = -(-g.KH * g.KW * g.C // 32) * 32 if Kpad is None else Kpad
+    return bool(_view_plan(g.fwd(Kpad), pooled=True).get("pool", False))
 
 
-def conv_pool_fwd(x, w, bias, out, code, KH, KW, stride=1, pad=0, relu=True, drop=None):
+def conv_pool_fwd(x, w, bias, out, code, KH=None, KW=None, stride=1, pad=0, relu=True, drop=None, g=None):
     """conv(+bias, ReLU) then 2x2 max-pool [then a folded dropout]: ``out`` = pooled [B][OH/2][OW/2][N],
     ``code`` = argmax position 0..3 per pooled element (4 = no gradient)."""
-    B, H, W, C = x.shape
-    _, PH, PW, N = out.shape
-    OH, OW = 2 * PH, 2 * PW
+    B, PH, PW, N = out.shape
+    g = g or _conv_geom(x.shape, (B, 2 * PH, 2 * PW, N), KH, KW, stride, pad)
     if x.is_cuda:
-        K = KH * KW * C
-        dkw = _drop_kw(drop)
-        _C().igemm_fwd(x, w, bias, None, out, B * OH * OW, N, K, w.shape[1], 0, N,
-                       _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD, relu, 1.0, pool_code=code, **dkw)
+        _C().igemm_fwd(x, w, bias, None, out, *g.fwd(w.shape[1]), relu, 1.0, pool_code=code, **_drop_kw(drop))
     else:
-        y = ref.conv_fwd(x, w, bias, KH, KW, stride, pad, relu).to(out.dtype).float()
+        y = ref.conv_fwd(x, w, bias, g.KH, g.KW, g.stride, g.pad, relu).to(out.dtype).float()
         win = y.reshape(B, PH, 2, PW, 2, N).permute(0, 1, 3, 5, 2, 4).reshape(B, PH, PW, N, 4)
         mx, am = win.max(dim=-1)  # first max
         if relu:
@@ -273,21 +260,19 @@ def kcnn_bwd(x, w1, b1, w2t, dyp, code, slabs, g_w1, g_b1, g_w2, g_b2, step_inc=
                   slabs, g_w1, g_b1, g_w2, g_b2, step_inc=step_inc)
 
 
-def conv_dgrad(dy, w, wt, out, KH, KW, stride=1, pad=0, mask=None, residual=None, residual_mask=None, bacc=None):
+def conv_dgrad(dy, w, wt, out, KH=None, KW=None, stride=1, pad=0, mask=None, residual=None, residual_mask=None,
+               bacc=None, g=None):
     """dX (NHWC [B][H][W][C]) of a conv whose output gradient is dy [B][OH][OW][N].
 
     Epilogue (ResNet block join): dX = (conv^T dy + residual * [residual_mask > 0]) * [mask > 0].
     ``bacc`` (mode 1): dX is the output gradient of a BatchNorm; its backward sums are accumulated by
     the epilogue (:func:`_bacc_kwargs`)."""
-    B, OH, OW, N = dy.shape
-    _, H, W, C = out.shape
+    g = g or _conv_geom(out.shape, dy.shape, KH, KW, stride, pad)
     if dy.is_cuda:
-        K = KH * KW * N
-        _C().igemm_fwd(dy, wt, None, mask, out, B * H * W, C, K, wt.shape[1], 0, C,
-                       _geom(OH, OW, N, H, W, KH, KW, stride, pad), MODE_DGRAD, False, 1.0, residual, residual_mask,
+        _C().igemm_fwd(dy, wt, None, mask, out, *g.dgrad(wt.shape[1]), False, 1.0, residual, residual_mask,
                        **_bacc_kwargs(bacc))
     else:
-        dx = ref.conv_dgrad(dy, w, out.shape, KH, KW, stride, pad, None)
+        dx = ref.conv_dgrad(dy, w, out.shape, g.KH, g.KW, g.stride, g.pad, None)
         if residual is not None:
             r = residual.float().reshape(dx.shape)
             if residual_mask is not None:
@@ -303,28 +288,26 @@ def wgrad_plan(B, H, W, C, OH, OW, N, KH, KW, stride, pad, with_bias, ws_floats)
     """The launch plan (csrc/conv_plan.hip wgrad_plan: kernel family, tile, splits, grid, the floats it writes
     into a workspace of ``ws_floats``) of :func:`conv_wgrad`; {} without the native extension.  A workspace
     smaller than ``wanted_floats`` gives fewer splits (``capped``): another summation order."""
+    return _view_wgrad_plan(ConvGeom.of(B, H, W, C, OH, OW, N, KH, KW, stride, pad).wgrad(), with_bias, ws_floats)
+
+
+def _view_wgrad_plan(view, with_bias, ws_floats) -> dict:
+    """csrc/conv_plan.hip's plan of the ``igemm_wgrad`` launch that takes ``view`` (a geometry.WgradView)."""
     m = native.get(build_if_missing=False)
-    if m is None:
-        return {}
-    return m.wgrad_plan(B * OH * OW, N, KH * KW * C, N, 0, _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD,
-                        bool(with_bias), int(ws_floats))
+    return m.wgrad_plan(*view, bool(with_bias), int(ws_floats)) if m is not None else {}
 
 
 def dense_wgrad_plan(B, K, N, with_bias, ws_floats) -> dict:
     """:func:`wgrad_plan` of :func:`dense_wgrad` (x [B][K], dy [B][N])."""
-    m = native.get(build_if_missing=False)
-    return m.wgrad_plan(B, N, K, N, K, _geom(), MODE_DIRECT, bool(with_bias), int(ws_floats)) if m is not None else {}
+    return _view_wgrad_plan(DenseGeom(B, K, N).wgrad(), with_bias, ws_floats)
 
 
-def conv_wgrad(dy, x, gw, gb, workspace, KH, KW, stride=1, pad=0, scale=1.0):
-    B, H, W, C = x.shape
-    _, OH, OW, N = dy.shape
+def conv_wgrad(dy, x, gw, gb, workspace, KH=None, KW=None, stride=1, pad=0, scale=1.0, g=None):
+    g = g or _conv_geom(x.shape, dy.shape, KH, KW, stride, pad)
     if dy.is_cuda:
-        K = KH * KW * C
-        _C().igemm_wgrad(dy, x, gw, gb, workspace, B * OH * OW, N, K, N, 0,
-                         _geom(H, W, C, OH, OW, KH, KW, stride, pad), MODE_FWD, scale)
+        _C().igemm_wgrad(dy, x, gw, gb, workspace, *g.wgrad(), scale)
     else:
-        g, b = ref.conv_wgrad(dy, x, KH, KW, stride, pad, gb is not None)
+        g, b = ref.conv_wgrad(dy, x, g.KH, g.KW, g.stride, g.pad, gb is not None)
         gw.copy_(g.reshape(gw.shape) * scale)
         if gb is not None:
             gb.copy_(b * scale)
@@ -530,40 +513,21 @@ def sigmoid_ce(logits, labels, dlogits=None, stats=None, grad_scale=1.0):
     return stats
 
 
-def pool_geometry(B, H, W, C, pool, strides, padding):
-    """[B, H, W, C, OH, OW, ph, pw, sh, sw, pt, pl] of a Keras/TF pooling layer ('valid' | 'same')."""
-    ph, pw = pool
-    sh, sw = strides
-    if padding == "same":
-        OH, OW = -(-H // sh), -(-W // sw)
-        tot_h = max((OH - 1) * sh + ph - H, 0)
-        tot_w = max((OW - 1) * sw + pw - W, 0)
-        pt, pl = tot_h // 2, tot_w // 2  # TF: the odd pixel of padding goes bottom / right
-    elif padding == "valid":
-        OH, OW = (H - ph) // sh + 1, (W - pw) // sw + 1
-        pt = pl = 0
-    else:
-        raise ValueError(f"pooling padding {padding!r}")
-    if OH < 1 or OW < 1:
-        raise ValueError(f"pool {pool} / {strides} does not fit a {H}x{W} input")
-    return [B, H, W, C, OH, OW, ph, pw, sh, sw, pt, pl]
+pool_geometry = PoolGeom.build  # (B, H, W, C, pool, strides, padding) of a Keras/TF pooling layer ('valid' | 'same')
 
 
 def _pool_ref(x, g, avg):
-    B, H, W, C, OH, OW, ph, pw, sh, sw, pt, pl = g
+    F, g = torch.nn.functional, PoolGeom(*g)
     xf = x.float().permute(0, 3, 1, 2)
-    pb, pr = max((OH - 1) * sh + ph - H - pt, 0), max((OW - 1) * sw + pw - W - pl, 0)
+    pads, win = (g.pl, max(g.pr, 0), g.pt, max(g.pb, 0)), ((g.ph, g.pw), (g.sh, g.sw))
     if avg:
-        ones = torch.ones(1, 1, H, W, dtype=xf.dtype, device=xf.device)
-        num = torch.nn.functional.avg_pool2d(torch.nn.functional.pad(xf, (pl, pr, pt, pb)), (ph, pw), (sh, sw),
-                                             divisor_override=1)
-        cnt = torch.nn.functional.avg_pool2d(torch.nn.functional.pad(ones, (pl, pr, pt, pb)), (ph, pw), (sh, sw),
-                                             divisor_override=1)
+        ones = torch.ones(1, 1, g.H, g.W, dtype=xf.dtype, device=xf.device)
+        num = F.avg_pool2d(F.pad(xf, pads), *win, divisor_override=1)
+        cnt = F.avg_pool2d(F.pad(ones, pads), *win, divisor_override=1)
         y = num / cnt.clamp_min(1.0)
     else:
-        y = torch.nn.functional.max_pool2d(torch.nn.functional.pad(xf, (pl, pr, pt, pb), value=float("-inf")),
-                                           (ph, pw), (sh, sw))
-    return y[:, :, :OH, :OW].permute(0, 2, 3, 1)
+        y = F.max_pool2d(F.pad(xf, pads, value=float("-inf")), *win)
+    return y[:, :, :g.OH, :g.OW].permute(0, 2, 3, 1)
 
 
 def pool2d_fwd(x, out, geom, avg=False):
@@ -589,20 +553,7 @@ def pool2d_bwd(x, dy, dx, geom, avg=False, in_relu=False):
 
 
 # ---- depthwise convolution (csrc/dwconv.hip): fp32 kernel [KH][KW][C*M], output channel co reads input co // M
-def dwconv_geometry(B, H, W, C, M, kernel, strides, padding):
-    """[B, H, W, C, M, OH, OW, KH, KW, sh, sw, pt, pl] of a Keras DepthwiseConv2D ('valid' | 'same': the odd
-    pixel of padding goes bottom / right, as TensorFlow does)."""
-    (kh, kw), (sh, sw) = _pair(kernel), _pair(strides)
-    if padding == "same":
-        (OH, OW), (pt, pl) = same_padding(H, W, kh, kw, (sh, sw))
-    elif padding == "valid":
-        OH, OW = conv_out_hw(H, W, kh, kw, (sh, sw), 0)
-        pt = pl = 0
-    else:
-        raise ValueError(f"depthwise conv padding {padding!r}")
-    if OH < 1 or OW < 1 or M < 1:
-        raise ValueError(f"depthwise kernel {kh}x{kw} / strides {sh},{sw} does not fit a {H}x{W} input")
-    return [int(B), int(H), int(W), int(C), int(M), OH, OW, kh, kw, sh, sw, pt, pl]
+dwconv_geometry = DwGeom.build  # (B, H, W, C, M, kernel, strides, padding) of a Keras DepthwiseConv2D
 
 
 def dwconv_fwd(x, w, bias, out, geom, relu=False):
@@ -636,59 +587,33 @@ def dwconv_wgrad(dy, x, gw, gb, workspace, geom):
     return gw
 
 
-# ---- transposed convolution: the data gradient of the conv G from [B][OH][OW][F] to [B][H][W][Cin] with the
-# same kernel size, strides and padding; kernel = G's OHWI matrix [Cin][KH*KW*F].  The conv kernels run it
-# with their roles swapped (forward = G's data gradient, input gradient = G's forward, kernel gradient = G's
-# with x and dy exchanged).
+# ---- transposed convolution: the data gradient of a conv G with the same kernel size, strides and padding;
+# kernel = G's OHWI matrix [Cin][KH*KW*F].  The conv kernels run it with their roles swapped (ConvGeom.t_fwd).
 def deconv_geometry(B, H, W, Cin, F, kernel, strides, padding):
-    """[B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl] of a Keras Conv2DTranspose: 'valid' gives
-    H*sh + max(KH - sh, 0) rows, 'same' H*sh rows with G's TensorFlow 'same' top / left pads (no
-    output_padding, no dilation)."""
-    (kh, kw), (sh, sw) = _pair(kernel), _pair(strides)
-    if min(int(B), int(H), int(W), int(Cin), int(F), kh, kw, sh, sw) < 1:
-        raise ValueError(f"transposed conv: kernel {kh}x{kw} / strides {sh},{sw} / {F} filters do not fit a "
-                         f"{H}x{W}x{Cin} input")
-    if padding == "same":
-        OH, OW = H * sh, W * sw
-        (gh, gw), (pt, pl) = same_padding(OH, OW, kh, kw, (sh, sw))
-    elif padding == "valid":
-        OH, OW = H * sh + max(kh - sh, 0), W * sw + max(kw - sw, 0)
-        pt = pl = 0
-        gh, gw = conv_out_hw(OH, OW, kh, kw, (sh, sw), 0)
-    else:
-        raise ValueError(f"transposed conv padding {padding!r}")
-    if (gh, gw) != (H, W):
-        raise ValueError(f"transposed conv: no {kh}x{kw} / {sh},{sw} {padding!r} conv maps {OH}x{OW} to {H}x{W}")
-    return [int(B), int(H), int(W), int(Cin), int(F), OH, OW, kh, kw, sh, sw, pt, pl]
+    """The DeconvGeom [B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl] of a Keras Conv2DTranspose."""
+    return ConvGeom.transposed(B, H, W, Cin, F, kernel, strides, padding).t_geom
 
 
 def deconv_plans(geom, w, wt, has_bias=False, has_mask=False, ws_floats=0) -> dict:
     """The kernel families (csrc/conv_plan.hip) the three launches of a transposed conv take: ``fwd`` (a
     MODE_DGRAD launch), ``dgrad`` (a MODE_FWD launch) and ``wgrad``; {} without the native extension.  A bias
     changes the forward's plan (the halo kernel refuses one)."""
-    m = native.get(build_if_missing=False)
-    if m is None:
+    if native.get(build_if_missing=False) is None:
         return {}
-    B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl = geom
-    st, pd = (sh, sw), (pt, pl)
-    fwd = m.conv_plan(B * OH * OW, F, KH * KW * Cin, int(wt.shape[1]), _geom(H, W, Cin, OH, OW, KH, KW, st, pd),
-                      MODE_DGRAD, has_bias=bool(has_bias))
-    dg =m.conv_plan(B * H * W, Cin, KH * KW * F, int(w.shape[1]), _geom(OH, OW, F, H, W, KH, KW, st, pd), MODE_FWD,
-                     has_mask=bool(has_mask))
-    wg = m.wgrad_plan(B * H * W, Cin, KH * KW * F, Cin, 0, _geom(OH, OW, F, H, W, KH, KW, st, pd), MODE_FWD, False,
-                      int(ws_floats))
-    return {"fwd": fwd, "dgrad": dg, "wgrad": wg}
+    G = DeconvGeom(*geom).G
+    return {"fwd": _view_plan(G.t_fwd(int(wt.shape[1])), has_bias=bool(has_bias)),
+            "dgrad": _view_plan(G.t_dgrad(int(w.shape[1])), has_mask=bool(has_mask)),
+            "wgrad": _view_wgrad_plan(G.t_wgrad(), False, ws_floats)}
 
 
 def deconv_fwd(x, w, wt, bias, out, geom, relu=False):
     """out [B][OH][OW][F] = [relu](transposed conv of NHWC ``x`` + bias).  ``w``: the kernel [Cin][KH*KW*F]
     (CPU) ; ``wt``: its dgrad-layout bf16 copy [Fpad][pad(KH*KW*Cin)] (GPU)."""
-    B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl = geom
+    G = DeconvGeom(*geom).G
     if x.is_cuda:
-        _C().igemm_fwd(x, wt, bias, None, out, B * OH * OW, F, KH * KW * Cin, wt.shape[1], 0, F,
-                       _geom(H, W, Cin, OH, OW, KH, KW, (sh, sw), (pt, pl)), MODE_DGRAD, bool(relu), 1.0)
+        _C().igemm_fwd(x, wt, bias, None, out, *G.t_fwd(wt.shape[1]), bool(relu), 1.0)
     else:
-        y = ref.conv_dgrad(x.reshape(B, H, W, Cin), w, (B, OH, OW, F), KH, KW, (sh, sw), (pt, pl))
+        y = ref.conv_dgrad(x.reshape(G.y_shape), w, G.x_shape, G.KH, G.KW, G.stride, G.pad)
         if bias is not None:
             y = y + bias.float()
         if relu:
@@ -699,12 +624,11 @@ def deconv_fwd(x, w, wt, bias, out, geom, relu=False):
 
 def deconv_dgrad(dy, w, dx, geom, mask=None):
     """dx [B][H][W][Cin] = G(dy) * relu'(mask): the forward of the conv G on the output gradient."""
-    B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl = geom
+    G = DeconvGeom(*geom).G
     if dy.is_cuda:
-        _C().igemm_fwd(dy, w, None, mask, dx, B * H * W, Cin, KH * KW * F, w.shape[1], 0, Cin,
-                       _geom(OH, OW, F, H, W, KH, KW, (sh, sw), (pt, pl)), MODE_FWD, False, 1.0)
+        _C().igemm_fwd(dy, w, None, mask, dx, *G.t_dgrad(w.shape[1]), False, 1.0)
     else:
-        g = ref.conv_fwd(dy.reshape(B, OH, OW, F), w, None, KH, KW, (sh, sw), (pt, pl), False, out_hw=(H, W))
+        g = ref.conv_fwd(dy.reshape(G.x_shape), w, None, G.KH, G.KW, G.stride, G.pad, False, out_hw=(G.OH, G.OW))
         if mask is not None:
             g = g * (mask.float().reshape(g.shape) > 0)
         dx.copy_(g.reshape(dx.shape))
@@ -725,10 +649,10 @@ def channel_sum(dy, gb, workspace, scale=1.0):
 def deconv_wgrad(dy, x, gw, gb, workspace, geom):
     """gw [Cin][KH*KW*F]: G's kernel gradient with x in the output-gradient slot and dy in the input slot (no
     bias column: it would sum x); gb [F] = sum over positions of dy (None: no bias)."""
-    B, H, W, Cin, F, OH, OW, KH, KW, sh, sw, pt, pl = geom
-    conv_wgrad(x.reshape(B, H, W, Cin), dy.reshape(B, OH, OW, F), gw, None, workspace, KH, KW, (sh, sw), (pt, pl))
+    G = DeconvGeom(*geom).G
+    conv_wgrad(x.reshape(G.y_shape), dy.reshape(G.x_shape), gw, None, workspace, g=G)
     if gb is not None:
-        channel_sum(dy.reshape(B * OH * OW, F), gb, workspace)
+        channel_sum(dy.reshape(-1, G.C), gb, workspace)
     return gw
 
 
@@ -739,25 +663,24 @@ UPSAMPLE_KINDS = ("nearest", "bilinear")
 def upsample2d_fwd(x, out, size, interpolation="nearest", half_pixel_centers=True):
     """out [B][H*sh][W*sw][C]: every pixel repeated ('nearest'), or 'bilinear' sampling at
     src = (dst + o) / s - o with o = 0.5 (``half_pixel_centers``, Keras / TF2) or 0 (tf.js)."""
-    B, H, W, C = x.shape
-    sh, sw = _pair(size)
+    g = UpGeom(*x.shape, *_pair(size))
     bil = UPSAMPLE_KINDS.index(interpolation) == 1
     if x.is_cuda:
-        _C().upsample2d_fwd(x.contiguous(), out, [B, H, W, C, sh, sw], bil, bool(half_pixel_centers))
+        _C().upsample2d_fwd(x.contiguous(), out, list(g), bil, bool(half_pixel_centers))
     else:
-        out.copy_(ref.upsample2d_fwd(x, (sh, sw), bil, half_pixel_centers).reshape(out.shape))
+        out.copy_(ref.upsample2d_fwd(x, (g.sh, g.sw), bil, half_pixel_centers).reshape(out.shape))
     return out
 
 
 def upsample2d_bwd(dy, dx, size, interpolation="nearest", half_pixel_centers=True, mask=None):
     """dx [B][H][W][C] = (sum of the dy pixels that read the pixel, weighted) * relu'(mask)."""
-    B, H, W, C = dx.shape
-    sh, sw = _pair(size)
+    g = UpGeom(*dx.shape, *_pair(size))
     bil = UPSAMPLE_KINDS.index(interpolation) == 1
     if dy.is_cuda:
-        _C().upsample2d_bwd(dy.contiguous(), mask, dx, [B, H, W, C, sh, sw], bil, bool(half_pixel_centers))
+        _C().upsample2d_bwd(dy.contiguous(), mask, dx, list(g), bil, bool(half_pixel_centers))
     else:
-        dx.copy_(ref.upsample2d_bwd(dy.reshape(B, H * sh, W * sw, C), (sh, sw), bil, half_pixel_centers, mask))
+        dx.copy_(ref.upsample2d_bwd(dy.reshape(g.B, g.H * g.sh, g.W * g.sw, g.C), (g.sh, g.sw), bil,
+                                    half_pixel_centers, mask))
     return dx
 
 
@@ -1319,19 +1242,14 @@ def convpool_dgrad_layout(H, W, C, KH, KW, pad, N):
     return tuple(convpool_plan(H, W, C, KH, KW, pad, N)[k] for k in ("dgrad_pair", "K2pad"))
 
 
-def _cp_in(x):
-    if isinstance(x, GatherRef):
-        return x.data, x.idx, x.scale
-    return x, None, 1.0
+_cp_in = _kc_in
 
 
 def convpool_fwd(x, w, bias, out, code, KH, KW, pad):
     """Fused conv(stride 1) + bias + ReLU + maxpool 2x2 -> pooled map ``out`` and argmax ``code``."""
-    B, H, W, C = x.shape
-    N = out.shape[-1]
     if x.is_cuda:
         src, idx, scale = _cp_in(x)
-        _C().convpool_fwd(src, idx, scale, w, bias, out, code, [B, H, W, C, KH, KW, pad, N])
+        _C().convpool_fwd(src, idx, scale, w, bias, out, code, list(ConvPoolGeom(*x.shape, KH, KW, pad, out.shape[-1])))
     else:
         if isinstance(x, GatherRef):
             x = (x.data.index_select(0, x.idx).float() * x.scale).reshape(x.shape)
@@ -1345,15 +1263,13 @@ def convpool_fwd(x, w, bias, out, code, KH, KW, pad):
 def convpool_wgrad(x, dp, code, gw, gb, workspace, KH, KW, pad, defer: list | None = None):
     """``defer``: a list to which the GPU path appends its split-m slab reduction instead of launching
     it; run them all with :func:`flush_slab_reductions` (one launch, bit-identical results)."""
-    B, H, W, C = x.shape
-    N = code.shape[-1]
     if code.is_cuda:
         src, idx, scale = _cp_in(x)
-        S = _C().convpool_wgrad(src, idx, scale, dp, code, gw, gb, workspace, [B, H, W, C, KH, KW, pad, N],
-                                defer is not None)
+        g = ConvPoolGeom(*x.shape, KH, KW, pad, code.shape[-1])
+        S = _C().convpool_wgrad(src, idx, scale, dp, code, gw, gb, workspace, list(g), defer is not None)
         if defer is not None and S > 0:
-            K = KH * KW * C
-            defer.append((workspace, gw.reshape(-1), gb, N, K, K + 1, int(S), 1.0))
+            K = g.KH * g.KW * g.C
+            defer.append((workspace, gw.reshape(-1), gb, g.N, K, K + 1, int(S), 1.0))
     else:
         if isinstance(x, GatherRef):
             x = (x.data.index_select(0, x.idx).float() * x.scale).reshape(x.shape)
@@ -1371,10 +1287,8 @@ def flush_slab_reductions(pending: list):
 
 
 def convpool_dgrad(dp, code, w, wt, dx, KH, KW, pad):
-    B, H, W, C = dx.shape
-    N = code.shape[-1]
     if code.is_cuda:
-        _C().convpool_dgrad(dp, code, wt, dx, [B, H, W, C, KH, KW, pad, N])
+        _C().convpool_dgrad(dp, code, wt, dx, list(ConvPoolGeom(*dx.shape, KH, KW, pad, code.shape[-1])))
     else:
         dx.copy_(ref.convpool_dgrad(dp, code, w, dx.shape, KH, KW, pad))
     return dx

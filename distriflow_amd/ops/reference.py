@@ -9,6 +9,8 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
+from .geometry import DwGeom, pad_after, pair
+from .geometry import out_hw as sym_out_hw
 
 def _nchw(x):
     return x.permute(0, 3, 1, 2)
@@ -26,24 +28,12 @@ def conv_weight_4d(w2d, N, KH, KW, C):
 def _conv_pad(x, KH, KW, stride, pad, OH, OW):
     """NCHW input padded for a padding-free conv of output OH x OW: ``pad`` = (top, left); the bottom /
     right padding (possibly negative = cropped rows that no output reads) follows from the output size."""
-    (sh, sw), (pt, pl) = _pair(stride), _pair(pad)
-    H, W = x.shape[2], x.shape[3]
-    pb = (OH - 1) * sh + KH - H - pt
-    pr = (OW - 1) * sw + KW - W - pl
-    return F.pad(x, (pl, pr, pt, pb))
-
-
-def _pair(v):
-    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
-
-
-def _out_hw(H, W, KH, KW, stride, pad):
-    (sh, sw), (ph, pw) = _pair(stride), _pair(pad)
-    return (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
+    (sh, sw), (pt, pl) = pair(stride), pair(pad)
+    return F.pad(x, (pl, pad_after(x.shape[3], OW, KW, sw, pl), pt, pad_after(x.shape[2], OH, KH, sh, pt)))
 
 
 def _conv(xc, w4, bias, KH, KW, stride, pad, OH, OW):
-    return F.conv2d(_conv_pad(xc, KH, KW, stride, pad, OH, OW), w4, bias, stride=_pair(stride))
+    return F.conv2d(_conv_pad(xc, KH, KW, stride, pad, OH, OW), w4, bias, stride=pair(stride))
 
 
 def conv_fwd(x, w2d, bias, KH, KW, stride, pad, relu, out_hw=None):
@@ -52,7 +42,7 @@ def conv_fwd(x, w2d, bias, KH, KW, stride, pad, relu, out_hw=None):
     B, H, W, C = x.shape
     N = bias.shape[0] if bias is not None else w2d.shape[0]
     w4 = conv_weight_4d(w2d.float(), N, KH, KW, C)
-    OH, OW = out_hw or _out_hw(H, W, KH, KW, stride, pad)
+    OH, OW = out_hw or sym_out_hw(H, W, (KH, KW), stride, pad)
     y = _conv(_nchw(x.float()), w4, bias.float() if bias is not None else None, KH, KW, stride, pad, OH, OW)
     if relu:
         y = torch.relu(y)
@@ -89,9 +79,10 @@ def conv_wgrad(dy, x, KH, KW, stride, pad, with_bias=True):
 def _dwconv(xc, w, bias, geom):
     """NCHW depthwise conv: ``w`` [KH][KW][C*M] (Keras depthwise_kernel flattened) -> torch [C*M][1][KH][KW] with
     groups = C (output channel co reads input channel co // M), after the explicit TF padding."""
-    B, H, W, C, M, OH, OW, KH, KW, sh, sw, pt, pl = geom
-    w4 = w.float().reshape(KH, KW, C * M).permute(2, 0, 1).unsqueeze(1)
-    return F.conv2d(_conv_pad(xc, KH, KW, (sh, sw), (pt, pl), OH, OW), w4, bias, stride=(sh, sw), groups=C)
+    g = DwGeom(*geom)
+    w4 = w.float().reshape(g.KH, g.KW, g.C * g.M).permute(2, 0, 1).unsqueeze(1)
+    return F.conv2d(_conv_pad(xc, g.KH, g.KW, (g.sh, g.sw), (g.pt, g.pl), g.OH, g.OW), w4, bias, stride=(g.sh, g.sw),
+                    groups=g.C)
 
 
 def dwconv_fwd(x, w, bias, geom, relu=False):
@@ -102,8 +93,8 @@ def dwconv_fwd(x, w, bias, geom, relu=False):
 
 
 def dwconv_dgrad(dy, w, geom, mask=None):
-    B, H, W, C = geom[:4]
-    xz = torch.zeros((dy.shape[0], C, H, W), dtype=torch.float32, device=dy.device, requires_grad=True)
+    g = DwGeom(*geom)
+    xz = torch.zeros((dy.shape[0], g.C, g.H, g.W), dtype=torch.float32, device=dy.device, requires_grad=True)
     with torch.enable_grad():
         y = _dwconv(xz, w.detach(), None, geom)
         dx, = torch.autograd.grad(y, xz, _nchw(dy.float()).reshape(y.shape))
@@ -114,12 +105,12 @@ def dwconv_dgrad(dy, w, geom, mask=None):
 
 
 def dwconv_wgrad(dy, x, geom, with_bias=True):
-    B, H, W, C, M, OH, OW, KH, KW = geom[:9]
-    wz = torch.zeros((KH, KW, C * M), dtype=torch.float32, device=dy.device, requires_grad=True)
+    g = DwGeom(*geom)
+    wz = torch.zeros((g.KH, g.KW, g.C * g.M), dtype=torch.float32, device=dy.device, requires_grad=True)
     with torch.enable_grad():
         y = _dwconv(_nchw(x.float()), wz, None, geom)
         gw, = torch.autograd.grad(y, wz, _nchw(dy.float()).reshape(y.shape))
-    gb = dy.float().reshape(-1, C * M).sum(0) if with_bias else None
+    gb = dy.float().reshape(-1, g.C * g.M).sum(0) if with_bias else None
     return gw, gb
 
 
@@ -289,13 +280,13 @@ def convpool_unpool(dp, code, OH, OW):
 
 def convpool_wgrad(x, dp, code, KH, KW, pad):
     B, H, W, C = x.shape
-    OH, OW = H + 2 * pad - KH + 1, W + 2 * pad - KW + 1
+    OH, OW = sym_out_hw(H, W, (KH, KW), 1, pad)
     dconv = convpool_unpool(dp, code, OH, OW)
     return conv_wgrad(dconv, x, KH, KW, 1, pad, True)
 
 
 def convpool_dgrad(dp, code, w2d, in_shape, KH, KW, pad):
     B, H, W, C = in_shape
-    OH, OW = H + 2 * pad - KH + 1, W + 2 * pad - KW + 1
+    OH, OW = sym_out_hw(H, W, (KH, KW), 1, pad)
     dconv = convpool_unpool(dp, code, OH, OW)
     return conv_dgrad(dconv, w2d, in_shape, KH, KW, 1, pad, None)
