@@ -8,13 +8,18 @@ before it compares anything; they are conditions, not tolerances.
 
 The reference is ``F.unfold`` / ``F.fold`` + matmul in float64, in batch chunks.  It does not go through
 ``ops.reference``: that casts to fp32, and an fp32 library conv may pick a Winograd-class algorithm, which is
-not exact on integers.
+not exact on integers.  The conv references take one (k, s, p) or a ``ConvGeom`` (per-axis kernel and strides,
+top / left padding, the bottom / right padding the output size implies); the transposed conv is that conv with
+the roles swapped, the depthwise conv a loop over its taps.
 
 Everything is generated on the CPU from a seeded generator (the same values with and without a GPU) and moved
 to ``device`` afterwards.
 """
 import torch
 import torch.nn.functional as F
+
+from distriflow_amd.ops import geometry
+from distriflow_amd.ops.geometry import ConvGeom, DeconvGeom, DwGeom, pad_after
 
 BF16_INT_MAX = 256        # every integer of magnitude <= 256 is a bf16 value
 FP32_INT_MAX = 1 << 24    # every integer of magnitude <= 2^24 is an fp32 value
@@ -116,57 +121,172 @@ def _chunk(B, per_image_elems, budget=1 << 25):
     return max(1, min(B, budget // max(1, per_image_elems)))
 
 
-def conv_fwd_ref(x, w, bias, k, s, p, relu):
-    """fp64 NHWC conv: x [B][H][W][C], w [N][k*k*C] with column (ky, kx, c), bias [N] or None -> [B][OH][OW][N]."""
-    B, H, W, C = x.shape
-    N = w.shape[0]
-    OH, OW = out_hw(H, W, k, s, p)
-    # F.unfold orders a column (c, ky, kx)
-    wu = w.view(N, k, k, C).permute(0, 3, 1, 2).reshape(N, C * k * k).double()
-    out = torch.empty(B, OH, OW, N, dtype=torch.float64, device=x.device)
-    step = _chunk(B, C * k * k * OH * OW)
+def conv_geom(xshape, N, k, s=1, p=0):
+    """The ``ConvGeom`` of a conv reference: ``k`` is a ConvGeom already (``s``, ``p`` unused), or the kernel k /
+    (kh, kw) with strides s / (sh, sw) and the symmetric padding p / (ph, pw)."""
+    if isinstance(k, ConvGeom):
+        return k
+    B, H, W, C = xshape
+    OH, OW = geometry.out_hw(H, W, k, s, p)
+    return ConvGeom.of(B, H, W, C, OH, OW, N, *geometry.pair(k), s, p)
+
+
+def _padded_hw(g):
+    """Size of the padded image the windows of ``g`` tile exactly (they read nothing past it)."""
+    return (g.OH - 1) * g.sh + g.KH, (g.OW - 1) * g.sw + g.KW
+
+
+def _unfold(xc, g):
+    """NCHW fp64 -> the columns [b][C*KH*KW][OH*OW] of ``g``'s windows: top / left padding (pt, pl), the bottom /
+    right padding the output size implies (negative: trailing pixels that no window reads are cropped)."""
+    xp = F.pad(xc, (g.pl, pad_after(g.W, g.OW, g.KW, g.sw, g.pl), g.pt, pad_after(g.H, g.OH, g.KH, g.sh, g.pt)))
+    assert tuple(xp.shape[2:]) == _padded_hw(g)
+    return F.unfold(xp, (g.KH, g.KW), stride=(g.sh, g.sw))
+
+
+def _w_unfold(w, g):
+    """[N][KH*KW*C] with column (ky, kx, c) -> fp64 [N][C*KH*KW] in F.unfold's column order (c, ky, kx)."""
+    return w.view(g.N, g.KH, g.KW, g.C).permute(0, 3, 1, 2).reshape(g.N, g.C * g.KH * g.KW).double()
+
+
+def conv_fwd_ref(x, w, bias, k, s=1, p=0, relu=False):
+    """fp64 NHWC conv: x [B][H][W][C], w [N][KH*KW*C] with column (ky, kx, c), bias [N] or None -> [B][OH][OW][N].
+    ``k, s, p``: see :func:`conv_geom`."""
+    B = x.shape[0]
+    g = conv_geom(x.shape, w.shape[0], k, s, p)
+    wu = _w_unfold(w, g)
+    out = torch.empty(B, g.OH, g.OW, g.N, dtype=torch.float64, device=x.device)
+    step = _chunk(B, wu.shape[1] * g.OH * g.OW)
     for b0 in range(0, B, step):
-        xc = x[b0:b0 + step].double().permute(0, 3, 1, 2)
-        cols = F.unfold(xc, k, padding=p, stride=s)          # [b][C*k*k][OH*OW]
-        y = torch.matmul(wu, cols)                           # [b][N][OH*OW]
-        out[b0:b0 + step] = y.permute(0, 2, 1).reshape(-1, OH, OW, N)
+        cols = _unfold(x[b0:b0 + step].double().permute(0, 3, 1, 2), g)   # [b][C*KH*KW][OH*OW]
+        y = torch.matmul(wu, cols)                                        # [b][N][OH*OW]
+        out[b0:b0 + step] = y.permute(0, 2, 1).reshape(-1, g.OH, g.OW, g.N)
     if bias is not None:
         out += bias.double()
     return out.relu_() if relu else out
 
 
-def conv_dgrad_ref(dy, w, xshape, k, s, p):
-    """fp64 data gradient of :func:`conv_fwd_ref`: dy [B][OH][OW][N] -> [B][H][W][C] (no epilogue)."""
-    B, H, W, C = xshape
-    N = w.shape[0]
-    OH, OW = out_hw(H, W, k, s, p)
-    wu = w.view(N, k, k, C).permute(0, 3, 1, 2).reshape(N, C * k * k).double()
-    out = torch.empty(B, H, W, C, dtype=torch.float64, device=dy.device)
-    step = _chunk(B, C * k * k * OH * OW)
+def conv_dgrad_ref(dy, w, xshape, k, s=1, p=0):
+    """fp64 data gradient of :func:`conv_fwd_ref`: dy [B][OH][OW][N] -> [B][H][W][C] (no epilogue); exactly 0 at
+    the pixels no window reads."""
+    B = xshape[0]
+    g = conv_geom(xshape, w.shape[0], k, s, p)
+    wu = _w_unfold(w, g)
+    PH, PW = _padded_hw(g)
+    hh, ww = min(g.H, PH - g.pt), min(g.W, PW - g.pl)   # the rows / columns of the image inside the padded one
+    out = torch.zeros(B, g.H, g.W, g.C, dtype=torch.float64, device=dy.device)
+    step = _chunk(B, wu.shape[1] * g.OH * g.OW)
     for b0 in range(0, B, step):
-        g = dy[b0:b0 + step].double().reshape(-1, OH * OW, N).permute(0, 2, 1)   # [b][N][L]
-        cols = torch.matmul(wu.t(), g)                                           # [b][C*k*k][L]
-        dx = F.fold(cols, (H, W), k, padding=p, stride=s)                        # [b][C][H][W]
-        out[b0:b0 + step] = dx.permute(0, 2, 3, 1)
+        gy = dy[b0:b0 + step].double().reshape(-1, g.OH * g.OW, g.N).permute(0, 2, 1)   # [b][N][L]
+        cols = torch.matmul(wu.t(), gy)                                                 # [b][C*KH*KW][L]
+        dx = F.fold(cols, (PH, PW), (g.KH, g.KW), stride=(g.sh, g.sw))                  # [b][C][PH][PW]
+        out[b0:b0 + step, :hh, :ww] = dx[:, :, g.pt:g.pt + hh, g.pl:g.pl + ww].permute(0, 2, 3, 1)
     return out
 
 
-def conv_wgrad_ref(dy, x, k, s, p):
-    """fp64 weight / bias gradient: gw [N][k*k*C] with column (ky, kx, c), gb [N]; also the per-element
+def conv_wgrad_ref(dy, x, k, s=1, p=0):
+    """fp64 weight / bias gradient: gw [N][KH*KW*C] with column (ky, kx, c), gb [N]; also the per-element
     sum of |dy * x| (the exactness condition of the weight gradient)."""
-    B, H, W, C = x.shape
+    B = x.shape[0]
     N = dy.shape[-1]
-    OH, OW = out_hw(H, W, k, s, p)
-    gw = torch.zeros(N, C * k * k, dtype=torch.float64, device=x.device)
+    g = conv_geom(x.shape, N, k, s, p)
+    CK = g.C * g.KH * g.KW
+    gw = torch.zeros(N, CK, dtype=torch.float64, device=x.device)
     ab = torch.zeros_like(gw)
-    step = _chunk(B, C * k * k * OH * OW)
+    step = _chunk(B, CK * g.OH * g.OW)
     for b0 in range(0, B, step):
-        cols = F.unfold(x[b0:b0 + step].double().permute(0, 3, 1, 2), k, padding=p, stride=s)  # [b][CKK][L]
-        g = dy[b0:b0 + step].double().reshape(-1, OH * OW, N).permute(0, 2, 1)                 # [b][N][L]
-        gw += torch.matmul(g, cols.transpose(1, 2)).sum(0)
-        ab += torch.matmul(g.abs(), cols.abs().transpose(1, 2)).sum(0)
-    reorder = lambda t: t.view(N, C, k, k).permute(0, 2, 3, 1).reshape(N, k * k * C)  # noqa: E731
+        cols = _unfold(x[b0:b0 + step].double().permute(0, 3, 1, 2), g)                        # [b][CKK][L]
+        gy = dy[b0:b0 + step].double().reshape(-1, g.OH * g.OW, N).permute(0, 2, 1)            # [b][N][L]
+        gw += torch.matmul(gy, cols.transpose(1, 2)).sum(0)
+        ab += torch.matmul(gy.abs(), cols.abs().transpose(1, 2)).sum(0)
+    reorder = lambda t: t.view(N, g.C, g.KH, g.KW).permute(0, 2, 3, 1).reshape(N, CK)  # noqa: E731
     return reorder(gw), dy.double().reshape(-1, N).sum(0), reorder(ab)
+
+
+# ------------------------------------------------------------------------------------------ transposed conv
+# A Conv2DTranspose is the conv G = DeconvGeom.G with the roles swapped (ops/geometry.py): x [B][H][W][Cin] is G's
+# output gradient, the layer's output [B][OH][OW][F] G's input, w = G's matrix [Cin][KH*KW*F].
+def deconv_fwd_ref(x, w, bias, dgeom, relu):
+    """fp64 [relu](G's data gradient of x + bias) -> [B][OH][OW][F]."""
+    G = DeconvGeom(*dgeom).G
+    y = conv_dgrad_ref(x.reshape(G.y_shape), w, G.x_shape, G)
+    if bias is not None:
+        y += bias.double()
+    return y.relu_() if relu else y
+
+
+def deconv_dgrad_ref(dy, w, dgeom, mask=None):
+    """fp64 G(dy) * [mask > 0] -> [B][H][W][Cin]."""
+    G = DeconvGeom(*dgeom).G
+    return join_ref(conv_fwd_ref(dy.reshape(G.x_shape), w, None, G), None, None, mask)
+
+
+def deconv_wgrad_ref(dy, x, dgeom):
+    """fp64 kernel gradient [Cin][KH*KW*F] (G's, with x and dy exchanged, no bias column), gb [F] = sum dy, and
+    the per-element sum of |x * dy|."""
+    G = DeconvGeom(*dgeom).G
+    gw, _, ab = conv_wgrad_ref(x.reshape(G.y_shape), dy.reshape(G.x_shape), G)
+    return gw, dy.double().reshape(-1, G.C).sum(0), ab
+
+
+# ------------------------------------------------------------------------------------------- depthwise conv
+# Weights [KH][KW][C*M], output channel co reads input channel co // M.  A loop over the KH*KW taps on shifted,
+# strided slices of the padded image: no library conv.
+def _dw_pads(g):
+    return g.pl, pad_after(g.W, g.OW, g.KW, g.sw, g.pl), g.pt, pad_after(g.H, g.OH, g.KH, g.sh, g.pt)
+
+
+def _dw_taps(g):
+    """(kh, kw, row slice, column slice) of every tap: the padded pixels the OH x OW windows read at that tap."""
+    for kh in range(g.KH):
+        for kw in range(g.KW):
+            yield kh, kw, slice(kh, kh + (g.OH - 1) * g.sh + 1, g.sh), slice(kw, kw + (g.OW - 1) * g.sw + 1, g.sw)
+
+
+def _dw_source(x, g):
+    """x [B][H][W][C] -> fp64 padded / cropped [B][PH][PW][C*M] with channel co = input channel co // M."""
+    xp = F.pad(x.double(), (0, 0) + _dw_pads(g))
+    assert tuple(xp.shape[1:3]) == _padded_hw(g)
+    return xp.repeat_interleave(g.M, dim=3) if g.M > 1 else xp
+
+
+def dwconv_fwd_ref(x, w, bias, geom, relu=False):
+    g = DwGeom(*geom)
+    xs, w = _dw_source(x, g), w.double()
+    y = torch.zeros(x.shape[0], g.OH, g.OW, g.C * g.M, dtype=torch.float64, device=x.device)
+    for kh, kw, rows, cols in _dw_taps(g):
+        y += xs[:, rows, cols] * w[kh, kw]
+    if bias is not None:
+        y += bias.double()
+    return y.relu_() if relu else y
+
+
+def dwconv_dgrad_ref(dy, w, geom, mask=None):
+    """fp64 [B][H][W][C]: every tap's dy * w scattered to the pixel it read, summed over the M outputs of a
+    channel; exactly 0 at pixels no window reads; * [mask > 0]."""
+    g = DwGeom(*geom)
+    B, (PH, PW) = dy.shape[0], _padded_hw(g)
+    dy, w = dy.double().reshape(B, g.OH, g.OW, g.C * g.M), w.double()
+    dp = torch.zeros(B, PH, PW, g.C * g.M, dtype=torch.float64, device=dy.device)
+    for kh, kw, rows, cols in _dw_taps(g):
+        dp[:, rows, cols] += dy * w[kh, kw]
+    dp = dp.view(B, PH, PW, g.C, g.M).sum(-1)
+    hh, ww = min(g.H, PH - g.pt), min(g.W, PW - g.pl)
+    dx = torch.zeros(B, g.H, g.W, g.C, dtype=torch.float64, device=dy.device)
+    dx[:, :hh, :ww] = dp[:, g.pt:g.pt + hh, g.pl:g.pl + ww]
+    return join_ref(dx, None, None, mask.reshape(dx.shape) if mask is not None else None)
+
+
+def dwconv_wgrad_ref(dy, x, geom):
+    """fp64 gw [KH][KW][C*M], gb [C*M], and the per-element sum of |dy * x|."""
+    g = DwGeom(*geom)
+    xs, dy = _dw_source(x, g), dy.double().reshape(x.shape[0], g.OH, g.OW, g.C * g.M)
+    gw = torch.zeros(g.KH, g.KW, g.C * g.M, dtype=torch.float64, device=x.device)
+    ab = torch.zeros_like(gw)
+    for kh, kw, rows, cols in _dw_taps(g):
+        prod = xs[:, rows, cols] * dy
+        gw[kh, kw], ab[kh, kw] = prod.sum((0, 1, 2)), prod.abs().sum((0, 1, 2))
+    return gw, dy.sum((0, 1, 2)), ab
 
 
 def join_ref(dx, res, rmask, mask):
@@ -483,3 +603,151 @@ def khead_case(B, K, C, drop, with_idx, bias=True, dp_mask=True, seed=0):
 def mlphead_case(B, dims, with_idx, x_relu, dx_scale, seed=0):
     d = head_ints(gen(1000 * seed + B + sum(dims)), B, dims, with_idx)
     return d, head_ref(d, HEAD_GRAD_SCALE, x_relu=x_relu, dx_scale=dx_scale)
+
+
+# ------------------------------------------------ irregular, transposed and depthwise convs: cases and data
+# tests/test_conv_geometry_exact_gpu.py, tests/test_deconv_exact_gpu.py and tests/test_depthwise_exact_gpu.py run
+# these on the GPU; tests/test_exact_util.py asserts the references and the conditions of exactness for every
+# case without one.
+# (B, H, W, C, N, kernel, strides, padding): none is ``ConvGeom.regular``, so all take the generic kernels
+IRREGULAR_CONVS = [
+    (4, 9, 8, 8, 16, (3, 5), (2, 1), "same"),
+    (4, 16, 16, 16, 32, (3, 3), (2, 2), "same"),
+    (3, 7, 10, 3, 8, (2, 4), (1, 2), "same"),      # LUT gather forward
+    (2, 9, 11, 8, 24, (1, 3), (3, 2), "valid"),
+    (2, 12, 6, 5, 40, (5, 1), (1, 1), "same"),     # LUT gather forward
+    # padding symmetric in one axis only; C = 24: the 32-wide K step crosses taps; M = 108: a partial 64-row
+    # tile; N = 72: a partial 128-wide tile
+    (3, 11, 12, 24, 72, (3, 3), (2, 2), "same"),
+    (5, 7, 7, 1, 8, (2, 2), (3, 3), "same"),       # C = 1; stride > kernel: unread pixels must get dx = 0
+    (2, 10, 10, 40, 136, (3, 2), (1, 1), "same"),  # two 128-wide tiles, the second 8 wide; two wgrad splits
+    (2, 6, 9, 8, 5, (2, 2), (1, 2), "valid"),      # N = 5: LUT data gradient, weight gradient without dvec
+]
+# (B, H, W, Cin, F, kernel, strides, padding) of a Conv2DTranspose: the nine of tests/test_decoder_gpu.py, then
+DECONVS = [
+    (2, 5, 5, 8, 8, (3, 3), (2, 2), "same"),
+    (2, 4, 6, 3, 5, (3, 3), (2, 2), "valid"),
+    (2, 4, 4, 16, 8, (4, 4), (2, 2), "same"),
+    (2, 4, 4, 64, 32, (4, 4), (2, 2), "same"),
+    (2, 8, 8, 64, 64, (3, 3), (1, 1), "same"),
+    (2, 3, 3, 8, 8, (2, 2), (3, 3), "same"),
+    (1, 1, 1, 8, 16, (3, 3), (1, 1), "same"),
+    (2, 5, 4, 8, 8, (5, 3), (1, 2), "same"),
+    (2, 7, 7, 8, 1, (3, 3), (2, 2), "same"),
+    (5, 7, 5, 64, 16, (3, 3), (2, 2), "valid"),    # parity classes of unequal size (15x11 output), partial tiles
+    (5, 8, 8, 64, 32, (4, 4), (2, 2), "same"),     # a parity class spans 2.5 row tiles; wgrad tr with 2 splits
+    (2, 3, 4, 64, 8, (1, 1), (2, 2), "valid"),     # three of the four parity classes have no tap: bias only
+    (2, 5, 3, 128, 64, (4, 4), (2, 2), "same"),    # two 64-channel blocks per tap; input gradient igemm64 FAST
+    (3, 5, 5, 24, 40, (3, 3), (2, 2), "same"),     # generic vector gather with Cin = 24
+    (2, 6, 6, 16, 8, (2, 2), (2, 2), "valid"),     # kernel = stride: every output pixel has exactly one tap
+    (2, 3, 5, 64, 64, (3, 3), (1, 1), "valid"),    # FAST stride 1 in both directions
+]
+# (B, H, W, C, M, kernel, strides, padding) of a DepthwiseConv2D: the fifteen of tests/test_depthwise_gpu.py
+DWCONVS = [
+    (3, 9, 9, 8, 1, (3, 3), (1, 1), "same"),
+    (2, 8, 8, 16, 1, (3, 3), (2, 2), "same"),
+    (2, 9, 9, 16, 1, (3, 3), (2, 2), "same"),
+    (3, 7, 10, 3, 1, (2, 4), (1, 2), "same"),
+    (2, 11, 11, 20, 1, (5, 5), (1, 1), "valid"),
+    (2, 9, 11, 4, 2, (3, 3), (1, 1), "same"),
+    (1, 1, 1, 8, 1, (3, 3), (1, 1), "same"),
+    (5, 17, 17, 72, 1, (3, 3), (1, 1), "same"),
+    (2, 6, 7, 8, 1, (2, 3), (1, 1), "same"),
+    (2, 10, 10, 8, 1, (3, 3), (3, 3), "same"),
+    (2, 10, 9, 8, 1, (3, 3), (1, 1), "valid"),
+    (1, 5, 5, 512, 1, (3, 3), (1, 1), "same"),
+    (1, 4, 5, 320, 1, (2, 3), (1, 1), "same"),
+    (1, 3, 3, 2056, 1, (3, 3), (2, 2), "same"),
+    (1, 3, 4, 150, 2, (2, 2), (1, 1), "valid"),
+]
+DWCONVS_MISALIGNED = [DWCONVS[0], DWCONVS[8]]      # the 3x3 vector kernels and the generic vector kernels
+# the smallest shapes whose launches stride their grid (csrc/dwconv.hip: kDwMaxGrid * 256 = 524288 work items)
+DW_GRID_ITEMS = 2048 * 256
+DWCONVS_GRID = [
+    # 525312 walks of CC = 9 channel vectors, 524288 mod 9 = 2: the second pass reloads another vector's weights
+    # (3x3 forward, data gradient, weight gradient; the weight gradient's 58368 walks / PL = 28 exceed 1024 slabs)
+    (114, 2, 512, 72, 1, (3, 3), (1, 1), "same"),
+    (4, 64, 64, 33, 2, (3, 3), (1, 1), "same"),    # generic scalar kernels, M = 2: 1081344 / 540672 items
+    (2, 23, 23, 128, 2, (2, 2), (1, 1), "same"),   # CO = 256: PL = 1, 1058 positions > 1024 slabs
+]
+
+
+def case_id(c):
+    return f"{c[0]}x{c[1]}x{c[2]}x{c[3]}x{c[4]}_k{c[5][0]}{c[5][1]}_s{c[6][0]}{c[6][1]}_{c[7]}"
+
+
+def _case_seed(c):
+    return sum((i + 1) * int(v) for i, v in enumerate(c[:5])) + 31 * c[5][0] + 37 * c[5][1] + 41 * c[6][0] + 43 * c[6][1]
+
+
+def conv_case(case):
+    """Integer data of an igemm conv case (the values of ``test_conv_exact_on_integers``): x, dy, mask, rmask in
+    {-1, 0, 1}, res in [-2, 2], w [N][KH*KW*C] in {-1, 0, 1} with about 64 non-zeros per reduction, bias in
+    [-3, 3].  -> dict with the ConvGeom ``g`` (CPU fp64)."""
+    g = ConvGeom.build(*case)
+    r = gen(_case_seed(case))
+    T = g.KH * g.KW
+    return {"g": g, "x": ints(r, g.x_shape, -1, 1), "dy": ints(r, g.y_shape, -1, 1),
+            "w": sparse_ints(r, (g.N, T * g.C), -1, 1, weight_density(T * max(g.C, g.N))), "b": ints(r, (g.N,), -3, 3),
+            "res": ints(r, g.x_shape, -2, 2), "rmask": ints(r, g.x_shape, -1, 1), "mask": ints(r, g.x_shape, -1, 1)}
+
+
+def deconv_case(case):
+    """Integer data of a transposed conv case, as :func:`conv_case`: x [B][H][W][Cin] (also the relu' mask of the
+    input gradient, as the layer passes it), dy [B][OH][OW][F], w = G's matrix [Cin][KH*KW*F], bias [F]; ``geom``
+    is the DeconvGeom."""
+    G = ConvGeom.transposed(*case)
+    r = gen(_case_seed(case) + 1)
+    T = G.KH * G.KW
+    return {"geom": G.t_geom, "G": G, "x": ints(r, G.y_shape, -1, 1), "dy": ints(r, G.x_shape, -1, 1),
+            "w": sparse_ints(r, (G.N, T * G.C), -1, 1, weight_density(T * max(G.C, G.N))), "b": ints(r, (G.C,), -3, 3)}
+
+
+def dw_case(case):
+    """Integer data of a depthwise case: x (also the relu' mask), dy in [-2, 2], fp32 weights [KH][KW][C*M] and
+    bias in [-3, 3]: |y| <= KH*KW * 6 + 3 and |dx| <= KH*KW * M * 6."""
+    g = DwGeom.build(*case)
+    r = gen(_case_seed(case) + 2)
+    CO = g.C * g.M
+    return {"geom": g, "x": ints(r, (g.B, g.H, g.W, g.C), -2, 2), "dy": ints(r, (g.B, g.OH, g.OW, CO), -2, 2),
+            "w": ints(r, (g.KH, g.KW, CO), -3, 3), "b": ints(r, (CO,), -3, 3)}
+
+
+def dw_work_items(geom):
+    """Work items of the forward, data-gradient and weight-gradient launches of csrc/dwconv.hip on aligned
+    operands: (image, 8-row chunk, column, channel vector) walks on the 3x3 vector kernels, else one per output
+    vector / element; weight gradient: walks / positions, and the position lanes per workgroup PL."""
+    g = DwGeom(*geom)
+    vec = g.M == 1 and g.C % 8 == 0
+    CO, k3 = g.C * g.M, g.KH == 3 and g.KW == 3
+    cu = CO // 8 if vec else CO
+    chunks = lambda n: -(-n // 8)  # noqa: E731
+    fwd = g.B * chunks(g.OH) * g.OW * cu if vec and k3 and g.sh <= 2 else g.B * g.OH * g.OW * cu
+    dg = g.B * chunks(g.H) * g.W * (g.C // 8) if vec and k3 and (g.sh, g.sw) == (1, 1) else \
+        g.B * g.H * g.W * (g.C // 8 if vec else g.C)
+    wg = g.B * chunks(g.OH) * g.OW if vec and k3 and g.sh <= 2 else g.B * g.OH * g.OW
+    return fwd, dg, wg, 256 // min(cu, 256)
+
+
+def zero_share(t):
+    return float((t == 0).double().mean())
+
+
+def offset_view(t):
+    """The same values as a view that starts one element into a larger buffer: contiguous, not 16-byte aligned."""
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    buf[1:] = t.reshape(-1)
+    v = buf[1:].view(t.shape)
+    assert v.data_ptr() % 16 != 0 and v.is_contiguous()
+    return v
+
+
+def assert_same(got, exp, what):
+    """``torch.equal(got, exp)`` (exp fp64; a NaN left in ``got`` differs), naming the first differing index."""
+    got = got.double()
+    assert got.shape == exp.shape, f"{what}: shape {tuple(got.shape)}, expected {tuple(exp.shape)}"
+    if not torch.equal(got, exp):
+        bad = got != exp
+        i = tuple(bad.nonzero()[0].tolist())
+        raise AssertionError(f"{what}: {int(bad.sum())} of {exp.numel()} elements differ, the first at {i}: "
+                             f"got {float(got[i])}, expected {float(exp[i])}")

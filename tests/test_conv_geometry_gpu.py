@@ -1,6 +1,7 @@
 """GPU conv kernels on irregular geometry (non-square kernels, per-axis strides, asymmetric Keras 'same'):
 the generic implicit-GEMM kernels (csrc/igemm.hip) against the fp32 reference ops, and a Keras model with
-such convs trained on the GPU engine against the CPU engine.  CPU side: tests/test_conv_geometry.py."""
+such convs trained on the GPU engine against the CPU engine.  CPU side: tests/test_conv_geometry.py.  The same
+kernels on integer data, exactly (torch.equal against fp64): tests/test_conv_geometry_exact_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -15,7 +15,10 @@ Tolerances.  The transposed conv runs the conv kernels, so the criterion is thei
 test_conv_geometry_gpu.py): max error <= 3e-2 * max|ref|.  channel_sum is an fp32 sum of bf16 values: per
 channel <= 2e-4 * sum|dy| (tests/test_depthwise_gpu.py).  Up-sampling: nearest forward copies (bitwise); on
 small-integer data every fp32 result is a bf16 value (asserted on the reference first), so nearest backward and
-bilinear (2, 2) are exact; other sizes have inexact weights and one bf16 rounding (2^-9): 1e-2 * max|ref|."""
+bilinear (2, 2) are exact; other sizes have inexact weights and one bf16 rounding (2^-9): 1e-2 * max|ref|.
+
+The transposed conv and channel_sum on integer data, exactly (torch.equal against fp64), over these cases and
+more, with a check that every kernel family is reached: tests/test_deconv_exact_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -6,7 +6,10 @@ engine and through the trainer's captured step.
 Tolerances.  Forward and data gradient are bf16 outputs of fp32 sums: one bf16 rounding is <= 2^-9 relative,
 the bound is 1e-2 * max|ref| (5x the rounding unit).  The weight and bias gradients are fp32 sums of exact
 products: per element <= 2e-4 * sum |dy| |x| (the same sum over absolute values); the worst-case sequential
-bound is n * 2^-24 = 8.6e-5 for the n = 1445 positions of the largest case."""
+bound is n * 2^-24 = 8.6e-5 for the n = 1445 positions of the largest case.
+
+The same kernels on integer data, exactly (torch.equal against fp64), with misaligned operands and shapes large
+enough to stride the grid and to reach the slab cap: tests/test_depthwise_exact_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -1,6 +1,8 @@
 """The reference helpers of tests/exact_util.py themselves (CPU): the tie rule the max-pool helpers encode, the two
 code conventions, agreement with torch's own pooling where no tie is possible; the saturated-head reference against
-fp64 autograd of the same chain with the real softmax, and its exactness conditions at every shape the GPU tests use."""
+fp64 autograd of the same chain with the real softmax, and its exactness conditions at every shape the GPU tests use;
+the conv (any ConvGeom), transposed conv and depthwise conv references against a four-loop tap sum and ops.reference,
+and the conditions of exactness of every case of the irregular, transposed and depthwise exact GPU tests."""
 import pytest
 import torch
 
@@ -117,3 +119,212 @@ def test_head_ref_takes_the_first_maximum_and_its_conditions_bite():
     bad = dict(r, dx=r["dx"] + 1.0 / 1024)
     with pytest.raises(AssertionError, match="bf16"):
         xu.assert_exact_head(bad)
+
+
+# ------------------------------------------------------- irregular, transposed and depthwise conv references
+# Each reference against (1) a direct four-loop tap sum written here, by torch.equal, and (2) ops.reference (fp32,
+# tied to Keras semantics by tests/test_conv_geometry.py) on the same integers with atol = 1e-3: two integer
+# results that differ at all differ by at least 1, so that is a condition, not a tolerance.  Then the conditions
+# under which the GPU tests may compare by torch.equal, for every case they run.
+INT = dict(atol=1e-3, rtol=0)
+# lower bounds on the share of exact zeros (igemm data: masks in {-1, 0, 1} are zero a third of the time; depthwise
+# masks in [-2, 2] a fifth; a pre-ReLU sum of some tens of terms of +-1 is zero a few percent of the time)
+MASK_ZEROS_IGEMM, MASK_ZEROS_DW, SUM_ZEROS = 0.25, 0.15, 0.01
+
+
+def _tap_loop(x, w4, dy, g):
+    """Forward, data gradient and weight gradient of a conv by the definition: y[b, oh, ow, n] = sum over (kh, kw)
+    with ih = oh*sh - pt + kh and iw = ow*sw - pl + kw inside the image of x[b, ih, iw, :] . w4[n, kh, kw, :]."""
+    B = x.shape[0]
+    y, dx, gw = torch.zeros(B, g.OH, g.OW, g.N).double(), torch.zeros(B, g.H, g.W, g.C).double(), torch.zeros_like(w4)
+    for oh in range(g.OH):
+        for ow in range(g.OW):
+            for kh in range(g.KH):
+                for kw in range(g.KW):
+                    ih, iw = oh * g.sh - g.pt + kh, ow * g.sw - g.pl + kw
+                    if 0 <= ih < g.H and 0 <= iw < g.W:
+                        y[:, oh, ow] += x[:, ih, iw] @ w4[:, kh, kw].t()
+                        dx[:, ih, iw] += dy[:, oh, ow] @ w4[:, kh, kw]
+                        gw[:, kh, kw] += dy[:, oh, ow].t() @ x[:, ih, iw]
+    return y, dx, gw.reshape(g.N, -1)
+
+
+def _check_conv_refs(g, x, w, b, dy):
+    """The three conv references of the ConvGeom ``g`` on x [B][H][W][C], dy [B][OH][OW][N], w [N][KH*KW*C]."""
+    y, dx, gw = _tap_loop(x, w.view(g.N, g.KH, g.KW, g.C), dy, g)
+    ry, rdx = xu.conv_fwd_ref(x, w, None, g), xu.conv_dgrad_ref(dy, w, g.x_shape, g)
+    rgw, rgb, rab = xu.conv_wgrad_ref(dy, x, g)
+    assert torch.equal(ry, y) and torch.equal(rdx, dx) and torch.equal(rgw, gw)
+    assert torch.equal(rgb, dy.reshape(-1, g.N).sum(0)) and bool((rab >= rgw.abs()).all())
+    assert torch.equal(xu.conv_fwd_ref(x, w, b, g, relu=True), (y + b).relu())
+    geo = (g.KH, g.KW, g.stride, g.pad)
+    torch.testing.assert_close(ry, ref.conv_fwd(x.float(), w.float(), None, *geo, False, out_hw=(g.OH, g.OW)).double(), **INT)
+    torch.testing.assert_close(rdx, ref.conv_dgrad(dy.float(), w.float(), g.x_shape, *geo).double(), **INT)
+    ow_, ob_ = ref.conv_wgrad(dy.float(), x.float(), *geo)
+    torch.testing.assert_close(rgw, ow_.double(), **INT)
+    torch.testing.assert_close(rgb, ob_.double(), **INT)
+    return ry, rdx, rab
+
+
+def test_conv_refs_keep_their_k_s_p_form():
+    """Existing callers pass one k, one s, one symmetric p: the same values as torch's own unfold with padding p,
+    trailing pixels that no window reads included ((9 + 2 - 3) % 2 == 0 but (8 + 2 - 3) % 2 != 0)."""
+    r = xu.gen(3)
+    for (B, H, W, C, N, k, s, p) in ((2, 9, 8, 3, 4, 3, 2, 1), (2, 7, 6, 2, 5, 4, 2, 1), (1, 6, 6, 3, 2, 2, 3, 0)):
+        x, w = xu.ints(r, (B, H, W, C), -2, 2), xu.ints(r, (N, k * k * C), -2, 2)
+        OH, OW = xu.out_hw(H, W, k, s, p)
+        dy = xu.ints(r, (B, OH, OW, N), -2, 2)
+        g = xu.conv_geom(x.shape, N, k, s, p)
+        assert (g.OH, g.OW) == (OH, OW) and g.pad == (p, p)
+        y, dx, gw = _tap_loop(x, w.view(N, k, k, C), dy, g)
+        assert torch.equal(xu.conv_fwd_ref(x, w, None, k, s, p, False), y)
+        assert torch.equal(xu.conv_dgrad_ref(dy, w, (B, H, W, C), k, s, p), dx)
+        assert torch.equal(xu.conv_wgrad_ref(dy, x, k, s, p)[0], gw)
+
+
+def test_conv_dgrad_ref_is_zero_where_no_window_reads():
+    """A 2x2 kernel at stride 3 under 'same': every third row and column is read by no window."""
+    d = xu.conv_case((5, 7, 7, 1, 8, (2, 2), (3, 3), "same"))
+    g = d["g"]
+    assert (g.OH, g.OW, g.pt, g.pl) == (3, 3, 0, 0)
+    dx = xu.conv_dgrad_ref(d["dy"], d["w"], g.x_shape, g)
+    assert float(dx[:, 2::3].abs().sum()) == 0 and float(dx[:, :, 2::3].abs().sum()) == 0 and float(dx.abs().sum()) > 0
+
+
+@pytest.mark.parametrize("case", xu.IRREGULAR_CONVS, ids=xu.case_id)
+def test_irregular_conv_refs_and_conditions(case):
+    d = xu.conv_case(case)
+    g, x, w, b, dy = d["g"], d["x"], d["w"], d["b"], d["dy"]
+    assert not g.regular
+    y, dx, ab = _check_conv_refs(g, x, w, b, dy)
+    for t in (y, y + b, dx, xu.join_ref(dx, d["res"], d["rmask"], d["mask"])):
+        xu.assert_exact_output(t)
+    assert float(ab.max()) < xu.FP32_INT_MAX and float(dy.abs().sum((0, 1, 2)).max()) < xu.FP32_INT_MAX
+    print(f"max |y| {float((y + b).abs().max())}, max |dx| {float(dx.abs().max())}; zeros: mask "
+          f"{xu.zero_share(d['mask']):.3f} rmask {xu.zero_share(d['rmask']):.3f} y + b {xu.zero_share(y + b):.3f}")
+    assert min(xu.zero_share(d["mask"]), xu.zero_share(d["rmask"])) >= MASK_ZEROS_IGEMM
+    assert xu.zero_share(y + b) >= SUM_ZEROS
+    # the mask rule bites: somewhere mask == 0 sits on a non-zero gradient
+    assert bool(((d["mask"] == 0) & (dx + d["res"] * (d["rmask"] > 0) != 0)).any())
+
+
+@pytest.mark.parametrize("case", xu.DECONVS, ids=xu.case_id)
+def test_deconv_refs_and_conditions(case):
+    d = xu.deconv_case(case)
+    G, x, w, b, dy = d["G"], d["x"], d["w"], d["b"], d["dy"]
+    assert tuple(d["geom"]) == tuple(ops.deconv_geometry(*case))
+    # the conv G on (its input = dy, its output gradient = x), then the roles swapped
+    gy, gdx, _ = _check_conv_refs(G, dy, w, torch.zeros(G.N).double(), x)
+    y = xu.deconv_fwd_ref(x, w, None, d["geom"], False)
+    assert torch.equal(y, gdx.reshape(y.shape))
+    assert torch.equal(xu.deconv_fwd_ref(x, w, b, d["geom"], True), (gdx + b).relu())
+    assert torch.equal(xu.deconv_dgrad_ref(dy, w, d["geom"], None), gy)
+    assert torch.equal(xu.deconv_dgrad_ref(dy, w, d["geom"], x), gy * (x > 0))
+    gw, gb, ab = xu.deconv_wgrad_ref(dy, x, d["geom"])
+    assert torch.equal(gw, xu.conv_wgrad_ref(x, dy, G)[0]) and torch.equal(gb, dy.reshape(-1, G.C).sum(0))
+    # ops' own CPU path of the three launches
+    oy = ops.deconv_fwd(x.float(), w.float(), None, b.float(), torch.empty(y.shape), d["geom"])
+    odx = ops.deconv_dgrad(dy.float(), w.float(), torch.empty(gy.shape), d["geom"], mask=x.float())
+    torch.testing.assert_close(y + b, oy.double(), **INT)
+    torch.testing.assert_close(gy * (x > 0), odx.double(), **INT)
+    ogw, ogb = torch.empty(gw.shape), torch.empty(G.C)
+    ops.deconv_wgrad(dy.float(), x.float(), ogw, ogb, None, d["geom"])
+    torch.testing.assert_close(gw, ogw.double(), **INT)
+    torch.testing.assert_close(gb, ogb.double(), **INT)
+    for t in (y, y + b, gy):
+        xu.assert_exact_output(t)
+    assert float(ab.max()) < xu.FP32_INT_MAX and float(dy.abs().sum((0, 1, 2)).max()) < xu.FP32_INT_MAX
+    print(f"max |y| {float((y + b).abs().max())}, max |dx| {float(gy.abs().max())}; zeros: mask {xu.zero_share(x):.3f} "
+          f"y + b {xu.zero_share(y + b):.3f}")
+    if x.numel() >= 512:
+        assert xu.zero_share(x) >= MASK_ZEROS_IGEMM
+    if y.numel() >= 512:
+        assert xu.zero_share(y + b) >= SUM_ZEROS
+    assert bool(((x == 0) & (gy != 0)).any()) or x.numel() < 64
+
+
+def test_case_lists_begin_with_the_tolerance_tests_cases():
+    import test_decoder_gpu
+    import test_depthwise_gpu
+    import test_conv_geometry_gpu
+
+    assert xu.DECONVS[:9] == test_decoder_gpu.CASES and len(xu.DECONVS) == 16
+    assert xu.DWCONVS == test_depthwise_gpu.CASES and len(xu.DWCONVS) == 15
+    assert xu.IRREGULAR_CONVS[:5] == test_conv_geometry_gpu.GEOMS and len(xu.IRREGULAR_CONVS) == 9
+
+
+def _dw_tap_loop(x, w, dy, g):
+    B, CO = x.shape[0], g.C * g.M
+    xr = x.repeat_interleave(g.M, dim=3)   # channel co reads input co // M
+    y, dxr, gw = torch.zeros(B, g.OH, g.OW, CO).double(), torch.zeros(B, g.H, g.W, CO).double(), torch.zeros_like(w)
+    for oh in range(g.OH):
+        for ow in range(g.OW):
+            for kh in range(g.KH):
+                for kw in range(g.KW):
+                    ih, iw = oh * g.sh - g.pt + kh, ow * g.sw - g.pl + kw
+                    if 0 <= ih < g.H and 0 <= iw < g.W:
+                        y[:, oh, ow] += xr[:, ih, iw] * w[kh, kw]
+                        dxr[:, ih, iw] += dy[:, oh, ow] * w[kh, kw]
+                        gw[kh, kw] += (dy[:, oh, ow] * xr[:, ih, iw]).sum(0)
+    return y, dxr.view(B, g.H, g.W, g.C, g.M).sum(-1), gw
+
+
+def _check_dw_refs(d):
+    g, x, w, b, dy = d["geom"], d["x"], d["w"], d["b"], d["dy"]
+    y, dx, gw = _dw_tap_loop(x, w, dy, g)
+    ry, rdx = xu.dwconv_fwd_ref(x, w, None, g), xu.dwconv_dgrad_ref(dy, w, g)
+    rgw, rgb, rab = xu.dwconv_wgrad_ref(dy, x, g)
+    assert torch.equal(ry, y) and torch.equal(rdx, dx) and torch.equal(rgw, gw)
+    assert torch.equal(rgb, dy.sum((0, 1, 2))) and bool((rab >= rgw.abs()).all())
+    assert torch.equal(xu.dwconv_fwd_ref(x, w, b, g, True), (y + b).relu())
+    assert torch.equal(xu.dwconv_dgrad_ref(dy, w, g, x), dx * (x > 0))
+    torch.testing.assert_close(ry + b, ref.dwconv_fwd(x.float(), w.float(), b.float(), g).double(), **INT)
+    torch.testing.assert_close(rdx * (x > 0), ref.dwconv_dgrad(dy.float(), w.float(), g, x.float()).double(), **INT)
+    ow_, ob_ = ref.dwconv_wgrad(dy.float(), x.float(), g, True)
+    torch.testing.assert_close(rgw, ow_.double(), **INT)
+    torch.testing.assert_close(rgb, ob_.double(), **INT)
+    return ry, rdx, rab
+
+
+@pytest.mark.parametrize("case", xu.DWCONVS, ids=xu.case_id)
+def test_dwconv_refs_and_conditions(case):
+    d = xu.dw_case(case)
+    g, x, b, dy = d["geom"], d["x"], d["b"], d["dy"]
+    y, dx, ab = _check_dw_refs(d)
+    T = g.KH * g.KW
+    assert float((y + b).abs().max()) <= T * 6 + 3 <= xu.BF16_INT_MAX and float(dx.abs().max()) <= T * g.M * 6 <= xu.BF16_INT_MAX
+    for t in (y, y + b, dx):
+        xu.assert_exact_output(t)
+    assert float(ab.max()) < xu.FP32_INT_MAX and float(dy.abs().sum((0, 1, 2)).max()) < xu.FP32_INT_MAX
+    print(f"max |y| {float((y + b).abs().max())}, max |dx| {float(dx.abs().max())}; zeros: mask {xu.zero_share(x):.3f} "
+          f"y + b {xu.zero_share(y + b):.3f}")
+    if x.numel() >= 512:
+        assert xu.zero_share(x) >= MASK_ZEROS_DW and xu.zero_share(y + b) >= SUM_ZEROS
+        assert bool(((x == 0) & (dx != 0)).any())
+
+
+@pytest.mark.parametrize("M", [1, 2])
+def test_dwconv_refs_with_a_depth_multiplier_and_unread_pixels(M):
+    """M = 1 and M = 2 on a geometry with asymmetric 'same' padding, and on one whose stride exceeds the kernel."""
+    for case in ((2, 8, 7, 3, M, (3, 2), (2, 1), "same"), (2, 7, 7, 2, M, (2, 2), (3, 3), "same")):
+        _, dx, _ = _check_dw_refs(xu.dw_case(case))
+    assert float(dx[:, 2::3].abs().sum()) == 0 and float(dx[:, :, 2::3].abs().sum()) == 0 and float(dx.abs().sum()) > 0
+
+
+@pytest.mark.parametrize("case", xu.DWCONVS_GRID, ids=xu.case_id)
+def test_dwconv_grid_stride_cases_stride_and_stay_exact(case):
+    """The large cases, bounded from the value ranges alone (x, dy in [-2, 2], w, bias in [-3, 3]): |y| <= 9*6 + 3,
+    |dx| <= 9*M*6, every weight-gradient sum below 4 * positions; and each launch it is there for does stride."""
+    g = ops.dwconv_geometry(*case)
+    T, P = g.KH * g.KW, g.B * g.OH * g.OW
+    assert T * 6 + 3 <= xu.BF16_INT_MAX and T * g.M * 6 <= xu.BF16_INT_MAX and 4 * P < xu.FP32_INT_MAX
+    assert g.B * max(g.H * g.W * g.C, g.OH * g.OW * g.C * g.M) <= 10 << 20
+    fwd, dg, wg, PL = xu.dw_work_items(g)
+    print(f"work items: forward {fwd}, data gradient {dg}, weight gradient {wg} at {PL} lanes per slab")
+    if case == xu.DWCONVS_GRID[0]:
+        assert fwd == dg == 525312 > xu.DW_GRID_ITEMS and xu.DW_GRID_ITEMS % (g.C // 8) == 2
+        assert PL == 28 and -(-wg // PL) > 1024
+    elif case == xu.DWCONVS_GRID[1]:
+        assert (fwd, dg) == (1081344, 540672) and dg > xu.DW_GRID_ITEMS
+    else:
+        assert PL == 1 and wg == 1058 > 1024

@@ -120,6 +120,10 @@ CONVS = [  # B, H, W, C, N, k, stride, pad
     # stride-2 data gradients over parity classes (igemm64 PAR): odd sizes, zero-tap classes of a 1x1
     (3, 9, 7, 64, 64, 3, 2, 1),
     (2, 7, 9, 128, 64, 1, 2, 0),
+    # an even kernel at stride 2 (the usual decoder / down-sampling layer): the data gradient on igemm64 FAST +
+    # parity classes, and on plain igemm64
+    (2, 8, 8, 64, 64, 4, 2, 1),
+    (3, 10, 6, 16, 24, 4, 2, 1),
 ]
 
 
